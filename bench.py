@@ -10,9 +10,13 @@ ranks (strong scaling: the 1 M-pair system is fixed) with one all-reduce of the 
 kinetic-energy sums per thermostat half step.  The headline value of a sharded run uses RCCL
 (the library's own ncclAllReduce on its device buffer, captured into the step's hipGraph; torch.distributed's
 all_reduce through the hook where that cannot be had), as
-BASELINE.json's north_star names it; the library's mailbox exchange (stores into every peer's mailbox
+BASELINE.json's north_star names it; with --full, the library's mailbox exchange (stores into every peer's mailbox
 over xGMI, waited for inside the rescale launch) is measured right after it and reported beside it as
 `extra.mailbox`, together with its validation verdict against the RCCL run.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the headline (`value`, `ms_per_step`, `config`).
+--full adds what takes runs of its own: the per-kernel table, the roofline, the integrator-only leg, the extra legs
+and the CPU baseline.  --dump-outputs DIR writes what the timed steps computed (see dump_outputs).
 
 `python bench.py --gpus N` from a plain shell starts its own N ranks (one per GPU) through
 torch.distributed.run before anything touches a GPU; under a launcher (WORLD_SIZE set) it is one of the ranks.
@@ -38,6 +42,11 @@ BACKEND = os.environ.get("TGNH_BENCH_BACKEND", "nccl")
 CDEV = "cuda" if BACKEND == "nccl" else "cpu"          # where the small tensors of the setup collectives live
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md; ~6.3 TB/s measured achievable)
+
+# --dump-outputs: positions and velocities of at most this many particle slots (float64: 48 MiB), the rest is a few thermostat
+# numbers; larger systems are sampled with a fixed seed, so two builds of the project write the same slots
+DUMP_MAX_ROWS = 1 << 20
+DUMP_SEED = 20191024
 
 
 def parse():
@@ -84,6 +93,14 @@ def parse():
     p.add_argument("--probe-timeout", type=float, default=90.0, help="seconds the main run gives the RCCL-site probe")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-extra", action="store_true", help="skip the extra single-precision / variant legs")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline: per-kernel table (instrumented repeat), roofline, integrator-only leg, "
+                        "device copy bandwidth, extra legs (other variants / precisions / exchange) and the CPU baseline. "
+                        "Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write what the headline leg's last step left a caller (positions, velocities "
+                        f"of a fixed seeded sample of at most {DUMP_MAX_ROWS} particle slots; thermostat state and kinetic "
+                        "energies) as DIR/<name>.npy, float64")
     return p.parse_args()
 
 
@@ -238,15 +255,17 @@ def dominant_kid(variant):
     return _lib.KID_STEP if variant in ("resident", "plain-resident") else _lib.KID_SKD      # (plain-resident-trust: the begin half is the tile launch)
 
 
-def timed_run(ctx, steps, warmup, world, graph_steps=0, dom_kid=0):
+def timed_run(ctx, steps, warmup, world, graph_steps=0, dom_kid=0, instrument=True, after=None):
     """W untimed warm-up steps, then exactly `steps` steps between barrier + synchronize pairs; max over ranks.
     graph_steps > 0: the steps are replays of a hipGraph holding graph_steps steps (+ an eager remainder).
-    Leaves ctx.leg = what the JSON line reports for this leg, including the sum of the per-kernel times of one step
-    (instrumented repeat) and a `suspect` mark when the timed region was more than 1.3x that sum."""
+    after(ctx), if given, runs right after the timed region, before anything steps the state further.
+    Leaves ctx.leg = what the JSON line reports for this leg; with `instrument` also the sum of the per-kernel times of one
+    step (instrumented repeat) and a `suspect` mark when the timed region was more than 1.3x that sum."""
     import torch
     import torch.distributed as dist
-    ctx.timing(True)               # creates the HIP-event pool now, outside the timed region
-    ctx.timing(False)
+    if instrument:
+        ctx.timing(True)           # creates the HIP-event pool now, outside the timed region
+        ctx.timing(False)
     ctx.step(warmup)
     torch.cuda.synchronize()
     replay = None
@@ -266,7 +285,7 @@ def timed_run(ctx, steps, warmup, world, graph_steps=0, dom_kid=0):
             replay()                                   # first replay = the steps the capture recorded; untimed
             torch.cuda.synchronize()
     ctx.graph_used = replay is not None
-    if replay is None:
+    if replay is None and instrument:
         ctx.timing(2 + dom_kid)    # HIP events around the dominant kernel only: 2 records per step
     # Python's cyclic garbage collector stays out of the timed region (as in `timeit`): a full pass landing inside it is a
     # host-side stall of milliseconds to tens of milliseconds -- that was the leg the driver's round-1 record had at
@@ -295,9 +314,15 @@ def timed_run(ctx, steps, warmup, world, graph_steps=0, dom_kid=0):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     dom = None
-    if replay is None:
+    if replay is None and instrument:
         ctx.timing(False)
         dom = ctx.timing_read(dom_kid)                 # (total ms, launches) of the dominant kernel inside the timed region
+    if after is not None:
+        after(ctx)
+    ms = dt / steps * 1e3
+    if not instrument:
+        ctx.leg = {"steps_per_s": round(steps / dt, 2), "ms_per_step": round(ms, 4), "host_enqueue_ms": round(t_enq * 1e3, 3)}
+        return dt
     # full per-kernel table: an instrumented repeat of the same steps right after the timed region (event records
     # around all kernels cost ~20 us per step, which is why they are not inside it)
     nrep = max(1, min(steps, 200))
@@ -308,7 +333,6 @@ def timed_run(ctx, steps, warmup, world, graph_steps=0, dom_kid=0):
     ctx.dominant_in_timed_region = dom
     rows = kernel_table(ctx)
     sum_us = sum(v["avg_us"] * v["launches"] for v in rows.values()) / nrep
-    ms = dt / steps * 1e3
     ctx.leg = {"steps_per_s": round(steps / dt, 2), "ms_per_step": round(ms, 4), "instrumented_steps": nrep,
                "sum_kernels_us_per_step": round(sum_us, 2), "host_enqueue_ms": round(t_enq * 1e3, 3),
                "suspect": bool(sum_us > 0 and ms * 1e3 > 1.3 * sum_us), "kernels": rows}
@@ -405,6 +429,37 @@ def kernel_table(ctx):
             rows[name] = {"launches": n, "avg_us": round(avg_us, 3), "algorithmic_MB": round(b / 1e6, 3),
                           "GBps": round(b / (avg_us * 1e-6) / 1e9, 1) if b else None}
     return rows
+
+
+def dump_rows(num_particles):
+    """the particle slots --dump-outputs writes, ascending: all of them, or a fixed seeded sample of DUMP_MAX_ROWS"""
+    if num_particles <= DUMP_MAX_ROWS:
+        return np.arange(num_particles)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(num_particles, DUMP_MAX_ROWS, replace=False))
+
+
+def dump_outputs(ctx, directory, system, rank, world):
+    """What the headline leg left a caller after its last timed step, as DIR/<name>.npy (float64): the thermostat state
+    (eta, etaDot) and the per-thermostat kinetic energies of that step, replicated over the ranks, and positions and
+    velocities (getState's, a deferred step's owed half kick applied) of the slots dump_rows picks, in global slot order
+    (collective: the ranks' shards are gathered to rank 0)."""
+    import torch.distributed as dist
+    from openmm_drudenose_amd.system import shard_bounds
+    lo, hi = (0, system.num_particles) if world == 1 else shard_bounds(system, world)[rank:rank + 2]
+    rows = dump_rows(system.num_particles)
+    mine = rows[(rows >= lo) & (rows < hi)] - lo
+    out = {"thermostat_eta": ctx.thermostat_state(0), "thermostat_eta_dot": ctx.thermostat_state(1),
+           "thermostat_kinetic_energies": ctx.last_kinetic_energies()}
+    pv = (ctx.getPositions()[mine], ctx.getVelocities()[mine])
+    if world > 1:
+        every = [None] * world
+        dist.all_gather_object(every, pv)
+        pv = tuple(np.concatenate([e[k] for e in every]) for k in range(2))
+    out["positions"], out["velocities"] = pv
+    if rank == 0:
+        os.makedirs(directory, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, np.float64))
 
 
 def csrc_sha():
@@ -516,7 +571,7 @@ def side_leg_in_children(args, other, rank, world, argv):
     # (under torchrun the ranks' rendezvous is the agent's store; the children make their own on the new port)
     env = {k: v for k, v in os.environ.items() if not k.startswith("TORCHELASTIC_")}
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port[0]))
-    keep = child_argv(argv, ("--side-leg", "--no-extra", "--probe-rccl-site"), ("--exchange",))
+    keep = child_argv(argv, ("--side-leg", "--no-extra", "--probe-rccl-site"), ("--exchange", "--dump-outputs"))
     cmd = [sys.executable, os.path.abspath(__file__)] + keep + ["--exchange", other, "--side-leg", "--no-cpu-baseline"]
     info = {"measured_by": "child ranks with a process group of their own"}
     try:
@@ -569,7 +624,7 @@ def probe_rccl_site_in_children(args, rank, world, argv):
     dist.broadcast_object_list(port, src=0)
     env = {k: v for k, v in os.environ.items() if not k.startswith("TORCHELASTIC_")}
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port[0]))
-    cmd = [sys.executable, os.path.abspath(__file__)] + child_argv(argv, ("--side-leg", "--no-extra", "--probe-rccl-site"), ("--exchange",)) \
+    cmd = [sys.executable, os.path.abspath(__file__)] + child_argv(argv, ("--side-leg", "--no-extra", "--probe-rccl-site"), ("--exchange", "--dump-outputs")) \
         + ["--probe-rccl-site", "--no-cpu-baseline", "--no-extra"]
     ok, why = False, None
     try:
@@ -647,6 +702,20 @@ def step_model_bytes(num_slots, precision, variant):
     return num_slots * per
 
 
+def headline_record(args, world, dt, config):
+    """The result line's headline: `value` and `ms_per_step` are the timed region's, exactly --steps steps (max over ranks)."""
+    return {
+        "metric": "integrator steps/sec at 1M Drude pairs",
+        "value": round(args.steps / dt, 3), "unit": "steps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 5),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f32" if args.precision == "single" else "f64",
+        "data": "synthetic",
+        "config": config,
+    }
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -712,7 +781,7 @@ def main():
     use_graph = args.graph == "on" or (args.graph == "auto" and world > 1)
     gsteps = max(1, min(args.graph_steps, args.steps)) if use_graph else 0
 
-    def run_leg(exchange):
+    def run_leg(exchange, after=None):
         """one timed run of the main configuration with the given exchange -> (ctx, seconds) ; ctx still open"""
         ctx = build_context(args, system, group, ngroups, rank, world, args.precision, args.variant)
         if exchange == "mailbox" and not attach_mailbox(ctx, rank, world):
@@ -720,7 +789,7 @@ def main():
             return None, None
         # (rehearsals over gloo: its all_reduce cannot be captured into a hipGraph, RCCL's can)
         g = 0 if (exchange == "rccl" and BACKEND != "nccl") else gsteps
-        dt = timed_run(ctx, args.steps, args.warmup, world, g, dominant_kid(args.variant))
+        dt = timed_run(ctx, args.steps, args.warmup, world, g, dominant_kid(args.variant), instrument=args.full, after=after)
         return ctx, dt
 
     def side_leg(other):
@@ -764,19 +833,48 @@ def main():
         mailbox_info = {"validated_against_rccl": ok}
         if not ok:
             raise SystemExit("bench.py: --exchange mailbox, but the mailbox exchange did not validate against rccl on this node")
-    ctx, dt = run_leg(headline_exchange)
+    dump = None
+    if args.dump_outputs:
+        def dump(c):
+            dump_outputs(c, args.dump_outputs, system, rank, world)
+    ctx, dt = run_leg(headline_exchange, after=dump)
     if ctx is None:
         raise SystemExit("bench.py: the mailbox exchange could not be attached")
     if ctx.exchange == "mailbox" and not all_ranks_agree((ctx.status_flags() & 4) == 0):
         raise SystemExit("bench.py: the mailbox exchange timed out inside the timed run")
     graph_used = ctx.graph_used
-    step_kernel_name = ctx.resident_kernel() or "step_kernel"
     exchange_used = ctx.exchange
     rccl_site = ctx.rccl_site
+    local_slots = ctx.n
+    harness_force = ctx.sites_kind()                   # how the call-out inside `value` found its tether sites: lattice | packed | x0
+    config = {
+        "workload": f"SWM4-NDP water box, {args.molecules} molecules = {system.num_particles} particle slots, "
+                    f"{system.num_pairs} Drude pairs, 1 temperature group (+ molecular-COM and Drude thermostats), "
+                    f"{args.mode} mode, {args.precision} precision, numNHChains={args.chains}, hard wall "
+                    f"{args.hardwall} nm, harness force call-out inside the timed region (harness_force: {harness_force})",
+        "harness_force": harness_force,
+        "precision": args.precision, "variant": args.variant,
+        "hipgraph": graph_used,
+        "parallelism": f"particle-sharded x{world} (whole molecules), one KE all-reduce per step",
+        "exchange": exchange_used, "rccl_ranks": ranks_met if use_dist else None,
+        "rccl_site": rccl_site if exchange_used == "rccl" else None,
+        "rccl_site_probe": RCCL_SITE_OK,          # what child ranks found when they tried the library's site first (None: not probed)
+        "slots_per_gpu": local_slots,
+        "csrc_sha": csrc_sha(),
+    }
+    assert ctx.check() == 0
+    if not args.full:                                  # a plain run: the headline and nothing that takes a run of its own
+        close_sharded(ctx)
+        if rank == 0:
+            os.write(real_stdout, (json.dumps(headline_record(args, world, dt, config)) + "\n").encode())
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    step_kernel_name = ctx.resident_kernel() or "step_kernel"
     headline_ranks = per_rank_exchange_report(ctx, exchange_used, world) if use_dist else None
     leg = ctx.leg
     rows = leg["kernels"]
-    assert ctx.check() == 0
     # dominant kernel: step_kernel (resident variant: the whole step but the force call-out) or the fused rescale +
     # half kick + drift (+ hard wall) pass; a handle that cannot run step_kernel (RCCL hook) falls back to the passes
     dkid = dominant_kid(args.variant)
@@ -791,8 +889,6 @@ def main():
         dom = dict(rows.get(dom_name), where="HIP events in the instrumented repeat right after the timed region "
                                              "(the region itself was a hipGraph replay, or ran another launch structure than asked for)")
     achieved = bytes_dom / (dom["avg_us"] * 1e-6) / 1e9
-    local_slots = ctx.n
-    harness_force = ctx.sites_kind()                   # how the call-out inside `value` found its tether sites: lattice | packed | x0
     int_only = integrator_only_run(ctx, args.steps, world, gsteps)
     close_sharded(ctx)
 
@@ -834,34 +930,15 @@ def main():
     if rank == 0:
         b_step = step_model_bytes(system.num_particles, args.precision, args.variant)
         traffic, traffic_path = pmc_traffic(args.precision, local_slots, args.variant) if world == 1 else (None, None)
-        out = {
-            "metric": "integrator steps/sec at 1M Drude pairs",
-            "value": round(args.steps / dt, 3), "unit": "steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 5),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32" if args.precision == "single" else "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": f"SWM4-NDP water box, {args.molecules} molecules = {system.num_particles} particle slots, "
-                            f"{system.num_pairs} Drude pairs, 1 temperature group (+ molecular-COM and Drude thermostats), "
-                            f"{args.mode} mode, {args.precision} precision, numNHChains={args.chains}, hard wall "
-                            f"{args.hardwall} nm, harness force call-out inside the timed region (harness_force: {harness_force})",
-                "harness_force": harness_force,
-                "precision": args.precision, "variant": args.variant,
-                "variant_ran": args.variant if dkid == dominant_kid(args.variant) else {"resident": "defer", "plain-resident": "plain", "plain-resident-trust": "plain-trust"}.get(args.variant, args.variant),
-                "hipgraph": graph_used,
-                "parallelism": f"particle-sharded x{world} (whole molecules), one KE all-reduce per step",
-                "exchange": exchange_used, "rccl_ranks": ranks_met if use_dist else None,
-                "rccl_site": rccl_site if exchange_used == "rccl" else None,
-                "rccl_site_probe": RCCL_SITE_OK,          # what child ranks found when they tried the library's site first (None: not probed)
-                "per_rank": headline_ranks,
-                "slots_per_gpu": local_slots,
-                "model_bytes_per_step": b_step,
-                "step_GBps_vs_model": round(b_step / (dt / args.steps) / 1e9 / world, 1),
-                "sum_kernels_us_per_step": leg["sum_kernels_us_per_step"], "suspect": leg["suspect"],
-                "csrc_sha": csrc_sha(),
-            },
+        config.update({
+            "variant_ran": args.variant if dkid == dominant_kid(args.variant) else {"resident": "defer", "plain-resident": "plain", "plain-resident-trust": "plain-trust"}.get(args.variant, args.variant),
+            "per_rank": headline_ranks,
+            "model_bytes_per_step": b_step,
+            "step_GBps_vs_model": round(b_step / (dt / args.steps) / 1e9 / world, 1),
+            "sum_kernels_us_per_step": leg["sum_kernels_us_per_step"], "suspect": leg["suspect"],
+        })
+        out = headline_record(args, world, dt, config)
+        out.update({
             "roofline": {"bound": "hbm", "kernel": step_kernel_name if dkid == _lib.KID_STEP else "tile_kernel<scale+kick+drift>",
                          "achieved": round(achieved, 1),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
@@ -873,7 +950,7 @@ def main():
                          "device_copy_GBps": round(copy_gbps, 1),
                          "frac_of_device_copy": round(achieved / copy_gbps, 4)},
             "kernels": rows,
-        }
+        })
         # `value` times whole steps, the harness force call-out included (in a real context that slot is OpenMM's
         # calcForcesAndEnergy).  The integrator's own launches alone (SURVEY 8d reports the force kernel separately):
         own = sum(v["avg_us"] * v["launches"] for k, v in rows.items() if k != "harness force") / leg["instrumented_steps"]

@@ -46,3 +46,35 @@ def test_step_model_bytes_follow_the_variant():
     assert bench.step_model_bytes(n, "mixed", "plain-trust") == n * 296    # ... without the begin half's KE pass
     assert bench.step_model_bytes(n, "mixed", "defer") == n * 208       # 3V + 2F + 2X
     assert bench.step_model_bytes(n, "mixed", "plain-resident") == n * 328   # 6V + 3F + 2X
+
+
+def test_dump_outputs_are_a_fixed_sample_within_budget(tmp_path):
+    """--dump-outputs: every slot of a small box, a fixed seeded sample of a large one, float64, at most 64 MB in all."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    from openmm_drudenose_amd import synth
+    rows = bench.dump_rows(5_000_000)
+    assert np.array_equal(rows, bench.dump_rows(5_000_000))                       # the same slots in every run
+    assert len(rows) == bench.DUMP_MAX_ROWS and np.all(np.diff(rows) > 0) and rows[-1] < 5_000_000
+    assert 2 * len(rows) * 3 * 8 + 4096 <= 64e6                                   # positions + velocities + thermostat numbers
+    s, _, _ = synth.water_box(300)
+
+    class Context:                                                                # stand-in for HipContext's queries
+        def thermostat_state(self, which):
+            return np.arange(6.0) + which
+
+        def last_kinetic_energies(self):
+            return np.ones(3, np.float32)
+
+        def getPositions(self):
+            return s.positions.copy()
+
+        def getVelocities(self):
+            return s.velocities.copy()
+    bench.dump_outputs(Context(), str(tmp_path), s, 0, 1)
+    got = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert sorted(got) == ["positions", "thermostat_eta", "thermostat_eta_dot", "thermostat_kinetic_energies", "velocities"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["positions"], s.positions) and np.array_equal(got["velocities"], s.velocities)
+    assert np.array_equal(got["thermostat_eta_dot"], np.arange(6.0) + 1)

@@ -23,7 +23,7 @@ def _bench(argv, **env):
 
 @pytest.mark.gpu
 def test_two_rank_rehearsal_reports_both_exchanges():
-    p = _bench(["--gpus", "2", "--molecules", "20000", "--steps", "100", "--warmup", "10"])
+    p = _bench(["--gpus", "2", "--molecules", "20000", "--steps", "100", "--warmup", "10", "--full"])
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout.decode()
@@ -45,7 +45,7 @@ def test_two_rank_rehearsal_reports_both_exchanges():
 @pytest.mark.gpu
 def test_a_side_leg_that_dies_does_not_take_the_headline_with_it():
     # the children are told to stop at once (their time limit is zero seconds): the run still ends with its headline line
-    p = _bench(["--gpus", "2", "--molecules", "20000", "--steps", "50", "--warmup", "5", "--side-leg-timeout", "0.001"])
+    p = _bench(["--gpus", "2", "--molecules", "20000", "--steps", "50", "--warmup", "5", "--side-leg-timeout", "0.001", "--full"])
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     j = json.loads([ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")][0])
     assert j["n_gpus"] == 2 and j["value"] > 0 and j["config"]["exchange"] == "rccl"

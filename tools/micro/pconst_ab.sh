@@ -7,7 +7,7 @@
 out=gpurun_out/$1; mkdir -p $out
 one() {  # label lib molecules extra-args...
   local label=$1 lib=$2 m=$3; shift 3
-  TGNH_LIB=$lib timeout -k 10 200 python bench.py --molecules $m --variant resident --no-extra --no-cpu-baseline "$@" 2>> $out/ab.err | python -c "
+  TGNH_LIB=$lib timeout -k 10 200 python bench.py --full --molecules $m --variant resident --no-extra --no-cpu-baseline "$@" 2>> $out/ab.err | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$label', $m, d['config']['variant_ran'], d['value'], {k:v['avg_us'] for k,v in d['kernels'].items()})" | tee -a $out/ab.txt
 }
 for i in 1 2 3; do

@@ -26,7 +26,7 @@ BENCH = os.path.join(ROOT, "bench.py")
 
 
 def bench(env, args):
-    r = subprocess.run([sys.executable, BENCH, "--no-cpu-baseline", "--no-extra", *args], env=env, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, BENCH, "--full", "--no-cpu-baseline", "--no-extra", *args], env=env, capture_output=True, text=True)
     if r.returncode:
         return None, r.stderr[-300:]
     return json.loads(r.stdout.strip().splitlines()[-1]), None

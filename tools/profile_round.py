@@ -90,7 +90,7 @@ def main():
     prof = os.path.join(ROOT, "gpurun_out", "profiles_out")
     os.makedirs(prof, exist_ok=True)
     bench = ["python3", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(a.steps), "--warmup", str(a.warmup),
-             "--molecules", str(a.molecules), "--variant", a.variant]
+             "--molecules", str(a.molecules), "--variant", a.variant, "--full"]
     lean = bench + ["--no-extra", "--no-cpu-baseline"]
 
     # 1. kernel trace + stats of the bench command itself

@@ -21,11 +21,11 @@ for v in "--variant resident" "--variant resident --dist" "--variant defer"; do
     timeout -k 10 300 python3 tools/step_gaps.py $tag --molecules 125000 $v > /dev/null 2>&1 || { echo "step_gaps $v failed"; exit 1; }
 done
 timeout -k 10 300 python3 tools/step_gaps.py $tag --molecules 1000000 --variant resident > /dev/null 2>&1 || { echo "step_gaps 5M failed"; exit 1; }
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $out/bench_driver_shape.json 2> $out/bench_driver_shape.err || { echo "bench (driver shape) failed"; exit 1; }
-timeout -k 10 300 python bench.py --no-extra > $out/bench_default_run.json 2> $out/bench_default_run.err || { echo "bench (default) failed"; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $out/bench_driver_shape.json 2> $out/bench_driver_shape.err || { echo "bench (driver shape) failed"; exit 1; }
+timeout -k 10 300 python bench.py --full --no-extra > $out/bench_default_run.json 2> $out/bench_default_run.err || { echo "bench (default) failed"; exit 1; }
 : > $out/gather_vs_tiled.txt
 for m in 1000000 125000; do for v in plain-gather plain; do
-    timeout -k 10 300 python bench.py --molecules $m --variant $v --no-extra --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null \
+    timeout -k 10 300 python bench.py --full --molecules $m --variant $v --no-extra --no-cpu-baseline --steps 200 --warmup 20 2>/dev/null \
       | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$m $v', d['value'], {k:v['avg_us'] for k,v in d['kernels'].items()})" >> $out/gather_vs_tiled.txt || { echo "gather bench failed"; exit 1; }
 done; done
 cat $out/gather_vs_tiled.txt

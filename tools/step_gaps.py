@@ -39,7 +39,7 @@ def main():
         shutil.rmtree(scratch, ignore_errors=True)
         os.makedirs(scratch)
         cmd = ["rocprofv3", "--kernel-trace", "-d", scratch, "--output-format", "csv", "--", "python3", os.path.join(ROOT, "bench.py"),
-               "--molecules", str(a.molecules), "--variant", a.variant, "--graph", "on", "--steps", "2000", "--warmup", "100", "--no-extra", "--no-cpu-baseline"]
+               "--molecules", str(a.molecules), "--variant", a.variant, "--graph", "on", "--steps", "2000", "--warmup", "100", "--full", "--no-extra", "--no-cpu-baseline"]
         env = dict(os.environ, TMPDIR="/tmp")
         if a.dist:
             env["TGNH_FORCE_DIST"] = "1"
