@@ -962,7 +962,8 @@ extern "C" tgnh_status tgnh_exchange_create(tgnh_handle h, int world, int rank, 
     CHECK_H(h);
     if (h->host_only) return fail(TGNH_ERR_STATE, "host-only handle");
     if (world < 1 || world > XCHG_MAX_WORLD || rank < 0 || rank >= world) return fail(TGNH_ERR_ARG, "bad world / rank");
-    if (h->L.NT > XCHG_NT_PAD || h->gather_chain) return fail(TGNH_ERR_UNSUPPORTED, "too many thermostats for a mailbox (more than 32 temperature groups: use an all-reduce hook or RCCL)");
+    if (h->L.NT > MAX_GROUPS + 2) return fail(TGNH_ERR_UNSUPPORTED, "too many thermostats for a mailbox (more than 32 temperature groups: use an all-reduce hook or RCCL)");
+    if (h->gather_chain) return fail(TGNH_ERR_UNSUPPORTED, "no mailbox for a chain too long for the LDS-resident form (it runs in gather_chain_kernel: use an all-reduce hook or RCCL)");
     if (h->x_mailbox) return fail(TGNH_ERR_STATE, "exchange already created");
     HIP_OK(hipSetDevice(h->device));
     const size_t bytes = XCHG_MAILBOX_BYTES(world);

@@ -362,6 +362,11 @@ static void com_and_norm(const tgo_state* s, const double* vel, double* comv, do
             double comMass = 0.0;
             for (int j = 0; j < s->res_count[r]; j++) {
                 int index = s->res_first[r] + j;
+                /* A residue in several runs: res_first is its LAST run's start, and K :90-91 walks `count` particles from
+                   there -- past the end of the arrays for a residue whose last run lies near it: the reference reads out of
+                   bounds.  The walk stops at the end here, as gather_com_kernel's does, so oracle and library fix the same
+                   choice (the only departure from a statement-for-statement restatement of K). */
+                if (index >= s->n) break;
                 double w = s->inv_mass[index];
                 if (w != 0) {
                     double m = 1.0 / w;

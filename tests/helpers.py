@@ -191,6 +191,44 @@ def far_pairs(seed=7):
     return out
 
 
+def scattered_residues(seed=11):
+    """The mixed box with its residue array in random order: every residue comes in many runs, and the reference's walk of `count`
+    particles from a residue's last run (K :90-91) leaves the array for the residues whose last run lies near its end.  One
+    temperature group (a Drude particle and its parent must share theirs, Ref :128-131, and the shuffle parts them from any other)."""
+    s, g, _ = synth.mixed(120, 10)
+    resid = s.resid.copy()
+    np.random.default_rng(seed).shuffle(resid)
+    out = synth.DrudeSystem(mass=s.mass, pair_drude=s.pair_drude, pair_parent=s.pair_parent, resid=resid, positions=s.positions,
+                            velocities=s.velocities, name="scattered-residues")
+    return out, np.zeros_like(g), 1
+
+
+def far_pairs_at_size(n_water=400_000, long=((10_000, 1_000), (40_000, 10_000), (100_000, 50_000)), seed=9):
+    """far_pairs at size: `n_water` water-like molecules and ions (the mixed box, four groups), then long contiguous molecules of
+    (slots, distance): in every block of 2 x distance slots, the Drude particles of the block's first half sit `distance` slots
+    behind their parents in its second half (every other slot of it).  The COM is a molecule's own here (every residue one run),
+    and the longest residue is walked by one team of gather_com_kernel."""
+    rng = np.random.default_rng(seed)
+    s, g, ng = synth.mixed(n_water, 1000)
+    mass, resid, group, pos = [s.mass], [s.resid], [g], [s.positions]
+    pd, pp = [s.pair_drude], [s.pair_parent]
+    start, r = s.num_particles, int(s.resid.max()) + 1
+    for size, dist in long:
+        assert size % (2 * dist) == 0
+        m = rng.uniform(6.0, 30.0, size)
+        blocks = start + np.arange(0, size, 2 * dist)[:, None]
+        par = (blocks + np.arange(0, dist, 2)[None, :]).ravel()
+        m[par + dist - start] = 0.4
+        pp.append(par); pd.append(par + dist)
+        mass.append(m); resid.append(np.full(size, r)); group.append(np.full(size, 1))
+        pos.append(rng.uniform(0.0, 20.0, (size, 3)))
+        start += size
+        r += 1
+    return synth._finish(np.concatenate(mass), np.concatenate(pd).astype(np.int32), np.concatenate(pp).astype(np.int32),
+                         np.concatenate(resid).astype(np.int32), np.concatenate(pos), np.concatenate(group).astype(np.int32), ng, rng,
+                         300.0, 1.0, "far-pairs-at-size")
+
+
 def interleaved(n_mol=60):
     """Two particles of neighbouring molecules swapped: residues 0 and 1 each come in several runs.  The reference's table says
     (count, start of the LAST run) for them (Cu :121-124) and its COM kernel walks `count` particles from there (K :90-91),

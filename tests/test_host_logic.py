@@ -396,6 +396,38 @@ def test_up_to_32_temperature_groups():
     assert t.num_thermostats() == 302 and np.allclose(t.dof()[0], o.dof()[0], rtol=1e-14)
 
 
+LONG_CHAIN = "a chain too long for the LDS-resident form"
+# (G, C) at the edge of the LDS-resident chain: (G + 2)(4 C + 1) doubles of 2048, chains of more than 16 links (tgnh_create)
+CHAIN_EDGE = [(4, 85, 2046), (12, 36, 2030), (32, 16, 2210)]
+
+
+def _groups_system(G):
+    return synth.mixed(60, 6) if G == 4 else synth.many_groups(60, 6, G)
+
+
+@pytest.mark.parametrize("G,C,need", CHAIN_EDGE)
+@pytest.mark.parametrize("longer", [False, True])
+def test_chain_length_at_the_lds_threshold(G, C, need, longer):
+    """The longest chains the LDS-resident form holds stay tiled; one link more takes the gather path with its own chain
+    (gather_chain_kernel, links in a global scratch row): tgnh_get_step_path's raw value 2, which step_path() folds into "gather".
+    (G = 32, C = 16: 2210 doubles, but 16 links are chain_long_kernel's own limit -- the threshold asks for both.)"""
+    import ctypes as C_
+    C = C + longer
+    assert (G + 2) * (4 * (C - longer) + 1) == need
+    s, g, ng = _groups_system(G)
+    assert ng == G
+    t = HostTopology(s, integ(chains=C, group=g, ngroups=ng), mode="TGNH", precision="mixed")
+    raw, why = C_.c_int(-1), C_.c_char_p()
+    assert t.lib.tgnh_get_step_path(t.h, C_.byref(raw), C_.byref(why)) == 0
+    if longer:
+        assert t.step_path() == ("gather", LONG_CHAIN) and raw.value == 2 and why.value.decode() == LONG_CHAIN
+    else:
+        assert t.step_path() == ("tiled", "") and raw.value == 0
+    o = make_oracle(s, g, ng, "TGNH", integ(chains=C, group=g, ngroups=ng))
+    assert np.allclose(t.dof()[0], o.dof()[0], rtol=1e-14)
+    t.close()
+
+
 @pytest.mark.parametrize("seed", range(12))
 def test_random_topologies_tile_and_count_like_the_oracle(seed):
     """Ragged inputs: molecules of 1-40 slots in random order of size (a few longer than a tile), Drude pairs anywhere

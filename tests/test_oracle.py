@@ -120,6 +120,52 @@ def test_rescale_scales_ke_by_square():
         assert np.allclose(ke1, ke0 * sc ** 2, rtol=1e-12, atol=0)
 
 
+def _truncated_walk_bins(s, g, ng, vel):
+    """K :82-113 / :152-186 restated in numpy fp64: the residue table says (count, start of the residue's LAST run) (Cu :114-125), the
+    COM walks `count` particles from there -- cut at the end of the array, where the reference reads past it."""
+    n, R = s.num_particles, s.num_residues
+    count = np.bincount(s.resid, minlength=R)
+    first = np.full(R, -1)
+    prev = -1
+    for i, r in enumerate(s.resid):
+        if r != prev:
+            first[r], prev = i, r
+    w = np.where(s.mass > 0, 1.0 / np.where(s.mass > 0, s.mass, 1.0), 0.0)
+    com = np.zeros((R, 3))
+    inv_m = np.zeros(R)
+    for r in range(R):
+        idx = np.arange(first[r], min(first[r] + count[r], n))
+        idx = idx[w[idx] != 0]
+        m = 1.0 / w[idx]
+        inv_m[r] = 1.0 / m.sum()
+        com[r] = (vel[idx] * m[:, None]).sum(0) * inv_m[r]
+    norm = vel - com[s.resid]
+    ke = np.zeros(ng + 2)
+    ke[ng] = ((com ** 2).sum(1) / inv_m).sum()
+    normal = np.setdiff1d(np.arange(n), np.r_[s.pair_drude, s.pair_parent])
+    normal = normal[w[normal] != 0]
+    np.add.at(ke, g[normal], (norm[normal] ** 2).sum(1) / w[normal])
+    m1, m2 = s.mass[s.pair_drude], s.mass[s.pair_parent]
+    cm = (norm[s.pair_drude] * m1[:, None] + norm[s.pair_parent] * m2[:, None]) / (m1 + m2)[:, None]
+    np.add.at(ke, g[s.pair_drude], (cm ** 2).sum(1) * (m1 + m2))
+    ke[ng + 1] = (((norm[s.pair_parent] - norm[s.pair_drude]) ** 2).sum(1) * m1 * m2 / (m1 + m2)).sum()
+    return ke, first + count > n
+
+
+@pytest.mark.parametrize("name", ["scattered", "drudes-at-the-end"])
+def test_residue_walk_past_the_array_stops_at_its_end(name):
+    """A residue in several runs: the reference's COM walk of `count` particles from the last run's start leaves the arrays for
+    the residues whose last run lies near their end (K :90-91 reads out of bounds there).  The oracle stops at the end, as the
+    library's gather_com_kernel does, so both fix the same choice: its kinetic-energy bins against a numpy restatement of the
+    truncated walk."""
+    from helpers import scattered_residues, drudes_at_the_end
+    s, g, ng = scattered_residues() if name == "scattered" else drudes_at_the_end(40)
+    expect, cut = _truncated_walk_bins(s, g, ng, s.velocities)
+    assert cut.any()                                               # the walk really leaves the array for some residue
+    o = _oracle(s, g, ng, MODE_TGNH, _integ())
+    assert np.allclose(o.kinetic_energies(s.velocities), expect, rtol=1e-13, atol=0)
+
+
 @pytest.mark.parametrize("chains", [1, 3])
 @pytest.mark.parametrize("hardwall", [0.0, 0.02])
 def test_bridge_identity_tgnh_equals_dualnh(chains, hardwall):

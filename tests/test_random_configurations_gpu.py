@@ -11,30 +11,45 @@ import oracle_soak
 pytestmark = pytest.mark.gpu
 
 
+STRUCTURAL = ("(an empty shard)", "(mailbox: <= 34 thermostats)")      # sharded_case's named skips: nothing to shard, or no mailbox for it
+
+
 def _run(case, seeds, nsteps):
-    verdicts = {"ok": 0, "skip": 0}
+    """-> counts of four outcomes: ok; refused at create (TGNH_ERR_UNSUPPORTED: oracle_soak.REFUSED grows); no verdict from the
+    oracle (OracleError: random constraint clusters its own SHAKE gives up on); a structural skip of the sharded case.  Any other
+    skip is a failure."""
+    verdicts = {"ok": 0, "refused": 0, "no_verdict": 0, "structural": 0}
     for seed in seeds:
         info = {"what": ""}
+        refused = sum(oracle_soak.REFUSED.values())
         try:
-            kind = case(np.random.default_rng(seed), nsteps, info)[0]
+            kind, what = case(np.random.default_rng(seed), nsteps, info)[:2]
         except oracle_soak.OracleError:
-            kind = "skip"                                    # random constraint clusters the oracle's own SHAKE gives up on
+            kind, what = "no_verdict", ""
         except Exception as e:
             raise AssertionError(f"seed {seed}: {info['what']}") from e
+        if kind == "skip":
+            if sum(oracle_soak.REFUSED.values()) > refused:
+                kind = "refused"
+            elif what.endswith(STRUCTURAL):
+                kind = "structural"
+            else:
+                raise AssertionError(f"seed {seed}: skipped for no named reason: {what}")
         verdicts[kind] += 1
+    print(case.__name__, verdicts, dict(oracle_soak.REFUSED))
     return verdicts
 
 
 def test_random_configurations_against_the_oracle():
     v = _run(oracle_soak.one_case, range(400), 30)
-    assert v["ok"] >= 350, v                                 # (the rest: refused as unsupported at create, or no verdict from the oracle)
+    assert v["refused"] == 0 and v["ok"] >= 388, v          # MI355X: 389 ok, 11 without a verdict from the oracle
 
 
 def test_random_sharded_configurations_against_the_oracle():
     v = _run(oracle_soak.sharded_case, range(500000, 500150), 20)
-    assert v["ok"] >= 130, v
+    assert v["refused"] == 0 and v["ok"] >= 138, v          # MI355X: 139 ok, 11 structural skips
 
 
 def test_random_checkpoints_restore_bit_for_bit():
     v = _run(oracle_soak.checkpoint_case, range(4000000, 4000150), 15)
-    assert v["ok"] >= 130, v
+    assert v["refused"] == 0 and v["ok"] >= 149, v          # MI355X: 150 of 150
