@@ -12,8 +12,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdrudetgnh_hip.so")
-SOURCES = ["tgnh_host.cpp", "tgnh_kernels.hip", "tgnh_gather.hip", "tgnh_harness.hip"]
-HEADERS = ["tgnh_internal.h", "tgnh_chain_device.h", "tgnh_tile_device.h", os.path.join("..", "..", "include", "drude_tgnh.h")]
+SOURCES = ["tgnh_topology.cpp", "tgnh_lifecycle.cpp", "tgnh_exchange.cpp", "tgnh_step.cpp", "tgnh_queries.cpp", "tgnh_harness_host.cpp",
+           "tgnh_kernels.hip", "tgnh_gather.hip", "tgnh_harness.hip"]
+# every header of csrc/ (read off the directory, as source_sha does: a new header cannot leave a stale object behind) and the ABI header
+HEADERS = sorted(n for n in os.listdir(CSRC) if n.endswith(".h")) + [os.path.join("..", "..", "include", "drude_tgnh.h")]
 ARCH = "gfx950"
 
 
@@ -74,7 +76,7 @@ def build(force=False, verbose=False):
     for name in os.listdir(objdir):                      # objects of earlier source states
         if name.endswith(".o") and os.path.join(objdir, name) not in objs:
             os.remove(os.path.join(objdir, name))
-    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + objs + ["-ldl", "-o", LIB]   # (RCCL is bound with dlopen at the first tgnh_rccl_* call: tgnh_host.cpp)
+    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC"] + objs + ["-ldl", "-o", LIB]   # (RCCL is bound with dlopen at the first tgnh_rccl_* call: tgnh_exchange.cpp)
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)

@@ -1,0 +1,205 @@
+// tgnh_context.h -- the handle behind the C ABI: its state by concern, and the owner of its device memory.  Host side only
+// (tgnh_*.cpp and the host half of tgnh_harness.hip); the kernels see tgnh_internal.h's launch arguments and nothing of this.
+#ifndef TGNH_CONTEXT_H_
+#define TGNH_CONTEXT_H_
+
+#include <map>
+#include <string>
+#include <vector>
+
+#include "tgnh_internal.h"
+
+void tgnh_set_error(const std::string& msg);   // sets what tgnh_last_error() returns (tgnh_lifecycle.cpp)
+
+namespace tgnh {
+// Device (or pinned host) memory with one owner: freed when the owner goes, or when it is allocated anew.  Reads as the
+// pointer it holds.  The handle's device must be current when a buffer is released (tgnh_destroy sees to it).
+template <typename T> class DeviceBuf {
+    T* p_ = nullptr;
+    bool pinned_ = false;
+public:
+    DeviceBuf() = default;
+    DeviceBuf(DeviceBuf&& o) noexcept : p_(o.p_), pinned_(o.pinned_) { o.p_ = nullptr; }      // (move-only: no copies, no assignment)
+    ~DeviceBuf() { reset(); }
+    void reset() { if (p_) (void)(pinned_ ? hipHostFree(p_) : hipFree(p_)); p_ = nullptr; }
+    // n elements; ext_flags != 0: hipExtMallocWithFlags (TGNH_MEETING_MEM, hipDeviceMallocUncached)
+    hipError_t alloc(size_t n, bool zero = false, unsigned ext_flags = 0) {
+        reset(); pinned_ = false;
+        void* p = nullptr;
+        hipError_t e = ext_flags ? hipExtMallocWithFlags(&p, sizeof(T) * n, ext_flags) : hipMalloc(&p, sizeof(T) * n);
+        if (e != hipSuccess) return e;
+        p_ = static_cast<T*>(p);
+        return zero ? hipMemset(p_, 0, sizeof(T) * n) : hipSuccess;
+    }
+    hipError_t alloc_pinned(size_t n) { reset(); pinned_ = true; return hipHostMalloc(reinterpret_cast<void**>(&p_), sizeof(T) * n, hipHostMallocDefault); }
+    hipError_t upload(const T* src, size_t n) {              // a table from the host (an empty one still gets an address)
+        hipError_t e = alloc(n ? n : 1);
+        return e != hipSuccess || !n ? e : hipMemcpy(p_, src, sizeof(T) * n, hipMemcpyHostToDevice);
+    }
+    hipError_t upload(const std::vector<T>& v) { return upload(v.data(), v.size()); }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+};
+typedef DeviceBuf<unsigned char> DeviceBytes;   // what the kernels read as real4 / mixed4 of the handle's precision
+}  // namespace tgnh
+
+// Every DeviceBuf below is the handle's own.  Raw pointers are somebody else's memory: the caller's bound arrays (Bound), the
+// peers' mailboxes opened over IPC (Exchange::opened, closed -- not freed -- here), a caller's ncclComm_t, and the pointers
+// inside an XchgArgs, which point into buffers owned here.
+struct tgnh_context {
+    tgnh_desc d;                      // scalars only; pointers are nulled after create
+    int device = 0;
+    bool host_only = false;           // device == -1: topology / dof only, no launches
+    struct Topology {                 // host topology (A1), kept for parity queries, and its device tables
+        std::vector<double> mass;
+        std::vector<int> pair_drude, pair_parent, group, resid, normal;
+        std::vector<int> res_count, res_first;
+        std::vector<int> tile_start, tile_res;
+        std::vector<int2> res_entries;    // per-tile molecule entries
+        std::vector<int> big_first, big_count;   // molecules longer than a tile (COM from big_com_kernel)
+        int num_big = 0, num_tiles = 0;
+        std::vector<uint32_t> meta;
+        std::vector<int2> wave_tile;      // wave tiles (empty: some molecule or pair does not fit a wavefront)
+        std::vector<uint32_t> wmeta;
+        std::vector<uint32_t> tile_pat, wtile_pat;    // per 512-slot tile: period | molecules << 8 | pattern << 16; per wave tile: period | pattern << 8; 0 = none
+        std::vector<uint32_t> pattern, wpattern;      // 64 words per pattern
+        int num_wtiles = 0;
+        tgnh::DeviceBuf<uint32_t> d_meta, d_wmeta, d_tile_pat, d_pattern, d_wpattern;
+        tgnh::DeviceBuf<int> d_tile_start, d_tile_res;
+        tgnh::DeviceBuf<int2> d_res_table, d_wave_tile, d_big_table;
+        tgnh::DeviceBytes d_big_com;
+    } topo;
+    // the gather path: taken when the tiles cannot hold the topology (reason says why); the reference's index lists, per particle
+    struct Gather {
+        bool generic = false;
+        bool chain = false;               // ... and its chain too: more than 34 thermostats, or links that do not fit the LDS (gather_chain_kernel)
+        std::string reason;
+        std::vector<int2> res_table;
+        std::vector<int> resid, partner;
+        int com_lanes = 64;
+        tgnh::DeviceBuf<int> d_group, d_resid, d_partner;
+        tgnh::DeviceBuf<int2> d_res_table;
+        tgnh::DeviceBytes d_com;
+        tgnh::DeviceBuf<double> d_scratch;    // chains longer than 4 links of more than 34 thermostats: a row of 4 C + 1 doubles each
+    } gather;
+    struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
+        std::vector<double> h_state;      // host copy of the initial thermostat block
+        std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction
+        std::vector<double> dof, nkbt;
+        double realkbT = 0, drudekbT = 0;
+        tgnh::ChainLayout L{};
+        tgnh::DeviceBuf<double> d_partials;
+        tgnh::DeviceBuf<double> d_state;      // thermostat block
+        tgnh::DeviceBuf<double> d_stage;      // same layout: where an in-kernel chain leaves the advanced block
+        tgnh::DeviceBuf<double> d_scalar;     // plain KE: [0] the result, [1 ..] work-group partials
+    } thermo;
+    struct LaunchConfig {             // fixed at create (the grids: filled in at the first launch of their kind)
+        int grid = 0, gb = 1;
+        int num_cus = 256, grid_override = 0;
+        std::map<int, int> grid_cache;    // ops (+hard-wall bit) -> persistent grid size
+        bool alternate_sweeps = true;
+        int inline_sum_rows = tgnh::CHAIN_INLINE_SUM_ROWS;
+        bool inline_sum_all = false;      // more rows than that (and < 2 M slots): all four wavefronts of the rescale launch sum them (sum_rows = 2)
+        bool carry_ok = false;            // TGNH_FLAG_TRUST_STATE_CHANGED is in effect for this handle (set, unsharded, no molecule spans two groups)
+        bool inline_chain = false;        // numNHChains == 1: the chain runs inside the rescale launch
+        bool wave_ke = false;             // the KE passes run over the wave tiles (wke_kernel)
+        int resident_grid[5][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};   // step_kernel's grid by kind and hard wall
+        int resident_share = 1;
+        int wresident_per_cu = 0, wresident_grid = 0;   // the same for wstep_kernel (0: none, or no wave tiles)
+        int resident_per_cu = 0;          // work-groups of step_kernel per compute unit that the census at create found resident together (0: none -- the handle steps the DEFER_SCALE way)
+    } cfg;
+    // What a step still owes: work an entry point has left to a later launch, and what the last launches left behind.
+    struct Owed {
+        // the first eight are bits 0..7 of tgnh_get_pending_state, in this order; the last five are not reported
+        bool end_pending = false;         // RESIDENT_STEP: the whole end half of the last step waits for the next step_begin's launch
+        bool scale_pending = false;       // DEFER_SCALE: velm lags by scale[]
+        bool kick_pending = false;        // DEFER_SCALE: velm also lags by the second half kick (force buffer unchanged since)
+        bool first_half_done = false;     // DEFER_SCALE: chain for the coming step's first half already run
+        bool chain_pending = false;       // summed KE waits for the next rescale launch to run the chain
+        bool sum_pending = false;         // with chain_pending: the partial rows are not summed yet either (the rescale launch does both)
+        bool xwait_pending = false;       // with chain_pending: the sums were sent over the mailboxes, nobody has waited for the peers' yet
+        bool stage_pending = false;       // d_stage is newer than d_state; the next chain_kernel launch commits it
+        bool ke_carry = false;            // (bit 9) TRUST_STATE_CHANGED: ke_post of the last end half IS the kinetic energy of the stored velocities
+        bool chain_pending_twice = false; // with chain_pending: both chain halves (DEFER_SCALE)
+        bool carry_pending = false;       // ... and that KE is the last chain's ke_post (ChainArgs::ke_carry), not ke_red
+        bool tail_summed = false;         // the last KE launch summed its rows itself (wke_kernel's tail sum): no row-sum launch
+        bool end_folded = false;          // the last fused end half left the kick to its rescale launch (OP_PREKICK: algorithmic bytes of KID_SCALE)
+        bool g_com_fresh = false;         // gather path: the COM table is of the velocities as they are (set by a KE pass; cleared by the next launch that writes velocities and on entry to every entry point)
+        enum : uint32_t { BIT_SWEEP_REVERSE = 1u << 8 };      // (Run::sweep_reverse, reported beside these)
+        uint32_t bits() const {           // the layout include/drude_tgnh.h documents, written down here and nowhere else
+            return end_pending | scale_pending << 1 | kick_pending << 2 | first_half_done << 3 | chain_pending << 4 | sum_pending << 5 |
+                   xwait_pending << 6 | stage_pending << 7 | ke_carry << 9;
+        }
+        void chain_ran() { chain_pending = sum_pending = xwait_pending = carry_pending = false; }     // (whoever ran it says where the block now lies: stage_pending)
+        void velocities_current() { scale_pending = kick_pending = false; }
+        void end_half_deferred(bool kick) { scale_pending = first_half_done = true; kick_pending = kick; }   // DEFER_SCALE: both chain halves are in scale[], velm lags
+        void resident_settled() { end_pending = first_half_done = false; velocities_current(); chain_pending = sum_pending = xwait_pending = false; }
+        void thermostat_reset() { end_pending = first_half_done = false; velocities_current(); chain_pending = stage_pending = carry_pending = ke_carry = false; }
+    } owed;
+    struct Run {
+        double time = 0;
+        int64_t step_count = 0;
+        int sweep_reverse = 0;            // direction of the next streaming launch (alternates)
+        int ke_parts = 0;                 // rows of partial sums the last KE launch wrote
+    } run;
+    struct Bound {                    // the caller's arrays (tgnh_bind_buffers)
+        void *posq = nullptr, *posq_corr = nullptr, *velm = nullptr, *pos_delta = nullptr;
+        const void* force = nullptr;
+    } bound;
+    struct Status {
+        tgnh::DeviceBuf<uint32_t> d_word;
+        tgnh::DeviceBuf<uint32_t> h_seen;    // pinned: where read-backs of the status word land (periodic, and at every query)
+        int failed_code = 0;                 // sticky: a failure the device reported (note_status); every later entry returns it
+        std::string failed;
+    } status;
+    struct Meeting {                  // where the work-groups of one launch meet (step_kernel, wstep_kernel, wke_kernel's tail sum)
+        tgnh::DeviceBuf<unsigned int> d_sync;           // launch number
+        tgnh::DeviceBuf<unsigned long long> d_rows;     // ... and the tagged rows (uncached)
+        tgnh::DeviceBuf<unsigned long long> self_box;      // RESIDENT_STEP without a sharded exchange: a private one-rank mailbox
+        tgnh::DeviceBuf<unsigned long long> d_self_misc;   // ... its counter, latch and peer table
+        tgnh::XchgArgs self_x{};
+    } meet;
+    struct Exchange {                 // the kinetic-energy sums across ranks: a hook, RCCL, or the mailboxes (which replace the hook when attached)
+        tgnh_allreduce_fn allreduce = nullptr;
+        void* allreduce_user = nullptr;
+        void* rccl_comm = nullptr;        // ncclComm_t: the library enqueues ncclAllReduce itself (tgnh_rccl_init / tgnh_set_rccl_comm)
+        bool rccl_owned = false;
+        tgnh::XchgArgs args{};
+        bool on = false;
+        int world = 0, rank = 0;
+        tgnh::DeviceBuf<unsigned long long> mailbox;     // mine (uncached device memory)
+        tgnh::DeviceBuf<unsigned long long*> d_peers;    // device table of every rank's mailbox
+        std::vector<void*> opened;                       // peers' mailboxes opened by IPC (to close)
+        tgnh::DeviceBuf<unsigned long long> d_seq;
+        tgnh::DeviceBuf<unsigned int> d_dead;
+        tgnh::DeviceBuf<unsigned long long> d_stat;      // mailbox wait statistics (XchgArgs::stat)
+        void close_peers() { for (void* p : opened) (void)hipIpcCloseMemHandle(p); opened.clear(); }
+        ~Exchange() { close_peers(); }
+    } xchg;
+    struct Harness {                  // the test harness's call-outs (tgnh_harness.hip, tgnh_harness_host.cpp)
+        tgnh::DeviceBuf<int4> d_cl_atoms, d_vs_atoms;
+        tgnh::DeviceBuf<double> d_cl_dist, d_vs_w;
+        int num_clusters = 0, num_sites = 0;
+        tgnh::DeviceBuf<uint8_t> d_sflag;         // packed tether sites (ForceArgs::sflag / sbase / sites), tgnh_harness_pack_sites
+        tgnh::DeviceBuf<uint32_t> d_sbase;
+        tgnh::DeviceBytes d_sites;
+        int lat_k = 0, lat_side = 0, lat_mol0 = 0;              // ... or lattice sites: the hint (lat_k = 0: none), and whether pack_sites found it to hold
+        double lat_spacing = 0;
+        std::vector<double> lat_geom;
+        bool lat_on = false;
+        tgnh::DeviceBuf<unsigned char> d_lat_tab;
+        tgnh::DeviceBytes d_g_x0;         // gather path: the tether sites as tgnh_harness_pack_sites was handed them
+    } harness;
+    struct Timing {
+        bool on = false;
+        int only = -1;                    // >= 0: only this kernel id is timed
+        struct Ev { hipEvent_t a, b; int kid; };
+        std::vector<Ev> ev_pool;
+        size_t ev_used = 0;
+        double t_total[tgnh::KID_COUNT] = {0};
+        int64_t t_count[tgnh::KID_COUNT] = {0};
+        ~Timing() { for (auto& e : ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); } }
+    } timing;
+};
+
+#endif

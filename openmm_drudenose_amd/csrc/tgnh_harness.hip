@@ -8,7 +8,7 @@
 // Constraint cluster: up to 4 atoms and the 6 possible distances among them in the fixed order
 // (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); distance 0 = no constraint.  One lane per cluster, SHAKE sweeps in that
 // order until every |d^2 - r^2| <= 2 tol d^2 -- everything in registers, static indices.
-#include "tgnh_internal.h"
+#include "tgnh_context.h"
 
 namespace tgnh {
 
@@ -301,7 +301,7 @@ using namespace tgnh;
 static tgnh_status harness_ready(tgnh_handle h) {
     if (!h) H_FAIL(TGNH_ERR_ARG, "null handle");
     if (h->host_only) H_FAIL(TGNH_ERR_STATE, "host-only handle (device -1): no GPU work can be launched on it");
-    if (!h->velm) H_FAIL(TGNH_ERR_STATE, "tgnh_bind_buffers has not been called");
+    if (!h->bound.velm) H_FAIL(TGNH_ERR_STATE, "tgnh_bind_buffers has not been called");
     return TGNH_OK;
 }
 
@@ -312,29 +312,26 @@ extern "C" tgnh_status tgnh_harness_set_clusters(tgnh_handle h, int n, const int
     for (long long i = 0; i < 4LL * n; i++)
         if (atoms[i] < -1 || atoms[i] >= h->d.num_particles) H_FAIL(TGNH_ERR_ARG, "cluster atom index out of range");
     H_HIP(hipSetDevice(h->device));
-    if (h->d_cl_atoms) { (void)hipFree(h->d_cl_atoms); h->d_cl_atoms = nullptr; }
-    if (h->d_cl_dist) { (void)hipFree(h->d_cl_dist); h->d_cl_dist = nullptr; }
-    h->num_clusters = n;
+    h->harness.d_cl_atoms.reset(); h->harness.d_cl_dist.reset();
+    h->harness.num_clusters = n;
     if (n == 0) return TGNH_OK;
-    H_HIP(hipMalloc(&h->d_cl_atoms, sizeof(int4) * n));
-    H_HIP(hipMemcpy(h->d_cl_atoms, atoms, sizeof(int4) * n, hipMemcpyHostToDevice));
-    H_HIP(hipMalloc(&h->d_cl_dist, sizeof(double) * 6 * n));
-    H_HIP(hipMemcpy(h->d_cl_dist, dist, sizeof(double) * 6 * n, hipMemcpyHostToDevice));
+    H_HIP(h->harness.d_cl_atoms.upload(reinterpret_cast<const int4*>(atoms), n));
+    H_HIP(h->harness.d_cl_dist.upload(dist, 6 * (size_t)n));
     return TGNH_OK;
 }
 
 static ClusterArgs cluster_args(tgnh_handle h, double tol) {
     ClusterArgs a{};
-    a.atoms = h->d_cl_atoms; a.dist = h->d_cl_dist; a.n = h->num_clusters;
-    a.posq = h->posq; a.posq_corr = h->posq_corr; a.velm = h->velm; a.pos_delta = h->pos_delta;
-    a.tol = tol; a.status = h->d_status;
+    a.atoms = h->harness.d_cl_atoms; a.dist = h->harness.d_cl_dist; a.n = h->harness.num_clusters;
+    a.posq = h->bound.posq; a.posq_corr = h->bound.posq_corr; a.velm = h->bound.velm; a.pos_delta = h->bound.pos_delta;
+    a.tol = tol; a.status = h->status.d_word;
     return a;
 }
 
 extern "C" tgnh_status tgnh_harness_shake_positions(tgnh_handle h, double tol, void* stream) {
     tgnh_status rc = harness_ready(h); if (rc) return rc;
-    if (!h->pos_delta) H_FAIL(TGNH_ERR_STATE, "posDelta buffer not bound");
-    if (h->num_clusters == 0) return TGNH_OK;
+    if (!h->bound.pos_delta) H_FAIL(TGNH_ERR_STATE, "posDelta buffer not bound");
+    if (h->harness.num_clusters == 0) return TGNH_OK;
     H_HIP(hipSetDevice(h->device));
     H_HIP(launch_shake<false>(h->d.precision, cluster_args(h, tol), (hipStream_t)stream));
     return TGNH_OK;
@@ -342,8 +339,8 @@ extern "C" tgnh_status tgnh_harness_shake_positions(tgnh_handle h, double tol, v
 
 extern "C" tgnh_status tgnh_harness_shake_velocities(tgnh_handle h, double tol, void* stream) {
     tgnh_status rc = harness_ready(h); if (rc) return rc;
-    h->ke_carry = false;                 // velocities are about to change behind the integrator (TRUST_STATE_CHANGED: recompute)
-    if (h->num_clusters == 0) return TGNH_OK;
+    h->owed.ke_carry = false;                 // velocities are about to change behind the integrator (TRUST_STATE_CHANGED: recompute)
+    if (h->harness.num_clusters == 0) return TGNH_OK;
     H_HIP(hipSetDevice(h->device));
     H_HIP(launch_shake<true>(h->d.precision, cluster_args(h, tol), (hipStream_t)stream));
     return TGNH_OK;
@@ -356,23 +353,20 @@ extern "C" tgnh_status tgnh_harness_set_virtual_sites(tgnh_handle h, int n, cons
     for (long long i = 0; i < 4LL * n; i++)
         if (atoms[i] < 0 || atoms[i] >= h->d.num_particles) H_FAIL(TGNH_ERR_ARG, "virtual-site atom index out of range");
     H_HIP(hipSetDevice(h->device));
-    if (h->d_vs_atoms) { (void)hipFree(h->d_vs_atoms); h->d_vs_atoms = nullptr; }
-    if (h->d_vs_w) { (void)hipFree(h->d_vs_w); h->d_vs_w = nullptr; }
-    h->num_sites = n;
+    h->harness.d_vs_atoms.reset(); h->harness.d_vs_w.reset();
+    h->harness.num_sites = n;
     if (n == 0) return TGNH_OK;
-    H_HIP(hipMalloc(&h->d_vs_atoms, sizeof(int4) * n));
-    H_HIP(hipMemcpy(h->d_vs_atoms, atoms, sizeof(int4) * n, hipMemcpyHostToDevice));
-    H_HIP(hipMalloc(&h->d_vs_w, sizeof(double) * 3 * n));
-    H_HIP(hipMemcpy(h->d_vs_w, weights, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+    H_HIP(h->harness.d_vs_atoms.upload(reinterpret_cast<const int4*>(atoms), n));
+    H_HIP(h->harness.d_vs_w.upload(weights, 3 * (size_t)n));
     return TGNH_OK;
 }
 
 extern "C" tgnh_status tgnh_harness_virtual_sites(tgnh_handle h, void* stream) {
     tgnh_status rc = harness_ready(h); if (rc) return rc;
-    if (h->num_sites == 0) return TGNH_OK;
+    if (h->harness.num_sites == 0) return TGNH_OK;
     H_HIP(hipSetDevice(h->device));
     SiteArgs a{};
-    a.atoms = h->d_vs_atoms; a.w = h->d_vs_w; a.n = h->num_sites; a.posq = h->posq; a.posq_corr = h->posq_corr;
+    a.atoms = h->harness.d_vs_atoms; a.w = h->harness.d_vs_w; a.n = h->harness.num_sites; a.posq = h->bound.posq; a.posq_corr = h->bound.posq_corr;
     H_HIP(launch_sites(h->d.precision, a, (hipStream_t)stream));
     return TGNH_OK;
 }
@@ -386,7 +380,7 @@ extern "C" tgnh_status tgnh_run_harness_constrained(tgnh_handle h, const void* x
         rc = tgnh_harness_shake_positions(h, tol, stream); if (rc) return rc;            // Cu :363 call-out
         rc = tgnh_step_begin_move(h, stream); if (rc) return rc;                         // Cu :366-376
         rc = tgnh_harness_virtual_sites(h, stream); if (rc) return rc;                   // Cu :377 call-out
-        rc = tgnh_harness_force(h, x0, k_drude, k_tether, const_cast<void*>(h->force), stream); if (rc) return rc;   // Cu :380 call-out
+        rc = tgnh_harness_force(h, x0, k_drude, k_tether, const_cast<void*>(h->bound.force), stream); if (rc) return rc;   // Cu :380 call-out
         rc = tgnh_step_end_kick(h, stream); if (rc) return rc;                           // Cu :384-388
         if (h->d.mode == TGNH_MODE_TGNH) {                                               // Cu :391 call-out (the Reference platform has none)
             rc = tgnh_harness_shake_velocities(h, tol, stream); if (rc) return rc;
@@ -405,7 +399,7 @@ extern "C" tgnh_status tgnh_harness_water_force(tgnh_handle h, double box, doubl
     if (h->d.num_particles % 5) H_FAIL(TGNH_ERR_ARG, "the testWater force field needs O, D, H1, H2, M per molecule");
     H_HIP(hipSetDevice(h->device));
     WaterArgs a{};
-    a.posq = h->posq; a.posq_corr = h->posq_corr; a.force = reinterpret_cast<long long*>(force_out);
+    a.posq = h->bound.posq; a.posq_corr = h->bound.posq_corr; a.force = reinterpret_cast<long long*>(force_out);
     a.n_mol = h->d.num_particles / 5; a.padded = h->d.padded_num_particles; a.box = box; a.cutoff = cutoff;
     hipStream_t s = (hipStream_t)stream;
     switch (h->d.precision) {
@@ -419,13 +413,13 @@ extern "C" tgnh_status tgnh_harness_water_force(tgnh_handle h, double box, doubl
 
 extern "C" tgnh_status tgnh_harness_remove_cm_motion(tgnh_handle h, void* stream) {
     tgnh_status rc = harness_ready(h); if (rc) return rc;
-    h->ke_carry = false;                 // (OpenMM's CMMotionRemover does not tell the integrator: the glue does not set TRUST_STATE_CHANGED beside one)
+    h->owed.ke_carry = false;                 // (OpenMM's CMMotionRemover does not tell the integrator: the glue does not set TRUST_STATE_CHANGED beside one)
     H_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     switch (h->d.precision) {
-        case TGNH_PREC_SINGLE: TGNH_LAUNCH((cmm_kernel<TGNH_PREC_SINGLE>), dim3(1), dim3(BLOCK), 0, s, h->velm, h->d.num_particles); break;
-        case TGNH_PREC_MIXED: TGNH_LAUNCH((cmm_kernel<TGNH_PREC_MIXED>), dim3(1), dim3(BLOCK), 0, s, h->velm, h->d.num_particles); break;
-        default: TGNH_LAUNCH((cmm_kernel<TGNH_PREC_DOUBLE>), dim3(1), dim3(BLOCK), 0, s, h->velm, h->d.num_particles); break;
+        case TGNH_PREC_SINGLE: TGNH_LAUNCH((cmm_kernel<TGNH_PREC_SINGLE>), dim3(1), dim3(BLOCK), 0, s, h->bound.velm, h->d.num_particles); break;
+        case TGNH_PREC_MIXED: TGNH_LAUNCH((cmm_kernel<TGNH_PREC_MIXED>), dim3(1), dim3(BLOCK), 0, s, h->bound.velm, h->d.num_particles); break;
+        default: TGNH_LAUNCH((cmm_kernel<TGNH_PREC_DOUBLE>), dim3(1), dim3(BLOCK), 0, s, h->bound.velm, h->d.num_particles); break;
     }
     H_HIP(hipGetLastError());
     return TGNH_OK;

@@ -1,0 +1,69 @@
+// tgnh_host.h -- what the host units behind the C ABI (include/drude_tgnh.h) share: tgnh_topology.cpp, tgnh_lifecycle.cpp,
+// tgnh_exchange.cpp, tgnh_step.cpp, tgnh_queries.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
+// live in tgnh_kernels.hip, tgnh_gather.hip and tgnh_harness.hip.
+//
+// Reference semantics followed (scychon/openmm_drudeNose):
+//   Ref = platforms/reference/src/ReferenceDrudeTGNHKernels.cpp
+//   Cu  = platforms/cuda/src/CudaDrudeTGNHKernels.cpp
+//   API = openmmapi/src/DrudeTGNHIntegrator.cpp
+#ifndef TGNH_HOST_H_
+#define TGNH_HOST_H_
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "tgnh_context.h"
+
+using namespace tgnh;
+
+#pragma GCC visibility push(hidden)      // shared between the units, not with the world
+inline tgnh_status fail(tgnh_status code, const std::string& msg) {
+    tgnh_set_error(msg);
+    return code;
+}
+#define HIP_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(TGNH_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+#define CHECK_H(h) do { if (!(h)) return fail(TGNH_ERR_ARG, "null handle"); } while (0)
+
+// tgnh_topology.cpp
+void make_layout(tgnh_context* c);
+tgnh_status build_topology(tgnh_context* c, const tgnh_desc* d);
+void local_dof_terms(tgnh_context* c);
+tgnh_status finalize_thermostat(tgnh_context* c);
+// tgnh_lifecycle.cpp
+tgnh_status deferred_guard(tgnh_handle h, const char* what);
+// tgnh_step.cpp
+void note_status(tgnh_handle h, uint32_t flags);
+tgnh_status entry(tgnh_handle h, bool need_bufs);
+bool resident_now(tgnh_handle h);
+tgnh_status run_tile(tgnh_handle h, int ops, int kid, hipStream_t s, const double* scale = nullptr);
+GatherArgs gather_args(tgnh_handle h, const double* scale);
+ChainArgs chain_args(tgnh_handle h);
+tgnh_status run_chain_gather(tgnh_handle h, hipStream_t s, bool sum_only);
+tgnh_status materialize_chain(tgnh_handle h, hipStream_t s);
+tgnh_status settle_kick(tgnh_handle h, hipStream_t s);
+tgnh_status settle_end(tgnh_handle h, hipStream_t s);
+tgnh_status flush_impl(tgnh_handle h, hipStream_t s);
+
+// a launch between two events when timing is on (tgnh_timing_enable)
+struct Timed {
+    tgnh_context* c; hipStream_t s; int kid; tgnh_context::Timing::Ev* ev = nullptr;
+    Timed(tgnh_context* c_, hipStream_t s_, int kid_) : c(c_), s(s_), kid(kid_) {
+        if (!c->timing.on) return;
+        if (c->timing.only >= 0 && kid != c->timing.only) return;
+        if (c->timing.ev_used == c->timing.ev_pool.size()) {
+            tgnh_context::Timing::Ev e; e.kid = kid;
+            if (hipEventCreate(&e.a) != hipSuccess || hipEventCreate(&e.b) != hipSuccess) return;
+            c->timing.ev_pool.push_back(e);
+        }
+        ev = &c->timing.ev_pool[c->timing.ev_used++];
+        ev->kid = kid;
+        (void)hipEventRecord(ev->a, s);
+    }
+    ~Timed() { if (ev) (void)hipEventRecord(ev->b, s); }
+};
+#pragma GCC visibility pop
+
+#endif

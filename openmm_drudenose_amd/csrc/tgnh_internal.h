@@ -1,13 +1,10 @@
-// tgnh_internal.h -- shared between the host side (tgnh_host.cpp) and the
-// gfx950 kernels (tgnh_kernels.hip).  Not part of the ABI.
+// tgnh_internal.h -- what the host side (tgnh_*.cpp) and the gfx950 kernels (tgnh_*.hip) share: constants, the
+// launch-argument structs and the launchers.  The handle itself is host-only (tgnh_context.h).  Not part of the ABI.
 #ifndef TGNH_INTERNAL_H_
 #define TGNH_INTERNAL_H_
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <map>
-#include <string>
-#include <vector>
 
 #include "../../include/drude_tgnh.h"
 
@@ -317,133 +314,5 @@ hipError_t launch_plain_ke(int precision, const void* velm, const long long* for
 size_t tile_lds_bytes(int precision, int ops, bool hardwall, bool use_com);
 
 }  // namespace tgnh
-
-void tgnh_set_error(const std::string& msg);   // sets what tgnh_last_error() returns (tgnh_host.cpp)
-
-struct tgnh_context {
-    tgnh_desc d;                      // scalars only; pointers are nulled after create
-    int device = 0;
-    bool host_only = false;           // device == -1: topology / dof only, no launches
-    std::vector<double> h_state;      // host copy of the initial thermostat block
-    // host topology (A1), kept for parity queries
-    std::vector<double> mass;
-    std::vector<int> pair_drude, pair_parent, group, resid, normal;
-    std::vector<int> res_count, res_first;
-    std::vector<int> tile_start, tile_res;
-    std::vector<int2> res_entries;    // per-tile molecule entries
-    std::vector<int> big_first, big_count;   // molecules longer than a tile (COM from big_com_kernel)
-    int num_big = 0;
-    // the gather path: taken when the tiles cannot hold the topology (generic_reason says why); the reference's index lists, per particle
-    bool generic = false;
-    bool gather_chain = false;        // ... and its chain too: more than 34 thermostats, or links that do not fit the LDS (gather_chain_kernel)
-    std::string generic_reason;
-    std::vector<int2> g_res_table;
-    std::vector<int> g_resid, g_partner;
-    int *d_g_group = nullptr, *d_g_resid = nullptr, *d_g_partner = nullptr;
-    int2* d_g_res_table = nullptr;
-    int g_com_lanes = 64;
-    bool g_com_fresh = false;         // the COM table is of the velocities as they are (set by a KE pass; cleared by the next launch that writes velocities and on entry to every entry point)
-    void* d_g_com = nullptr;
-    double* d_g_scratch = nullptr;    // chains longer than 4 links of more than 34 thermostats: a row of 4 C + 1 doubles each
-    void* d_g_x0 = nullptr;           // harness: the tether sites as tgnh_harness_pack_sites was handed them
-    int2* d_big_table = nullptr;
-    void* d_big_com = nullptr;
-    std::vector<uint32_t> meta;
-    std::vector<int2> wave_tile;      // wave tiles (empty: some molecule or pair does not fit a wavefront)
-    std::vector<uint32_t> wmeta;
-    std::vector<uint32_t> tile_pat, wtile_pat;    // per 512-slot tile: period | molecules << 8 | pattern << 16; per wave tile: period | pattern << 8; 0 = none
-    std::vector<uint32_t> pattern, wpattern;      // 64 words per pattern
-    uint32_t *d_tile_pat = nullptr, *d_pattern = nullptr, *d_wpattern = nullptr;
-    int num_wtiles = 0;
-    int2* d_wave_tile = nullptr;
-    uint32_t* d_wmeta = nullptr;
-    bool tail_summed = false;         // the last KE launch summed its rows itself (wke_kernel's tail sum): no row-sum launch
-    bool wave_ke = false;             // the KE passes run over the wave tiles (wke_kernel)
-    // dof bookkeeping (A2)
-    std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction
-    std::vector<double> dof, nkbt;
-    double realkbT = 0, drudekbT = 0;
-    tgnh::ChainLayout L{};
-    // device
-    uint32_t* d_meta = nullptr;
-    int* d_tile_start = nullptr;
-    int* d_tile_res = nullptr;
-    int2* d_res_table = nullptr;
-    double* d_partials = nullptr;
-    double* d_state = nullptr;        // thermostat block
-    double* d_stage = nullptr;        // same layout: where an in-kernel chain leaves the advanced block
-    bool stage_pending = false;       // d_stage is newer than d_state; the next chain_kernel launch commits it
-    int sweep_reverse = 0;            // direction of the next streaming launch (alternates)
-    bool alternate_sweeps = true;
-    int inline_sum_rows = tgnh::CHAIN_INLINE_SUM_ROWS;
-    bool inline_sum_all = false;      // more rows than that (and < 2 M slots): all four wavefronts of the rescale launch sum them (sum_rows = 2)
-    bool sum_pending = false;         // with chain_pending: the partial rows are not summed yet either (the rescale launch does both)
-    bool chain_pending = false, chain_pending_twice = false;   // summed KE waits for the next rescale launch to run the chain
-    bool carry_pending = false;       // ... and that KE is the last chain's ke_post (ChainArgs::ke_carry), not ke_red
-    bool carry_ok = false;            // TGNH_FLAG_TRUST_STATE_CHANGED is in effect for this handle (set, unsharded, no molecule spans two groups)
-    bool inline_chain = false;        // numNHChains == 1: the chain runs inside the rescale launch
-    uint32_t* d_status = nullptr;
-    uint32_t* h_status_seen = nullptr;   // pinned: where read-backs of the status word land (periodic, and at every query)
-    int failed_code = 0;                 // sticky: a failure the device reported (note_status); every later entry returns it
-    std::string failed;
-    double* d_scalar = nullptr;       // plain KE: [0] the result, [1 ..] work-group partials
-    // harness call-outs (tgnh_harness.hip)
-    int4* d_cl_atoms = nullptr; double* d_cl_dist = nullptr; int num_clusters = 0;
-    int4* d_vs_atoms = nullptr; double* d_vs_w = nullptr; int num_sites = 0;
-    int grid = 0, num_tiles = 0, gb = 1;
-    int num_cus = 256, grid_override = 0, ke_parts = 0;
-    std::map<int, int> grid_cache;    // ops (+hard-wall bit) -> persistent grid size
-    // bound buffers
-    void *posq = nullptr, *posq_corr = nullptr, *velm = nullptr, *pos_delta = nullptr;
-    const void* force = nullptr;
-    // run state
-    bool scale_pending = false;       // DEFER_SCALE: velm lags by scale[]
-    bool kick_pending = false;        // DEFER_SCALE: velm also lags by the second half kick (force buffer unchanged since)
-    bool end_pending = false;         // RESIDENT_STEP: the whole end half of the last step waits for the next step_begin's launch
-    unsigned int* d_sync = nullptr;   // step_kernel's meeting: launch number
-    unsigned long long* d_rows = nullptr;   // ... and the tagged rows (uncached)
-    unsigned long long* self_box = nullptr;      // RESIDENT_STEP without a sharded exchange: a private one-rank mailbox
-    unsigned long long* d_self_misc = nullptr;   // ... its counter, latch and peer table
-    tgnh::XchgArgs self_x{};
-    int resident_grid[5][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}};   // step_kernel's grid by kind and hard wall
-    int resident_share = 1, last_step_kind = 0;
-    int wresident_per_cu = 0, wresident_grid = 0;   // the same for wstep_kernel (0: none, or no wave tiles)
-    int resident_per_cu = 0;          // work-groups of step_kernel per compute unit that the census at create found resident together (0: none -- the handle steps the DEFER_SCALE way)
-    bool first_half_done = false;     // DEFER_SCALE: chain for the coming step's first half already run
-    bool end_folded = false;          // the last fused end half left the kick to its rescale launch (OP_PREKICK: algorithmic bytes of KID_SCALE)
-    bool ke_carry = false;            // TRUST_STATE_CHANGED: ke_post of the last end half IS the kinetic energy of the stored velocities
-    double time = 0;
-    int64_t step_count = 0;
-    tgnh_allreduce_fn allreduce = nullptr;
-    void* allreduce_user = nullptr;
-    void* rccl_comm = nullptr;        // ncclComm_t: the library enqueues ncclAllReduce itself (tgnh_rccl_init / tgnh_set_rccl_comm)
-    bool rccl_owned = false;
-    unsigned long long* d_x_stat = nullptr;   // mailbox wait statistics (XchgArgs::stat)
-    uint8_t* d_sflag = nullptr;               // harness: packed tether sites (ForceArgs::sflag / sbase / sites), tgnh_harness_pack_sites
-    uint32_t* d_sbase = nullptr;
-    void* d_sites = nullptr;
-    int lat_k = 0, lat_side = 0, lat_mol0 = 0;              // ... or lattice sites: the hint (lat_k = 0: none), and whether pack_sites found it to hold
-    double lat_spacing = 0;
-    std::vector<double> lat_geom;
-    bool lat_on = false;
-    unsigned char* d_lat_tab = nullptr;
-    // mailbox exchange (tgnh_exchange_*): replaces the hook when attached
-    tgnh::XchgArgs x{};
-    bool xchg_on = false, xwait_pending = false;
-    int x_world = 0, x_rank = 0;
-    unsigned long long* x_mailbox = nullptr;  // mine (uncached device memory)
-    unsigned long long** d_x_peers = nullptr; // device table of every rank's mailbox
-    std::vector<void*> x_opened;              // peers' mailboxes opened by IPC (to close)
-    unsigned long long* d_x_seq = nullptr;
-    unsigned int* d_x_dead = nullptr;
-    // timing
-    bool timing = false;
-    int timing_only = -1;             // >= 0: only this kernel id is timed
-    struct Ev { hipEvent_t a, b; int kid; };
-    std::vector<Ev> ev_pool;
-    size_t ev_used = 0;
-    double t_total[tgnh::KID_COUNT] = {0};
-    int64_t t_count[tgnh::KID_COUNT] = {0};
-};
 
 #endif

@@ -1,0 +1,679 @@
+// tgnh_step.cpp -- step orchestration (A11): device-reported failures, launch sizing, run_tile / run_gather / run_chain / run_resident, tgnh_step_*, flush, clock
+#include "tgnh_host.h"
+
+// ---------------------------------------------------------------------------
+// device-reported failures
+// ---------------------------------------------------------------------------
+constexpr int64_t STATUS_POLL_EVERY = 64;
+
+// Called wherever the status word has reached the host.  bit 2: a mailbox exchange timed out -- from then on the
+// kinetic-energy sums are incomplete and the ranks' thermostats diverge; bit 0 in dualNH mode: the Reference platform
+// throws (Ref :311-312).  Both make every later step / query fail (entry()).  bit 1 (the harness SHAKE did not
+// converge) is reported by tgnh_get_status_flags only: OpenMM's own constraint kernels do not throw either.
+void note_status(tgnh_handle h, uint32_t flags) {
+    if (h->status.failed_code) return;
+    // bit 3 first: when step_kernel's work-group 0 gives up on a row it sets bit 3 and withholds the sums, and every other
+    // work-group then runs into its own time-out (bit 2) -- a residency problem, not a link fault
+    if (flags & 8u) {
+        h->status.failed_code = TGNH_ERR_STATE;
+        h->status.failed = "resident step (noticed at step " + std::to_string((long long)h->run.step_count) + "): the launch's work-groups did "
+                    "not all become resident within the time limit (TGNH_FLAG_RESIDENT_STEP needs the device to itself)";
+        if (flags & 4u) h->status.failed += "; the waiting work-groups timed out in turn (status bits 2 and 3)";
+    } else if (flags & 16u) {
+        h->status.failed_code = TGNH_ERR_STATE;
+        h->status.failed = "kinetic-energy pass (noticed at step " + std::to_string((long long)h->run.step_count) + "): work-group 0 did not "
+                    "receive every work-group's row of sums within the time limit (the sums were left as NaN: nothing integrated "
+                    "on with a partial sum); the device is shared with something that keeps this launch's work-groups from running "
+                    "-- or a chain was handed a NaN kinetic energy: with an all-reduce attached, the rank on which that happened";
+    } else if (flags & 4u) {
+        h->status.failed_code = TGNH_ERR_STATE;
+        h->status.failed = "mailbox exchange timed out (noticed at step " + std::to_string((long long)h->run.step_count) +
+                    "): a peer did not send its kinetic-energy sums; the run cannot continue";
+    } else if ((flags & 1u) && h->d.mode == TGNH_MODE_DUALNH) {
+        h->status.failed_code = TGNH_ERR_HARDWALL;
+        h->status.failed = "Drude particle moved too far beyond hard wall constraint";        // Ref :311-312
+    }
+}
+
+// ---------------------------------------------------------------------------
+// launches
+// ---------------------------------------------------------------------------
+static tgnh_status need_buffers(tgnh_handle h) {
+    if (h->host_only) return fail(TGNH_ERR_STATE, "host-only handle (device -1): no GPU work can be launched on it");
+    if (!h->bound.velm) return fail(TGNH_ERR_STATE, "tgnh_bind_buffers has not been called");
+    return TGNH_OK;
+}
+
+static TileArgs tile_args(tgnh_handle h, const double* scale) {
+    TileArgs a{};
+    a.posq = h->bound.posq; a.posq_corr = h->bound.posq_corr; a.velm = h->bound.velm;
+    a.force = reinterpret_cast<const long long*>(h->bound.force); a.pos_delta = h->bound.pos_delta;
+    a.meta = h->topo.d_meta; a.tile_start = h->topo.d_tile_start; a.tile_res = h->topo.d_tile_res; a.res_table = h->topo.d_res_table;
+    a.big_com = h->topo.d_big_com;
+    a.scale = scale ? scale : h->thermo.d_state + h->thermo.L.off_scale;
+    a.partials = h->thermo.d_partials; a.status = h->status.d_word;
+    a.num_tiles = h->topo.num_tiles; a.padded = h->d.padded_num_particles; a.num_groups = h->thermo.L.G;
+    a.reverse = h->run.sweep_reverse;
+    a.wave_tile = h->topo.d_wave_tile; a.wmeta = h->topo.d_wmeta; a.num_wtiles = h->topo.num_wtiles;
+    a.tile_pat = h->topo.d_tile_pat; a.pattern = h->topo.d_pattern; a.wpattern = h->topo.d_wpattern;
+    a.use_com = (h->d.mode == TGNH_MODE_TGNH && h->d.use_com_temp_group) ? 1 : 0;
+    a.hardwall = h->d.max_drude_distance > 0 ? 1 : 0;                         // Ref :299, Cu :372
+    a.dt = h->d.step_size; a.max_dist = h->d.max_drude_distance;
+    a.hw_scale = std::sqrt(h->d.kB * h->d.drude_temperature);                 // Ref :300, Cu :299
+    return a;
+}
+
+// persistent grid = the work-groups of this instantiation that are resident at once (occupancy x CUs), so every
+// work-group walks the same number of tiles (+-1) and there is no partial last wave of work-groups
+static int grid_for(tgnh_handle h, int ops, bool hardwall, size_t lds) {
+    if (h->cfg.grid_override > 0) return std::min(h->topo.num_tiles, h->cfg.grid_override);
+    const int key = ops | (hardwall ? 1 << 16 : 0);
+    auto it = h->cfg.grid_cache.find(key);
+    if (it != h->cfg.grid_cache.end()) return it->second;
+    int per_cu = tile_blocks_per_cu(h->d.precision, ops, h->cfg.gb, lds, (ops & OP_SCALE) && h->cfg.inline_chain && h->thermo.L.C > 1);
+    if (per_cu < 1) per_cu = 2;
+    int g = std::min(std::min(h->topo.num_tiles, per_cu * h->cfg.num_cus), GRID_CAP);
+    if (g < 1) g = 1;
+    h->cfg.grid_cache[key] = g;
+    return g;
+}
+
+// wke_kernel: the resident work-groups, at most one per four wavefront tiles
+static int wave_grid_for(tgnh_handle h, int ops) {
+    const int nw = h->topo.num_wtiles, need = (nw + TBLOCK / 64 - 1) / (TBLOCK / 64);
+    if (h->cfg.grid_override > 0) return std::max(1, std::min(need, h->cfg.grid_override));
+    const int key = ops | (1 << 17);
+    auto it = h->cfg.grid_cache.find(key);
+    if (it != h->cfg.grid_cache.end()) return it->second;
+    int per_cu = wke_blocks_per_cu(h->d.precision, ops, h->cfg.gb);
+    if (per_cu < 1) per_cu = 2;
+#ifdef TGNH_TUNING
+    if (const char* e = getenv("TGNH_WKE_PER_CU")) { int v = atoi(e); if (v >= 1) per_cu = std::min(per_cu, v); }
+#endif
+    int g = std::max(1, std::min(std::min(need, per_cu * h->cfg.num_cus), GRID_CAP));
+    h->cfg.grid_cache[key] = g;
+    return g;
+}
+
+static tgnh_status commit_stage(tgnh_handle h, hipStream_t s);
+
+// words of the tagged-row area (TileArgs::rows) and what a launch of `grid` work-groups with NT thermostats writes there
+// (row_word in tgnh_kernels.hip: rows in blocks of 64, word-major inside a block, two words per thermostat)
+static size_t tagged_words_allocated() { return (size_t)2 * GRID_CAP * CHAIN_INLINE_SUM_NT; }
+static size_t tagged_words_touched(int grid, int NT) {
+    if (grid < 1) return 0;
+    const int r = grid - 1, j = 2 * NT - 1;
+    return ((size_t)(r >> 6) * (2 * CHAIN_INLINE_SUM_NT) + j) * 64 + (r & 63) + 1;
+}
+
+// The sizes a streaming launch is bound by, checked on the host before it goes out: one row of partial sums per work-group
+// in a table of GRID_CAP rows; tagged rows only with G <= 8; a wave-tile table of num_wtiles + 1 entries in which every tile
+// holds <= 64 slots (tgnh_create built them so: this is the launch-side half of that contract).
+static tgnh_status check_launch(tgnh_handle h, const TileArgs& a, int grid, int block, bool wave, bool tagged) {
+    if (grid < 1 || grid > GRID_CAP || grid > h->cfg.grid) return fail(TGNH_ERR_STATE, "internal: grid exceeds the partial-row table");
+    if (wave) {
+        if (!a.wave_tile || (int)h->topo.wave_tile.size() != a.num_wtiles + 1 || a.num_wtiles < 1)
+            return fail(TGNH_ERR_STATE, "internal: wave-tile table does not match the launch");
+        if ((long long)grid * (block / 64) > (long long)a.num_wtiles + (block / 64) - 1)
+            return fail(TGNH_ERR_STATE, "internal: more work-groups than wave tiles");
+    } else if (grid > h->topo.num_tiles) return fail(TGNH_ERR_STATE, "internal: more work-groups than tiles");
+    if (tagged) {
+        if (!a.rows || !a.sync || h->thermo.L.NT > CHAIN_INLINE_SUM_NT || tagged_words_touched(grid, h->thermo.L.NT) > tagged_words_allocated())
+            return fail(TGNH_ERR_STATE, "internal: tagged rows do not fit their area");
+    }
+    return TGNH_OK;
+}
+
+extern "C" tgnh_status tgnh_get_launch_bounds(tgnh_handle h, int32_t out[8]) {
+    CHECK_H(h);
+    if (!out) return fail(TGNH_ERR_ARG, "null out");
+    const int nw = h->topo.num_wtiles;
+    int g = h->topo.num_tiles;                                                    // tile_kernel / step_kernel: at most one work-group per tile
+    if (nw > 0) g = std::max(g, (nw + TBLOCK / 64 - 1) / (TBLOCK / 64));     // wke_kernel: per four wave tiles (wstep_kernel: per eight)
+    g = std::max(1, std::min(g, GRID_CAP));
+    const bool tagged = h->thermo.L.NT <= CHAIN_INLINE_SUM_NT && (h->meet.d_rows != nullptr || h->host_only);
+    out[0] = h->topo.num_tiles; out[1] = nw; out[2] = (int)h->topo.wave_tile.size(); out[3] = g;
+    out[4] = h->cfg.grid; out[5] = tagged ? (int)tagged_words_allocated() : 0;
+    out[6] = tagged ? (int)tagged_words_touched(g, h->thermo.L.NT) : 0; out[7] = h->thermo.L.NT;
+    return TGNH_OK;
+}
+
+static tgnh_status run_big_com(tgnh_handle h, bool kick, hipStream_t s) {
+    BigComArgs b{};
+    b.table = h->topo.d_big_table; b.n = h->topo.num_big; b.velm = h->bound.velm;
+    b.force = reinterpret_cast<const long long*>(h->bound.force); b.padded = h->d.padded_num_particles;
+    b.kick = kick ? 1 : 0; b.dt = h->d.step_size;
+    b.big_com = h->topo.d_big_com;
+    b.partials = h->thermo.d_partials + (size_t)GRID_CAP * h->thermo.L.NT; b.NT = h->thermo.L.NT; b.G = h->thermo.L.G;
+    Timed t(h, s, KID_OTHER);
+    HIP_OK(launch_big_com(h->d.precision, b, s));
+    return TGNH_OK;
+}
+
+// ---- the gather path (tgnh_gather.hip): the same operation masks, by global index ----
+GatherArgs gather_args(tgnh_handle h, const double* scale) {
+    GatherArgs a{};
+    a.posq = h->bound.posq; a.posq_corr = h->bound.posq_corr; a.velm = h->bound.velm;
+    a.force = reinterpret_cast<const long long*>(h->bound.force); a.pos_delta = h->bound.pos_delta;
+    a.group = h->gather.d_group; a.resid = h->gather.d_resid;
+    a.res_table = h->gather.d_res_table; a.partner = h->gather.d_partner; a.com = h->gather.d_com;
+    a.scale = scale ? scale : h->thermo.d_state + h->thermo.L.off_scale;
+    a.partials = h->thermo.d_partials; a.status = h->status.d_word;
+    a.n = h->d.num_particles; a.padded = h->d.padded_num_particles;
+    a.com_lanes = h->gather.com_lanes;
+    a.use_com = (h->d.mode == TGNH_MODE_TGNH && h->d.use_com_temp_group) ? 1 : 0;
+    a.n_res = a.use_com ? (int)h->gather.res_table.size() : 0;
+    a.G = h->thermo.L.G; a.NT = h->thermo.L.NT;
+    a.hardwall = h->d.max_drude_distance > 0 ? 1 : 0;                         // Ref :299, Cu :372
+    a.dt = h->d.step_size; a.max_dist = h->d.max_drude_distance;
+    a.hw_scale = std::sqrt(h->d.kB * h->d.drude_temperature);                 // Ref :300, Cu :299
+    return a;
+}
+
+// One operation mask of run_tile as launches of the gather kernels: the velocity / position part (rescale, kick, drift,
+// posDelta, move, hard wall) first, the kinetic energies of what it stored after it (K's order: Cu :384-388 then :474-488).
+static tgnh_status run_gather(tgnh_handle h, int ops, int kid, hipStream_t s, const double* scale) {
+    GatherArgs a = gather_args(h, scale);
+    if ((ops & (OP_POSDELTA | OP_MOVE)) && !h->bound.pos_delta) return fail(TGNH_ERR_STATE, "posDelta buffer not bound");
+    const int upd = ops & (OP_SCALE | OP_KICK | OP_DRIFT | OP_POSDELTA | OP_MOVE | OP_PREKICK);
+    if (ops & OP_NOSTORE) return fail(TGNH_ERR_STATE, "internal: the gather path stores every kick");
+    Timed t(h, s, kid);
+    if (upd) {
+        // K :474-479 before :351-353: v - v_com of the velocities about to be rescaled.  On this path every rescale follows a
+        // kinetic-energy pass and its chain inside one entry point (the flags that would part them are ignored), so the table
+        // that pass left is of these very velocities: not computed again
+        if ((upd & OP_SCALE) && a.use_com && !(h->owed.g_com_fresh && !(upd & OP_PREKICK))) {
+            a.kick_com = (upd & OP_PREKICK) ? 1 : 0;
+            HIP_OK(launch_gather_com(h->d.precision, a, s));
+        }
+        h->owed.g_com_fresh = false;
+        a.ops = upd;
+        HIP_OK(launch_gather_update(h->d.precision, a, s));
+    }
+    if (ops & OP_KE) {
+        a.kick_com = 0;
+        if (a.use_com) HIP_OK(launch_gather_com(h->d.precision, a, s));
+        const int grid = gather_ke_grid(a);
+        HIP_OK(launch_gather_ke(h->d.precision, a, grid, s));
+        h->run.ke_parts = grid;
+        h->owed.tail_summed = false;
+        h->owed.g_com_fresh = a.use_com != 0;
+    }
+    return TGNH_OK;
+}
+
+// sum the rows of the gather path's kinetic-energy kernel [+ all-reduce], run the chain: more than 34 thermostats / long links
+tgnh_status run_chain_gather(tgnh_handle h, hipStream_t s, bool sum_only) {
+    ChainArgs a = chain_args(h);
+    Timed t(h, s, KID_CHAIN);
+    HIP_OK(launch_gather_rowsum(h->thermo.d_partials, h->run.ke_parts, h->thermo.L.NT, h->thermo.d_state + h->thermo.L.off_ke_red, s));
+    if (h->xchg.allreduce && h->xchg.allreduce(h->thermo.d_state + h->thermo.L.off_ke_red, h->thermo.L.NT, (void*)s, h->xchg.allreduce_user) != 0)
+        return fail(TGNH_ERR_HIP, "all-reduce hook failed");
+    if (!sum_only) HIP_OK(launch_gather_chain(a, h->gather.d_scratch, s));
+    return TGNH_OK;
+}
+
+tgnh_status run_tile(tgnh_handle h, int ops, int kid, hipStream_t s, const double* scale) {
+    if (h->gather.generic) return run_gather(h, ops, kid, s, scale);
+    TileArgs a = tile_args(h, scale);
+    bool inline_chain = false;
+    bool pingpong = false;
+    if ((ops & OP_SCALE) && h->owed.chain_pending && !scale) {           // this rescale launch runs the chain itself
+        // A carried chain (no KE pass before it: nothing has committed the staged block on the way) reads the thermostat where the
+        // last in-kernel chain left it and writes the other copy: the two blocks differ only in what a chain writes, and a
+        // chain writes all of that every time (eta, etaDot, etaDotDot, KE before / after, the scale factors, KESum)
+        pingpong = h->owed.carry_pending && h->owed.stage_pending;
+        if (h->owed.stage_pending && !pingpong) { tgnh_status rc = commit_stage(h, s); if (rc) return rc; }
+        a.chain_on = 1;
+        a.chain = chain_args(h);                                    // (takes note of the staged block: cleared there)
+        a.chain.chain_twice = h->owed.chain_pending_twice ? 1 : 0;
+        a.chain.ke_carry = h->owed.carry_pending ? 1 : 0;
+        a.sum_rows = h->owed.sum_pending ? (h->run.ke_parts + h->topo.num_big <= h->cfg.inline_sum_rows ? 1 : 2) : 0;
+        a.x_wait = h->owed.xwait_pending ? 1 : 0;
+        a.st_in = pingpong ? h->thermo.d_stage : h->thermo.d_state;
+        a.st_out = pingpong ? h->thermo.d_state : h->thermo.d_stage;
+        inline_chain = true;
+    }
+    if ((ops & (OP_POSDELTA | OP_MOVE)) && !h->bound.pos_delta) return fail(TGNH_ERR_STATE, "posDelta buffer not bound");
+    size_t lds = tile_lds_bytes(h->d.precision, ops, a.hardwall != 0, a.use_com != 0);
+    if ((ops & OP_KE) && h->cfg.gb == 0) lds += sizeof(double) * (TBLOCK / 64) * h->thermo.L.G;   // per-wave group bins
+    // the pure KE passes (KE, kick+KE, kick+KE unstored) run over the wave tiles when the topology has them
+    const bool wave = h->cfg.wave_ke && (ops & OP_KE) && !(ops & ~(OP_KE | OP_KICK | OP_NOSTORE));
+    const int grid = wave ? wave_grid_for(h, ops) : grid_for(h, ops, a.hardwall != 0, lds);
+    if ((ops & OP_KE) && h->owed.stage_pending && !inline_chain) {      // commit the staged thermostat block on the way
+        a.commit_len = h->thermo.L.total; a.commit_src = h->thermo.d_stage; a.commit_dst = h->thermo.d_state;
+        a.commit_skip = h->thermo.L.off_ke_red; a.commit_skip_n = h->thermo.L.NT;
+        h->owed.stage_pending = false;
+    }
+    if (ops & OP_KE) {
+        // wave tiles: where a launch that only sums the partial rows would follow (an all-reduce waits for the sums, or the
+        // system is too large for the next rescale launch to sum them in its prologue), work-group 0 of this launch does it
+        h->owed.tail_summed = wave && h->meet.d_rows && !h->xchg.on && h->thermo.L.NT <= CHAIN_INLINE_SUM_NT &&
+                         !(h->cfg.inline_chain && !h->xchg.allreduce && (grid + h->topo.num_big <= h->cfg.inline_sum_rows || h->cfg.inline_sum_all));
+        if (h->owed.tail_summed) { a.tail_sum = 1; a.rows = h->meet.d_rows; a.sync = h->meet.d_sync; a.ke_red = h->thermo.d_state + h->thermo.L.off_ke_red; }
+        h->run.ke_parts = grid;
+        if (h->topo.num_big && a.use_com) {
+            // COM velocity of every big molecule for the velocities this launch reduces: the current ones, or the
+            // kicked ones (the kick is linear, so sum m v' = sum (m v + dt/2 F) needs no second pass).  The rescale
+            // launches that follow reuse the table: velocities do not change between a KE pass and its rescale.
+            tgnh_status rc = run_big_com(h, (ops & OP_KICK) != 0, s); if (rc) return rc;
+        }
+    }
+    { tgnh_status rc = check_launch(h, a, grid, TBLOCK, wave, a.tail_sum != 0); if (rc) return rc; }
+    {
+        Timed t(h, s, kid);
+        if (wave) HIP_OK(launch_wke(h->d.precision, ops, h->cfg.gb, a, grid, s));
+        else HIP_OK(launch_tile(h->d.precision, ops, h->cfg.gb, a, grid, lds, s));
+    }
+    if (inline_chain) {            // the advanced thermostat now lies in d_stage (carried from a staged block: back in d_state)
+        h->owed.chain_ran(); h->owed.stage_pending = !pingpong;
+    }
+    if (h->cfg.alternate_sweeps) h->run.sweep_reverse ^= 1;      // the next streaming launch starts where this one ends
+    return TGNH_OK;
+}
+
+ChainArgs chain_args(tgnh_handle h) {
+    ChainArgs a{};
+    a.L = h->thermo.L; a.st = h->thermo.d_state; a.partials = h->thermo.d_partials; a.nparts = h->run.ke_parts;
+    a.nbig = h->topo.num_big;
+    a.dt = h->d.step_size; a.S = h->d.drude_steps_per_real_step;
+    a.dtc = a.dt / a.S; a.inv_dtc = 1.0 / a.dtc;                               // Cu :440-443
+    a.realkbT = h->thermo.realkbT; a.drudekbT = h->thermo.drudekbT;
+    // chains of 5-16 links: chain_long_kernel<C>, the links in registers (round 3 ran them a link per lane, chain_lanes_run: kept
+    // behind a switch for the comparison in profiles/r04_chain_cost.md)
+    a.lanes = 0;
+#ifdef TGNH_TUNING
+    if (const char* e = getenv("TGNH_CHAIN_LANES")) a.lanes = e[0] != '0';
+#endif
+    a.stage = h->thermo.d_stage;
+    a.status = h->status.d_word;
+    if (h->xchg.on) a.x = h->xchg.args;
+    a.commit = h->owed.stage_pending ? 1 : 0;     // every chain_kernel launch takes over a staged block first
+    h->owed.stage_pending = false;
+    return a;
+}
+
+// a staged block with no chain_kernel launch coming up: commit it by a launch that does nothing else
+static tgnh_status commit_stage(tgnh_handle h, hipStream_t s) {
+    if (!h->owed.stage_pending) return TGNH_OK;
+    ChainArgs a = chain_args(h);
+    a.do_sum = 0; a.do_chain = 0;
+    HIP_OK(launch_chain(a, s));
+    return TGNH_OK;
+}
+
+// sum the work-group partials, all-reduce across ranks when sharded, run the chain
+static tgnh_status run_chain(tgnh_handle h, hipStream_t s, bool twice) {
+    if (h->gather.chain) return run_chain_gather(h, s, false);
+    ChainArgs a = chain_args(h);
+    a.chain_twice = twice ? 1 : 0;
+    if (h->xchg.on) {                // sharded, mailbox exchange: the sum launch sends; whoever runs the chain waits
+        a.do_sum = 1; a.x_send = 1;
+        if (h->cfg.inline_chain) {
+            a.do_chain = 0;
+            { Timed t(h, s, KID_CHAIN); HIP_OK(launch_chain(a, s)); }
+            h->owed.chain_pending = true; h->owed.chain_pending_twice = twice; h->owed.xwait_pending = true;
+        } else {
+            a.do_chain = 1; a.x_wait = 1;
+            Timed t(h, s, KID_CHAIN);
+            HIP_OK(launch_chain(a, s));
+        }
+        return TGNH_OK;
+    }
+    if (h->cfg.inline_chain && !h->xchg.allreduce && h->thermo.L.NT <= CHAIN_INLINE_SUM_NT &&
+        (h->run.ke_parts + h->topo.num_big <= h->cfg.inline_sum_rows || h->cfg.inline_sum_all)) {
+        // Unsharded, one-link chains, G <= 8: nothing to launch -- the next rescale launch sums the partial rows and
+        // runs the chain in its prologue (3 launches per step).  Up to 256 rows its chain wavefront reads them alone
+        // (one batch of loads); more rows are read by all four wavefronts, a quarter each, ahead of their tile
+        // loads (read by one wavefront they were a chain of L2 misses on the critical path, +7-9 us) -- that up to 2 M
+        // slots (inline_sum_all).  +4 % steps/s at 625 k slots, +7-17 % for small systems
+        // (profiles/r01_tuning_sweep.log).
+        h->owed.chain_pending = true; h->owed.sum_pending = true; h->owed.chain_pending_twice = twice;
+        return TGNH_OK;
+    }
+    const bool summed = h->owed.tail_summed;       // wke_kernel's tail sum: ke_red is complete, no row-sum launch (and nothing staged: a KE launch commits)
+    h->owed.tail_summed = false;
+    if (h->cfg.inline_chain) {           // sum (and all-reduce) now, the chain itself inside the next rescale launch
+        a.do_sum = 1; a.do_chain = 0;
+        if (!summed) { Timed t(h, s, KID_CHAIN); HIP_OK(launch_chain(a, s)); }
+        if (h->xchg.allreduce && h->xchg.allreduce(h->thermo.d_state + h->thermo.L.off_ke_red, h->thermo.L.NT, (void*)s, h->xchg.allreduce_user) != 0)
+            return fail(TGNH_ERR_HIP, "all-reduce hook failed");
+        h->owed.chain_pending = true; h->owed.chain_pending_twice = twice;
+        return TGNH_OK;
+    }
+    if (h->xchg.allreduce) {
+        a.do_sum = 1; a.do_chain = 0;
+        if (!summed) { Timed t(h, s, KID_CHAIN); HIP_OK(launch_chain(a, s)); }
+        if (h->xchg.allreduce(h->thermo.d_state + h->thermo.L.off_ke_red, h->thermo.L.NT, (void*)s, h->xchg.allreduce_user) != 0)
+            return fail(TGNH_ERR_HIP, "all-reduce hook failed");
+        a.do_sum = 0; a.do_chain = 1; a.commit = 0;
+        { Timed t(h, s, KID_CHAIN); HIP_OK(launch_chain(a, s)); }
+    } else {
+        a.do_sum = summed ? 0 : 1; a.do_chain = 1;
+        Timed t(h, s, KID_CHAIN);
+        HIP_OK(launch_chain(a, s));
+    }
+    return TGNH_OK;
+}
+
+// a chain that is still waiting for its rescale launch is run now, in place, by the standalone kernel
+tgnh_status materialize_chain(tgnh_handle h, hipStream_t s) {
+    { tgnh_status rc = settle_end(h, s); if (rc) return rc; }
+    if (!h->owed.chain_pending) return commit_stage(h, s);
+    ChainArgs a = chain_args(h);
+    a.do_sum = h->owed.sum_pending ? 1 : 0; a.do_chain = 1; a.chain_twice = h->owed.chain_pending_twice ? 1 : 0;
+    a.x_wait = h->owed.xwait_pending ? 1 : 0;
+    a.ke_carry = h->owed.carry_pending ? 1 : 0;
+    { Timed t(h, s, KID_CHAIN); HIP_OK(launch_chain(a, s)); }
+    h->owed.chain_ran();
+    return TGNH_OK;
+}
+
+// ---- TGNH_FLAG_RESIDENT_STEP: one launch per time step (step_kernel) ----
+// Eligible: deferred pass structure, one-link chains (the chain runs inside the launch), at most 8 temperature groups,
+// and an exchange the kernel can do itself (none, or the mailboxes -- a collective hook is a launch of its own).
+static bool resident_kind(tgnh_handle h, int kind) {
+    if (!((h->d.flags & TGNH_FLAG_RESIDENT_STEP) && h->cfg.inline_chain && h->cfg.gb != 0 && h->thermo.L.NT <= CHAIN_INLINE_SUM_NT &&
+          (h->xchg.on || !h->xchg.allreduce))) return false;
+    if (kind == 0 && h->cfg.wresident_per_cu > 0) return true;           // wstep_kernel: a whole deferred step, chains of 1-4 links
+    return h->cfg.resident_per_cu > 0 && h->thermo.L.C == 1;                    // step_kernel: every kind, one-link chains
+}
+bool resident_now(tgnh_handle h) {
+    return resident_kind(h, (h->d.flags & TGNH_FLAG_DEFER_SCALE) ? 0 : 1);
+}
+
+extern "C" tgnh_status tgnh_get_step_path(tgnh_handle h, int* gather, const char** reason) {
+    CHECK_H(h);
+    if (gather) *gather = h->gather.generic ? (h->gather.chain ? 2 : 1) : 0;
+    if (reason) *reason = h->gather.reason.c_str();
+    return TGNH_OK;
+}
+
+extern "C" tgnh_status tgnh_get_resident_kernel(tgnh_handle h, int* which) {
+    CHECK_H(h);
+    if (!which) return fail(TGNH_ERR_ARG, "null out");
+    const int kind = (h->d.flags & TGNH_FLAG_DEFER_SCALE) ? 0 : 1;
+    *which = !resident_kind(h, kind) ? 0 : (kind == 0 && h->cfg.wresident_per_cu > 0) ? 2 : 1;
+    return TGNH_OK;
+}
+
+// One launch of step_kernel.  kind 0: a whole deferred step (the last step's end half + this step's begin half, both chain
+// halves); 1 / 2: the begin / end half of the reference's pass structure; 3 / 4: the same around the constraint call-outs.
+static tgnh_status run_resident(tgnh_handle h, hipStream_t s, int kind) {
+    if (h->owed.stage_pending) { tgnh_status rc = commit_stage(h, s); if (rc) return rc; }
+    TileArgs a = tile_args(h, nullptr);
+    const int ops2 = step_kind_ops2(kind);
+    if ((ops2 & OP_POSDELTA) && !h->bound.pos_delta) return fail(TGNH_ERR_STATE, "posDelta buffer not bound");
+    const bool hw = a.hardwall != 0 && (ops2 & (OP_DRIFT | OP_MOVE));
+    const size_t lds = tile_lds_bytes(h->d.precision, ops2, hw, a.use_com != 0);
+    int& grid = h->cfg.resident_grid[kind][hw ? 1 : 0];
+    if (grid == 0 && !(kind == 0 && h->cfg.wresident_per_cu > 0)) {       // the work-groups that are resident at once (counted at create; never more than this kind's own occupancy)
+        int per_cu = std::min(h->cfg.resident_per_cu, step_blocks_per_cu(h->d.precision, h->cfg.gb, kind, lds));
+        if (per_cu < 1) return fail(TGNH_ERR_HIP, "step_kernel: occupancy query failed");
+        grid = std::max(1, std::min(std::min(h->topo.num_tiles, per_cu * h->cfg.num_cus / h->cfg.resident_share), GRID_CAP));
+    }
+    a.chain_on = 1;
+    a.chain = chain_args(h);
+    a.chain.chain_twice = kind == 0 ? 1 : 0;
+    a.chain.nparts = grid;
+    a.x_wait = 1;
+    if (!h->xchg.on) a.chain.x = h->meet.self_x;            // unsharded: the private one-rank mailbox
+    a.st_in = h->thermo.d_state; a.st_out = h->thermo.d_state;       // advanced in place by work-group 0 after everybody has read it
+    a.sync = h->meet.d_sync; a.rows = h->meet.d_rows;
+    if (h->topo.num_big && a.use_com) { tgnh_status rc = run_big_com(h, kind == 0 || kind == 2, s); if (rc) return rc; }
+    if (kind == 0 && h->cfg.wresident_per_cu > 0) {            // a whole deferred step over wave tiles (wstep_kernel)
+        if (h->cfg.wresident_grid == 0) {
+            const int need = (h->topo.num_wtiles + WBLOCK / 64 - 1) / (WBLOCK / 64);
+            h->cfg.wresident_grid = std::max(1, std::min(std::min(need, h->cfg.wresident_per_cu * h->cfg.num_cus / h->cfg.resident_share), GRID_CAP));
+        }
+        a.chain.nparts = h->cfg.wresident_grid;
+        h->run.ke_parts = h->cfg.wresident_grid;
+        { tgnh_status rc = check_launch(h, a, h->cfg.wresident_grid, WBLOCK, true, true); if (rc) return rc; }
+        Timed t(h, s, KID_STEP);
+        HIP_OK(launch_wstep(h->d.precision, h->cfg.gb, h->thermo.L.C > 1, a, h->cfg.wresident_grid, s));
+    } else {
+        h->run.ke_parts = grid;
+        { tgnh_status rc = check_launch(h, a, grid, TBLOCK, false, true); if (rc) return rc; }
+        Timed t(h, s, KID_STEP);
+        HIP_OK(launch_step(h->d.precision, h->cfg.gb, kind, a, grid, lds, s));
+    }
+    // the first pass walked the tiles in direction sweep_reverse, the second one back: the next launch starts here
+    h->owed.resident_settled();
+    return TGNH_OK;
+}
+
+// make scale[] hold the first thermostat half step for the current velocities (Ref :231, Cu :336)
+static tgnh_status first_half(tgnh_handle h, hipStream_t s) {
+    if (h->owed.first_half_done) return TGNH_OK;               // DEFER_SCALE: already folded into scale[]
+    if (h->owed.ke_carry) {
+        // TRUST_STATE_CHANGED, and nothing has written velocities since the last end half's rescale: every kinetic-energy bin
+        // of the stored velocities is s^2 times the bin that chain started from -- the ke_post it left (Cu :574 tracks exactly
+        // that product) -- so this half's KE pass (Cu :474-488) and its row sum are not run: the chain starts from ke_post
+        h->owed.ke_carry = false;
+        if (h->topo.num_big && h->d.mode == TGNH_MODE_TGNH && h->d.use_com_temp_group) {
+            // (molecules longer than a tile: the KE pass that is not run would have left their centre-of-mass velocities in
+            // the table the rescale launch reads -- the end half's rescale has changed them since)
+            tgnh_status rc = run_big_com(h, false, s); if (rc) return rc;
+        }
+        if (h->cfg.inline_chain) {                            // ... inside the rescale launch that follows: this half step is ONE launch
+            h->owed.chain_pending = true; h->owed.chain_pending_twice = false; h->owed.sum_pending = false; h->owed.carry_pending = true;
+            return TGNH_OK;
+        }
+        ChainArgs a = chain_args(h);
+        a.do_sum = 0; a.do_chain = 1; a.ke_carry = 1;
+        Timed t(h, s, KID_CHAIN);
+        HIP_OK(launch_chain(a, s));
+        return TGNH_OK;
+    }
+    tgnh_status rc = run_tile(h, OP_KE, KID_KE, s); if (rc) return rc;
+    return run_chain(h, s, false);
+}
+
+// Every entry point that launches work or hands results back starts here: a failure the device reported earlier
+// (a mailbox exchange that timed out; in dualNH mode a Drude beyond twice the hard wall, Ref :311-312) is sticky --
+// the trajectory is no longer the integrator's, so nothing more is computed on it.
+tgnh_status entry(tgnh_handle h, bool need_bufs) {
+    if (!h) return fail(TGNH_ERR_ARG, "null handle");
+    h->owed.g_com_fresh = false;                                           // (the caller may have written velocities since the last entry point)
+    if (need_bufs) { tgnh_status rc = need_buffers(h); if (rc) return rc; }
+    if (!h->host_only) {
+        HIP_OK(hipSetDevice(h->device));
+        if (h->status.h_seen) note_status(h, *h->status.h_seen);     // the last periodic read-back, if it has landed
+    }
+    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);
+    return TGNH_OK;
+}
+
+// Every STATUS_POLL_EVERY steps the status word is copied to pinned host memory behind the step (no synchronisation;
+// looked at on a later entry): a caller that never asks for anything still learns of a failure within that many steps.
+static tgnh_status poll_status_async(tgnh_handle h, hipStream_t s) {
+    if (!h->status.h_seen || h->run.step_count % STATUS_POLL_EVERY != 0) return TGNH_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return TGNH_OK;
+    HIP_OK(hipMemcpyAsync(h->status.h_seen, h->status.d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    return TGNH_OK;
+}
+
+// Consecutive streaming launches sweep the slots in alternating directions (a launch starts where the last one ended), and
+// the direction decides the order in which a wavefront adds its tiles' kinetic energies, i.e. the last bits of the sums.  A
+// time step holds an odd number of sweeps in every pass structure, so in an undisturbed run step k starts in direction k & 1;
+// that is made the rule: whatever was launched between two steps (queries, a flush), a step starts in the direction of
+// its number.  The trajectory's bits are then a function of the state and the step counter alone -- a handle restored from a
+// checkpoint (tgnh_set_time carries the counter) continues bit for bit, ranks of a sharded run sweep alike.
+static void start_of_step(tgnh_handle h) {
+    if (h->cfg.alternate_sweeps) h->run.sweep_reverse = (int)(h->run.step_count & 1);
+}
+
+extern "C" tgnh_status tgnh_step_begin(tgnh_handle h, void* stream) {
+    tgnh_status rc = entry(h, true); if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    start_of_step(h);
+    if (h->owed.end_pending) {
+        if (resident_now(h)) return run_resident(h, s, 0);           // the last step's end half and this begin half: one launch
+        rc = settle_end(h, s); if (rc) return rc;
+    }
+    if (!(h->d.flags & TGNH_FLAG_DEFER_SCALE) && resident_now(h) && !h->owed.ke_carry)
+        return run_resident(h, s, 1);                                // reference pass structure: KE, chain, rescale+kick+drift in one launch
+    rc = first_half(h, s); if (rc) return rc;                       // (kinetic energies carried over: no first pass, no meeting -- the tile launch with its in-kernel chain)
+    // Cu :351-376 fused; with a half kick still pending from the last step_end (DEFER_SCALE) that kick comes first
+    rc = run_tile(h, (h->owed.kick_pending ? OP_PREKICK : 0) | OP_SCALE | OP_KICK | OP_DRIFT, KID_SKD, s); if (rc) return rc;
+    h->owed.velocities_current(); h->owed.first_half_done = false;
+    return TGNH_OK;
+}
+
+static tgnh_status second_half(tgnh_handle h, hipStream_t s, int kick_ops) {
+    tgnh_status rc;
+    const bool defer = (h->d.flags & TGNH_FLAG_DEFER_SCALE) != 0;
+    h->owed.ke_carry = false;                                   // (an end half without a begin half before it: its own KE pass runs in any case)
+    if (h->owed.scale_pending || h->owed.kick_pending || h->owed.end_pending) { rc = flush_impl(h, s); if (rc) return rc; }   // two end halves in a row
+    if (!defer && resident_now(h)) {
+        // reference pass structure: kick, KE, chain, rescale (Cu :384-402) in one launch; velocities are final when it ends
+        rc = run_resident(h, s, kick_ops ? 2 : 4); if (rc) return rc;
+        h->owed.ke_carry = h->cfg.carry_ok && !h->xchg.allreduce && !h->xchg.on;
+        h->run.time += h->d.step_size;
+        h->run.step_count += 1;
+        return poll_status_async(h, s);
+    }
+    if (kick_ops && resident_now(h)) {
+        // TGNH_FLAG_RESIDENT_STEP: nothing is launched here -- the next tgnh_step_begin runs this end half and its own
+        // begin half in one launch (step_kernel); anything that needs the state earlier settles it the classic way
+        h->owed.end_pending = true;
+        h->run.time += h->d.step_size;
+        h->run.step_count += 1;
+        return poll_status_async(h, s);
+    }
+    // DEFER_SCALE, fused path: the kicked velocities only feed the sums (Cu :384-388 + :474-488); the next step's first
+    // launch -- or tgnh_flush -- forms them again from the same force buffer and goes on from there.
+    // The reference's own structure, fused path (round 4): the same unstored kick+KE pass, and the rescale launch of THIS call forms
+    // the kicked velocities again before it rescales them (OP_PREKICK: the same expression on the same force buffer, the same
+    // bits) -- V r, F r | V r/w, F r = 144 B per slot where kick+KE with a store and a plain rescale move 152, and the read-only
+    // pass runs at 62 us where the storing one takes 87-92 (5 M slots).  velm holds the reference's end-of-step velocities when
+    // tgnh_step_end returns, as before.  (The split path's halves work on stored velocities around the constraint call-outs.)
+    const bool fold = !defer && kick_ops != 0 && !h->gather.generic;           // (the gather path stores its kick: K's own structure)
+    const int nostore = kick_ops && !h->gather.generic ? OP_NOSTORE : 0;
+    h->owed.end_folded = fold;
+    rc = run_tile(h, kick_ops | OP_KE | nostore, kick_ops ? KID_KICK_KE : KID_KE, s); if (rc) return rc;
+    if (defer) {
+        rc = run_chain(h, s, true); if (rc) return rc;
+        h->owed.end_half_deferred(nostore != 0);
+    } else {
+        rc = run_chain(h, s, false); if (rc) return rc;                            // Cu :394-395
+        rc = run_tile(h, (fold ? OP_PREKICK : 0) | OP_SCALE, KID_SCALE, s); if (rc) return rc;   // Cu :402 (and :384-388 again, see above)
+        // the velocities now stored have the bins ke_post; they stay that until somebody writes velocities (unsharded only: a
+        // rank that recomputes while its peers carry over would enter a collective alone)
+        h->owed.ke_carry = h->cfg.carry_ok && !h->xchg.allreduce && !h->xchg.on;
+    }
+    h->run.time += h->d.step_size;                                                     // Cu :405-406 ; Ref :413-414
+    h->run.step_count += 1;
+    return poll_status_async(h, s);
+}
+
+extern "C" tgnh_status tgnh_step_end(tgnh_handle h, void* stream) {
+    tgnh_status rc = entry(h, true); if (rc) return rc;
+    return second_half(h, (hipStream_t)stream, OP_KICK);
+}
+
+// The split entry points work on stored velocities: a deferred half kick is materialised first.
+tgnh_status settle_kick(tgnh_handle h, hipStream_t s) {
+    return (h->owed.kick_pending || h->owed.end_pending) ? flush_impl(h, s) : TGNH_OK;
+}
+
+// TGNH_FLAG_RESIDENT_STEP left the end half of the last step to the next tgnh_step_begin; somebody needs it now:
+// the classic launches (kick+KE without a velocity store, row sum [+ exchange], both chain halves pending)
+tgnh_status settle_end(tgnh_handle h, hipStream_t s) {
+    if (!h->owed.end_pending) return TGNH_OK;
+    h->owed.end_pending = false;
+    tgnh_status rc = run_tile(h, OP_KICK | OP_KE | OP_NOSTORE, KID_KICK_KE, s); if (rc) return rc;
+    rc = run_chain(h, s, true); if (rc) return rc;
+    h->owed.end_half_deferred(true);
+    return TGNH_OK;
+}
+
+extern "C" tgnh_status tgnh_step_begin_kick(tgnh_handle h, void* stream) {
+    tgnh_status rc = entry(h, true); if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = settle_kick(h, s); if (rc) return rc;
+    start_of_step(h);
+    if (!(h->d.flags & TGNH_FLAG_DEFER_SCALE) && resident_now(h) && !h->owed.ke_carry) return run_resident(h, s, 3);
+    rc = first_half(h, s); if (rc) return rc;
+    rc = run_tile(h, OP_SCALE | OP_KICK | OP_POSDELTA, KID_OTHER, s); if (rc) return rc;   // Cu :351-360
+    h->owed.scale_pending = false; h->owed.first_half_done = false;
+    return TGNH_OK;
+}
+extern "C" tgnh_status tgnh_step_begin_move(tgnh_handle h, void* stream) {
+    tgnh_status rc = entry(h, true); if (rc) return rc;
+    h->owed.ke_carry = false;
+    rc = settle_kick(h, (hipStream_t)stream); if (rc) return rc;
+    return run_tile(h, OP_MOVE, KID_OTHER, (hipStream_t)stream);                   // Cu :366-376
+}
+extern "C" tgnh_status tgnh_step_end_kick(tgnh_handle h, void* stream) {
+    tgnh_status rc = entry(h, true); if (rc) return rc;
+    h->owed.ke_carry = false;
+    rc = settle_kick(h, (hipStream_t)stream); if (rc) return rc;
+    return run_tile(h, OP_KICK, KID_OTHER, (hipStream_t)stream);                   // Cu :384-388
+}
+extern "C" tgnh_status tgnh_step_end_thermo(tgnh_handle h, void* stream) {
+    tgnh_status rc = entry(h, true); if (rc) return rc;
+    return second_half(h, (hipStream_t)stream, 0);                                 // Cu :394-406
+}
+extern "C" tgnh_status tgnh_half_kick(tgnh_handle h, void* stream) { return tgnh_step_end_kick(h, stream); }
+
+// velm <- the reference's end-of-step velocities: the pending half kick (same force buffer), then the end-of-step
+// factors; scale[] keeps only the pre-run first half of the coming step
+tgnh_status flush_impl(tgnh_handle h, hipStream_t s) {
+    tgnh_status rc = settle_end(h, s); if (rc) return rc;
+    if (!h->owed.scale_pending && !h->owed.kick_pending) return TGNH_OK;
+    rc = materialize_chain(h, s); if (rc) return rc;
+    if (h->owed.scale_pending) {
+        rc = run_tile(h, (h->owed.kick_pending ? OP_PREKICK : 0) | OP_SCALE, KID_SCALE, s, h->thermo.d_state + h->thermo.L.off_scale_a); if (rc) return rc;
+        HIP_OK(hipMemcpyAsync(h->thermo.d_state + h->thermo.L.off_scale, h->thermo.d_state + h->thermo.L.off_scale_b, sizeof(double) * h->thermo.L.NT,
+                              hipMemcpyDeviceToDevice, s));
+    } else {
+        rc = run_tile(h, OP_KICK, KID_OTHER, s); if (rc) return rc;
+    }
+    if (h->topo.num_big && h->d.mode == TGNH_MODE_TGNH && h->d.use_com_temp_group) {
+        rc = run_big_com(h, false, s); if (rc) return rc;             // the velocities just changed: refresh the COM table
+    }
+    h->owed.velocities_current();      // first_half_done stays
+    return TGNH_OK;
+}
+
+extern "C" tgnh_status tgnh_flush(tgnh_handle h, void* stream) {
+    CHECK_H(h);
+    if (!h->owed.scale_pending && !h->owed.kick_pending && !h->owed.end_pending) return TGNH_OK;
+    tgnh_status rc = entry(h, true); if (rc) return rc;
+    return flush_impl(h, (hipStream_t)stream);
+}
+
+extern "C" tgnh_status tgnh_note_replayed_steps(tgnh_handle h, int nsteps) {
+    CHECK_H(h);
+    if (nsteps < 0) return fail(TGNH_ERR_ARG, "negative step count");
+    h->run.time += h->d.step_size * nsteps;
+    h->run.step_count += nsteps;
+    return TGNH_OK;
+}
+
+// Restores the clock of a checkpointed run (the reference keeps time / stepCount in the platform data, Ref :413-414,
+// Cu :405-406, and OpenMM's checkpoints carry them).
+extern "C" tgnh_status tgnh_set_time(tgnh_handle h, double time, int64_t step_count) {
+    CHECK_H(h);
+    if (step_count < 0) return fail(TGNH_ERR_ARG, "negative step count");
+    h->run.time = time;
+    h->run.step_count = step_count;
+    return TGNH_OK;
+}
+
+extern "C" tgnh_status tgnh_get_pending_state(tgnh_handle h, uint32_t* bits) {
+    CHECK_H(h);
+    if (!bits) return fail(TGNH_ERR_ARG, "null out");
+    *bits = h->owed.bits() | (h->run.sweep_reverse ? (uint32_t)tgnh_context::Owed::BIT_SWEEP_REVERSE : 0u);
+    return TGNH_OK;
+}
+
+extern "C" tgnh_status tgnh_state_changed(tgnh_handle h) {
+    CHECK_H(h);
+    tgnh_status rc = deferred_guard(h, "tgnh_state_changed");
+    if (rc) return rc;
+    h->owed.ke_carry = false;              // TRUST_STATE_CHANGED: the next thermostat half step sums the kinetic energies again (Cu :474-488)
+    return TGNH_OK;
+}
