@@ -1,5 +1,5 @@
 // tgnh_chain_device.h -- device code of the Nose-Hoover chain (A5), shared by chain_kernel and by the tile
-// kernel's in-kernel chain.  Included by tgnh_kernels.hip only.
+// and wave-tile kernels' in-kernel chain (step_meet) and the gather path.  Included by .hip files only.
 //
 // TGNH: one lane per thermostat (Cu :558-650).  dualNH: one lane runs the reference's coupled, interleaved
 // vectors (Ref :467-504), including its indexing quirk when useDrudeNHChains is false.
@@ -7,6 +7,9 @@
 // the S-fold loop and written back once.
 #ifndef TGNH_CHAIN_DEVICE_H_
 #define TGNH_CHAIN_DEVICE_H_
+#include "tgnh_device_math.h"
+#include "tgnh_trace.h"
+#include "tgnh_xchg_device.h"
 
 namespace tgnh {
 #ifdef TGNH_TRACE
@@ -15,7 +18,6 @@ static __device__ __attribute__((unused)) double g_chain_dbg[4];   // largest ex
 
 // Contraction is left on: every a*b+c below may become one fma (<= 1 ulp per operation away from the separately
 // rounded reference arithmetic; the chain is smooth, the parity gate is 1e-6 and is met at 1e-12).
-#pragma clang fp contract(fast)
 
 // exp() for the chain.  The arguments are -dtc/8*etaDot and -dtc/2*etaDot: exactly 0 for the dummy link
 // (exp(-0) = 1 exactly, as libm returns) and tiny otherwise, so a short Taylor polynomial in explicit FMAs is
@@ -457,108 +459,6 @@ __device__ __forceinline__ Chain1Map chain1_map(const ChainLayout& L, const int 
     m.used = itg != L.c1_unused;
     m.guard = itg < L.c1_guard_below;                             // etaMass > 0 guard: TGNH's real thermostats (Cu :561 vs :605, Ref :471)
     return m;
-}
-
-// ---- mailbox exchange (protocol: XchgArgs in tgnh_internal.h) ----
-__device__ __forceinline__ size_t xchg_cell(const XchgArgs& x, const unsigned par, const int src, const int i, const int copy = 0) {
-    return (size_t)copy * XCHG_REPLICA_U64 + (((size_t)par * x.world + src) * XCHG_NT_PAD + i) * XCHG_CELL_U64;
-}
-__device__ __forceinline__ unsigned long long xchg_ld(const unsigned long long* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-// The mailbox thread tid of a sending work-group stores into: thread tid serves peer tid % world, so every thread needs ONE
-// mailbox pointer, which a caller with time to spare fetches ahead of the send (step_kernel: before it collects the rows).
-__device__ __forceinline__ unsigned long long* xchg_peer_of(const XchgArgs& x, const int tid) {
-    return x.world == 1 ? x.mine : x.peers[tid % x.world];
-}
-// Called by one work-group with `mine` = this rank's sum in thread tid < NT, handed over through s_val (LDS, NT doubles).
-// Contains __syncthreads().  seq_new != 0 (thread 0): the number of this exchange, when the caller has read the counter
-// already (step_kernel reads it at kernel entry: no load on the path between the last row and the send).
-// peer = xchg_peer_of(x, tid) when the caller has fetched it already.
-__device__ __forceinline__ void xchg_send(const XchgArgs& x, const int NT, const int tid, const int nthreads, double* s_val,
-                                          const double mine, const unsigned long long seq_new = 0ull,
-                                          unsigned long long* peer = nullptr) {
-    __shared__ unsigned long long s_seq;
-    if (!peer) peer = xchg_peer_of(x, tid);
-    if (tid == 0) { const unsigned long long s = seq_new ? seq_new : *x.seq + 1ull; *x.seq = s; s_seq = s; }
-    if (tid < NT) s_val[tid] = mine;
-    __syncthreads();
-    const unsigned long long seq = s_seq, tag = (seq & 0xffffffffull) << 32;
-    const int tpp = nthreads / x.world;                      // threads per peer
-    if (tid >= tpp * x.world) return;
-    // every copy of the peer's cells [parity][my rank][0 .. NT): copy-major, so copy 0 goes out first
-    unsigned long long* const base = peer + xchg_cell(x, (unsigned)(seq & 1ull), x.rank, 0, 0);
-    for (int q = tid / x.world; q < NT * XCHG_REPLICAS; q += tpp) {
-        const int copy = q / NT, i = q - copy * NT;
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(s_val[i]);
-        unsigned long long* cell = base + (size_t)copy * XCHG_REPLICA_U64 + (size_t)i * XCHG_CELL_U64;
-        __hip_atomic_store(cell, tag | (bits & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(cell + 1, tag | (bits >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-// Called by all 64 lanes of one wavefront, converged; s_val = LDS scratch of world*NT doubles owned by that wavefront.
-// Returns the all-rank sum of thermostat `lane` (lanes < NT).  seq_expected != 0: the exchange to wait for when this
-// rank's own send may not have happened yet (step_kernel: sender and waiters are work-groups of one launch).
-// SPREAD: the work-groups of the launch poll different copies of the cells (step_kernel, where all of them wait at the
-// same moment); otherwise copy 0.
-template <bool SPREAD = false>
-__device__ __forceinline__ double xchg_wait_sum(const XchgArgs& x, const int NT, const int lane, double* s_val,
-                                                const unsigned long long seq_expected = 0ull, bool* failed = nullptr) {
-    const int cells = x.world * NT;
-    const bool stamp = x.stat != nullptr && blockIdx.x == 0;            // work-group 0 keeps the rank's wait statistics
-    const unsigned long long t_in = stamp ? wall_clock64() : 0ull;
-    const unsigned long long* const box = x.mine + (SPREAD ? (size_t)(blockIdx.x % (unsigned)XCHG_REPLICAS) * XCHG_REPLICA_U64 : 0);
-    // first batch: counter, latch and both parities of this lane's first cell, all in flight together
-    const unsigned long long seq_raw = seq_expected ? seq_expected : __hip_atomic_load(x.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned dead = __hip_atomic_load(x.dead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned long long a0 = 0, a1 = 0, b0 = 0, b1 = 0;
-    if (lane < cells) {
-        const int r = lane / NT, i = lane - r * NT;
-        const unsigned long long* c0 = box + xchg_cell(x, 0u, r, i);
-        const unsigned long long* c1 = box + xchg_cell(x, 1u, r, i);
-        a0 = xchg_ld(c0); a1 = xchg_ld(c0 + 1); b0 = xchg_ld(c1); b1 = xchg_ld(c1 + 1);
-    }
-    const unsigned par = (unsigned)(seq_raw & 1ull);
-    const unsigned long long tag = seq_raw & 0xffffffffull;
-    bool timed_out = false;
-    for (int k = lane; k < cells; k += 64) {
-        const int r = k / NT, i = k - r * NT;
-        const unsigned long long* c = box + xchg_cell(x, par, r, i);
-        unsigned long long w0, w1;
-        if (k == lane) { w0 = par ? b0 : a0; w1 = par ? b1 : a1; }
-        else { w0 = xchg_ld(c); w1 = xchg_ld(c + 1); }
-        unsigned n = 0;
-        while (((w0 >> 32) != tag || (w1 >> 32) != tag) && dead == 0u && !timed_out) {
-            if (++n > XCHG_SPIN_LIMIT) { timed_out = true; break; }
-            // the latch may be set while this wavefront is already polling (step_kernel's work-group 0 giving up on a row, another
-            // wavefront's time-out): looked at again every 64 polls, so that a failure ends every wait within microseconds
-            if ((n & 63u) == 0u) dead = __hip_atomic_load(x.dead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __builtin_amdgcn_s_sleep(4);
-            w0 = xchg_ld(c); w1 = xchg_ld(c + 1);
-        }
-        s_val[k] = __longlong_as_double((long long)((w1 << 32) | (w0 & 0xffffffffull)));
-    }
-    if (timed_out) {
-        atomicOr(x.status, 4u);
-        __hip_atomic_store(x.dead, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (failed) *failed = __any(timed_out || dead != 0u);
-    if (stamp) {                                                        // from "my sums are out" to "everybody's are here"
-        __builtin_amdgcn_s_waitcnt(0);
-        const unsigned long long dt = wall_clock64() - t_in;
-        if (lane == 0) {                                                // (one writer per launch: plain read-modify-write)
-            x.stat[0] += dt;
-            if (dt > x.stat[1]) x.stat[1] = dt;
-            x.stat[2] += 1ull;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    double s = 0.0;
-    if (lane < NT)
-        for (int r = 0; r < x.world; r++) s += s_val[r * NT + lane];       // rank order, on every rank
-    return s;
 }
 
 // Fixed-order sum of a FEW partial rows by one wavefront (every work-group computes the same bits).  The rows are
@@ -1217,8 +1117,6 @@ __device__ __forceinline__ void chainN_run(const ChainArgs& a, const double* st_
         }
     }
 }
-
-#pragma clang fp contract(fast)
 
 }  // namespace tgnh
 #endif

@@ -1,7 +1,7 @@
 // tgnh_gather.hip -- the step by GLOBAL INDEX: the slow path for topologies the tiled kernels cannot hold.
 //
-// tgnh_kernels.hip cuts the slot range into tiles inside which a Drude partner and the molecular centre of mass are on-chip
-// look-ups, and keeps the kinetic-energy bins of <= 32 temperature groups in registers / per-wavefront LDS rows.  The reference
+// tgnh_tile_kernels.h and tgnh_wave_kernels.h cut the slot range into tiles inside which a Drude partner and the molecular centre of mass are on-chip
+// look-ups, and keep the kinetic-energy bins of <= 32 temperature groups in registers / per-wavefront LDS rows.  The reference
 // has none of those limits: its kernels gather by arbitrary index (K :171-186 pairParticles, :123 particleResId) and size their
 // bins by G + 2 (K :138-200, Cu :157).  So whatever tgnh_create cannot tile -- a Drude particle more than a tile away from its
 // parent, pairs overlapping so densely in a long molecule that no cut between two pairs lies within a tile's reach, more than 32
@@ -23,7 +23,8 @@
 //
 // Sums: fp64, no atomics, fixed order (per-wavefront bins filled in an order that depends on the data only, then wavefronts and
 // work-groups in index order): reproducible bit for bit, like the tiled path's.
-#include "tgnh_tile_device.h"
+#include "tgnh_chain_device.h"
+#include "tgnh_slot_device.h"
 
 namespace tgnh {
 
@@ -253,15 +254,7 @@ __global__ __launch_bounds__(BLOCK) void gather_update_kernel(const GatherArgs a
             const bool mv = p.v.w != 0;
             pdelta[i] = mk4(mv ? dt * p.v.x : (mixed)0, mv ? dt * p.v.y : (mixed)0, mv ? dt * p.v.z : (mixed)0, (mixed)0);
         }
-        if (pos) {
-            if (PREC == TGNH_PREC_MIXED) {                       // K :457-458
-                const float hx = (float)p.px, hy = (float)p.py, hz = (float)p.pz;
-                posq[i] = mk4((real)hx, (real)hy, (real)hz, p.pq);
-                pcorr[i] = make_float4((float)(p.px - hx), (float)(p.py - hy), (float)(p.pz - hz), 0.0f);
-            } else {
-                posq[i] = mk4((real)p.px, (real)p.py, (real)p.pz, p.pq);
-            }
-        }
+        if (pos) store_position<PREC>(posq, pcorr, i, p.px, p.py, p.pz, p.pq);
     };
 
     for (long long it = (long long)blockIdx.x * BLOCK + threadIdx.x; it < a.n; it += (long long)gridDim.x * BLOCK) {
@@ -289,7 +282,7 @@ __global__ __launch_bounds__(BLOCK) void gather_update_kernel(const GatherArgs a
             if (do_prekick) { kick(p1); kick(p2); }
             const mixed mass1 = rcp_(p1.v.w), mass2 = rcp_(p2.v.w);      // (massless pair members: refused at create)
             const mixed invTot = rcp_(mass1 + mass2);
-            if (do_scale) {                                      // K :270-300
+            if (do_scale) {                                      // K :270-300, K's two-member form (the tiles write a member from its own point of view: another expression tree)
                 const mixed m1f = invTot * mass1, m2f = invTot * mass2;
                 const mixed r1x = p1.v.x - p1.cx, r1y = p1.v.y - p1.cy, r1z = p1.v.z - p1.cz;
                 const mixed r2x = p2.v.x - p2.cx, r2y = p2.v.y - p2.cy, r2z = p2.v.z - p2.cz;
@@ -391,17 +384,9 @@ static int gather_grid(const long long items, const int cap) {
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-#define GATHER_BY_PREC(kernel, grid, lds, s, ...)                                                                          \
-    switch (precision) {                                                                                                   \
-        case TGNH_PREC_SINGLE: TGNH_LAUNCH((kernel<TGNH_PREC_SINGLE>), dim3(grid), dim3(BLOCK), lds, s, __VA_ARGS__); break; \
-        case TGNH_PREC_MIXED: TGNH_LAUNCH((kernel<TGNH_PREC_MIXED>), dim3(grid), dim3(BLOCK), lds, s, __VA_ARGS__); break;   \
-        case TGNH_PREC_DOUBLE: TGNH_LAUNCH((kernel<TGNH_PREC_DOUBLE>), dim3(grid), dim3(BLOCK), lds, s, __VA_ARGS__); break; \
-        default: return hipErrorInvalidValue;                                                                              \
-    }
-
 hipError_t launch_gather_com(int precision, const GatherArgs& a, hipStream_t s) {
     const int grid = gather_grid((long long)a.n_res * a.com_lanes, 8192);
-    GATHER_BY_PREC(gather_com_kernel, grid, 0, s, a)
+    TGNH_LAUNCH_PREC(gather_com_kernel, precision, dim3(grid), dim3(BLOCK), 0, s, a);
     return hipGetLastError();
 }
 int gather_ke_grid(const GatherArgs& a) {
@@ -410,7 +395,7 @@ int gather_ke_grid(const GatherArgs& a) {
 hipError_t launch_gather_ke(int precision, const GatherArgs& a, int grid, hipStream_t s) {
     const size_t lds = sizeof(double) * (BLOCK / 64) * (size_t)a.NT;
     if (lds > 64 * 1024) return hipErrorInvalidValue;                          // (tgnh_create refuses more groups than fit)
-    GATHER_BY_PREC(gather_ke_kernel, grid, lds, s, a)
+    TGNH_LAUNCH_PREC(gather_ke_kernel, precision, dim3(grid), dim3(BLOCK), lds, s, a);
     return hipGetLastError();
 }
 hipError_t launch_gather_rowsum(const double* partials, int nrows, int NT, double* ke_red, hipStream_t s) {
@@ -423,12 +408,12 @@ hipError_t launch_gather_chain(const ChainArgs& a, double* scratch, hipStream_t 
 }
 hipError_t launch_gather_update(int precision, const GatherArgs& a, hipStream_t s) {
     const int grid = gather_grid(a.n, 8192);
-    GATHER_BY_PREC(gather_update_kernel, grid, 0, s, a)
+    TGNH_LAUNCH_PREC(gather_update_kernel, precision, dim3(grid), dim3(BLOCK), 0, s, a);
     return hipGetLastError();
 }
 hipError_t launch_gather_force(int precision, const GatherArgs& a, const void* x0, long long* force, double k_drude, double k_tether, hipStream_t s) {
     const int grid = gather_grid(a.n, 8192);
-    GATHER_BY_PREC(gather_force_kernel, grid, 0, s, a, x0, force, k_drude, k_tether)
+    TGNH_LAUNCH_PREC(gather_force_kernel, precision, dim3(grid), dim3(BLOCK), 0, s, a, x0, force, k_drude, k_tether);
     return hipGetLastError();
 }
 

@@ -1,4 +1,5 @@
-// tgnh_harness.hip -- harness call-outs of the constrained path: SHAKE on posDelta, the velocity stage,
+// tgnh_harness.hip -- the harness's kernels: its force (bench / test workload: force_kernel, force_packed_kernel,
+// force_lattice_kernel), and the call-outs of the constrained path: SHAKE on posDelta, the velocity stage,
 // three-particle-average virtual sites.  NOT part of the reference's plugin: it delegates all three to OpenMM
 // (Cu :363 applyConstraints, :391 applyVelocityConstraints, :377 computeVirtualSites; Ref :268, :373).
 // They exist so that the split step path (tgnh_step_begin_kick / _move / _end_kick / _end_thermo) can be
@@ -9,14 +10,220 @@
 // (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); distance 0 = no constraint.  One lane per cluster, SHAKE sweeps in that
 // order until every |d^2 - r^2| <= 2 tol d^2 -- everything in registers, static indices.
 #include "tgnh_context.h"
+#include "tgnh_device_math.h"
 
 namespace tgnh {
 
-template <int PREC> struct HPrec;
-template <> struct HPrec<TGNH_PREC_SINGLE> { typedef float real; typedef float mixed; typedef float4 real4; typedef float4 mixed4; };
-template <> struct HPrec<TGNH_PREC_MIXED>  { typedef float real; typedef double mixed; typedef float4 real4; typedef double4 mixed4; };
-template <> struct HPrec<TGNH_PREC_DOUBLE> { typedef double real; typedef double mixed; typedef double4 real4; typedef double4 mixed4; };
+// ---------------------------------------------------------------------------
+// harness force (bench/test workload; not part of the reference)
+// ---------------------------------------------------------------------------
+template <int PREC>
+__global__ __launch_bounds__(BLOCK) void force_kernel(const ForceArgs a) {
+    typedef typename Prec<PREC>::real4 real4;
+    typedef typename Prec<PREC>::mixed mixed;
+    const real4* __restrict__ posq = reinterpret_cast<const real4*>(a.posq);
+    const float4* __restrict__ pcorr = reinterpret_cast<const float4*>(a.posq_corr);
+    const real4* __restrict__ x0 = reinterpret_cast<const real4*>(a.x0);      // (site x,y,z ; w = 1 if tethered)
+    const mixed kd = (mixed)a.k_drude, kt = (mixed)a.k_tether;
+    const int lane = threadIdx.x & 63;
+    // uniform trip count per wavefront so the shuffles below see all 64 lanes
+    const int nround = (a.n + gridDim.x * BLOCK - 1) / (gridDim.x * BLOCK);
+    for (int rr = 0; rr < nround; rr++) {
+        // optionally last chunk first (lane order inside a chunk unchanged): start where the previous launch ended
+        const int r = a.reverse ? nround - 1 - rr : rr;
+        const int blk = a.reverse ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
+        const int i = (r * gridDim.x + blk) * BLOCK + threadIdx.x;
+        const bool in = i < a.n;
+        uint32_t m = 0;
+        mixed x = 0, y = 0, z = 0;
+        if (in) {
+            m = a.meta[i];
+            const real4 p = posq[i];
+            x = p.x; y = p.y; z = p.z;
+            if (PREC == TGNH_PREC_MIXED) { const float4 c = pcorr[i]; x += (mixed)c.x; y += (mixed)c.y; z += (mixed)c.z; }
+        }
+        const uint32_t role = m & 3u;
+        const int off = (int)((m >> 10) & 2047u) - 1024;
+        // partner position: from the partner's lane when it is in this wavefront (the usual case: partners are
+        // neighbours), else one more global read
+        const int pl = lane + off;
+        const int src = (pl >= 0 && pl < 64) ? pl : lane;
+        mixed ox = __shfl(x, src, 64), oy = __shfl(y, src, 64), oz = __shfl(z, src, 64);
+        mixed fx = 0, fy = 0, fz = 0;
+        if (in) {
+            if (role != ROLE_DRUDE) {                                   // tether of massive non-Drude sites
+                const real4 s = x0[i];
+                if (s.w != 0) { fx = -kt * (x - (mixed)s.x); fy = -kt * (y - (mixed)s.y); fz = -kt * (z - (mixed)s.z); }
+            }
+            if (role != ROLE_NORMAL) {                                  // Drude spring
+                if (src != pl) {
+                    const int j = i + off;
+                    const real4 q = posq[j];
+                    ox = q.x; oy = q.y; oz = q.z;
+                    if (PREC == TGNH_PREC_MIXED) { const float4 c = pcorr[j]; ox += (mixed)c.x; oy += (mixed)c.y; oz += (mixed)c.z; }
+                }
+                // separation Drude - parent; force -k sep on the Drude, +k sep on the parent
+                const bool is_d = role == ROLE_DRUDE;
+                const mixed sgn = is_d ? (mixed)-1 : (mixed)1;
+                const mixed sx = is_d ? x - ox : ox - x, sy = is_d ? y - oy : oy - y, sz = is_d ? z - oz : oz - z;
+                fx += sgn * kd * sx; fy += sgn * kd * sy; fz += sgn * kd * sz;
+            }
+            a.force[i] = (long long)(fx * (mixed)4294967296.0);
+            a.force[i + a.padded] = (long long)(fy * (mixed)4294967296.0);
+            a.force[i + 2 * a.padded] = (long long)(fz * (mixed)4294967296.0);
+        }
+    }
+}
 
+// The same forces from the packed sites (ForceArgs::sflag): every load of a slot is issued before the first is used, the
+// site comes from the compact array (its index: the chunk's base + the tethered lanes before this one), the meta word is
+// read only by a slot whose partner is more than 15 slots away.
+template <int PREC>
+__global__ __launch_bounds__(BLOCK) void force_packed_kernel(const ForceArgs a) {
+    typedef typename Prec<PREC>::real real;
+    typedef typename Prec<PREC>::real4 real4;
+    typedef typename Prec<PREC>::mixed mixed;
+    const real4* __restrict__ posq = reinterpret_cast<const real4*>(a.posq);
+    const float4* __restrict__ pcorr = reinterpret_cast<const float4*>(a.posq_corr);
+    const real* __restrict__ sites = reinterpret_cast<const real*>(a.sites);
+    const mixed kd = (mixed)a.k_drude, kt = (mixed)a.k_tether;
+    const int lane = threadIdx.x & 63;
+    const int nround = (a.n + gridDim.x * BLOCK - 1) / (gridDim.x * BLOCK);
+    for (int rr = 0; rr < nround; rr++) {
+        const int r = a.reverse ? nround - 1 - rr : rr;
+        const int blk = a.reverse ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
+        const int i = (r * gridDim.x + blk) * BLOCK + threadIdx.x;           // (a wavefront covers one aligned 64-slot chunk)
+        const bool in = i < a.n;
+        uint32_t b = 0;
+        real4 p = {}; float4 c = {};
+        if (in) {
+            b = a.sflag[i];
+            p = posq[i];
+            if (PREC == TGNH_PREC_MIXED) c = pcorr[i];
+        }
+        const bool tethered = (b & 4u) != 0;
+        const unsigned long long before = __ballot(tethered) & ((1ull << lane) - 1ull);
+        real s0 = 0, s1 = 0, s2 = 0;
+        if (tethered) {
+            const real* rec = sites + 3 * (size_t)(a.sbase[i >> 6] + (uint32_t)__popcll(before));
+            s0 = rec[0]; s1 = rec[1]; s2 = rec[2];
+        }
+        mixed x = p.x, y = p.y, z = p.z;
+        if (PREC == TGNH_PREC_MIXED) { x += (mixed)c.x; y += (mixed)c.y; z += (mixed)c.z; }
+        const uint32_t role = b & 3u;
+        int off = (int)(b >> 3) - 16;
+        if (in && (b >> 3) == 0) off = (int)((a.meta[i] >> 10) & 2047u) - 1024;
+        const int pl = lane + off;
+        const int src = (pl >= 0 && pl < 64) ? pl : lane;
+        mixed ox = __shfl(x, src, 64), oy = __shfl(y, src, 64), oz = __shfl(z, src, 64);
+        mixed fx = 0, fy = 0, fz = 0;
+        if (in) {
+            if (tethered) { fx = -kt * (x - (mixed)s0); fy = -kt * (y - (mixed)s1); fz = -kt * (z - (mixed)s2); }
+            if (role != ROLE_NORMAL) {
+                if (src != pl) {
+                    const int j = i + off;
+                    const real4 q = posq[j];
+                    ox = q.x; oy = q.y; oz = q.z;
+                    if (PREC == TGNH_PREC_MIXED) { const float4 cq = pcorr[j]; ox += (mixed)cq.x; oy += (mixed)cq.y; oz += (mixed)cq.z; }
+                }
+                const bool is_d = role == ROLE_DRUDE;
+                const mixed sgn = is_d ? (mixed)-1 : (mixed)1;
+                const mixed sx = is_d ? x - ox : ox - x, sy = is_d ? y - oy : oy - y, sz = is_d ? z - oz : oz - z;
+                fx += sgn * kd * sx; fy += sgn * kd * sy; fz += sgn * kd * sz;
+            }
+            a.force[i] = (long long)(fx * (mixed)4294967296.0);
+            a.force[i + a.padded] = (long long)(fy * (mixed)4294967296.0);
+            a.force[i + 2 * a.padded] = (long long)(fz * (mixed)4294967296.0);
+        }
+    }
+}
+
+// ... and from LATTICE sites (ForceArgs::lat_*: one molecule repeated on a simple cubic lattice, checked slot by slot by
+// tgnh_harness_pack_sites): flag byte and site are functions of the slot index -- molecule m = i div k, slot i - m k of it, lattice
+// point (m div side^2, (m div side) mod side, m mod side) -- so the kernel reads positions and writes forces, nothing else: the
+// 56 B per slot (mixed) the call-out cannot do without.  The site is fl(fl64(index x spacing) + geom), two roundings and a
+// conversion, the bits numpy gave the packed sites (__dmul_rn / __dadd_rn: never contracted; the force arithmetic itself is the
+// packed kernel's, under the same contraction rules: the same forces bit for bit); x div d as floor((x + 1/2) / d): never within
+// rounding of an integer.
+template <int PREC>
+__global__ __launch_bounds__(BLOCK) void force_lattice_kernel(const ForceArgs a) {
+    typedef typename Prec<PREC>::real real;
+    typedef typename Prec<PREC>::real4 real4;
+    typedef typename Prec<PREC>::mixed mixed;
+    __shared__ double s_geom[64 * 3];
+    __shared__ unsigned char s_flag[64];
+    const real4* __restrict__ posq = reinterpret_cast<const real4*>(a.posq);
+    const float4* __restrict__ pcorr = reinterpret_cast<const float4*>(a.posq_corr);
+    if (threadIdx.x < 64) s_flag[threadIdx.x] = a.lat_tab[threadIdx.x];
+    if (threadIdx.x < 192) s_geom[threadIdx.x] = reinterpret_cast<const double*>(a.lat_tab + 64)[threadIdx.x];
+    __syncthreads();
+    const mixed kd = (mixed)a.k_drude, kt = (mixed)a.k_tether;
+    const int lane = threadIdx.x & 63;
+    const int nround = (a.n + gridDim.x * BLOCK - 1) / (gridDim.x * BLOCK);
+    for (int rr = 0; rr < nround; rr++) {
+        const int r = a.reverse ? nround - 1 - rr : rr;
+        const int blk = a.reverse ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
+        const int i = (r * gridDim.x + blk) * BLOCK + threadIdx.x;
+        const bool in = i < a.n;
+        real4 p = {}; float4 c = {};
+        if (in) {
+            p = posq[i];
+            if (PREC == TGNH_PREC_MIXED) c = pcorr[i];
+        }
+        const int mloc = (int)(((double)i + 0.5) * a.lat_inv_k), pos = in ? i - mloc * a.lat_k : 0;
+        const int mol = a.lat_mol0 + mloc;                               // this handle's molecules start at lat_mol0 of the box (shards)
+        const uint32_t b = in ? s_flag[pos] : 0u;
+        const bool tethered = (b & 4u) != 0;
+        real s0 = 0, s1 = 0, s2 = 0;
+        if (tethered) {
+            const int ix = (int)(((double)mol + 0.5) * a.lat_inv_side2), rem = mol - ix * a.lat_side * a.lat_side;
+            const int iy = (int)(((double)rem + 0.5) * a.lat_inv_side), iz = rem - iy * a.lat_side;
+            s0 = (real)__dadd_rn(__dmul_rn((double)ix, a.lat_spacing), s_geom[3 * pos]);
+            s1 = (real)__dadd_rn(__dmul_rn((double)iy, a.lat_spacing), s_geom[3 * pos + 1]);
+            s2 = (real)__dadd_rn(__dmul_rn((double)iz, a.lat_spacing), s_geom[3 * pos + 2]);
+        }
+        mixed x = p.x, y = p.y, z = p.z;
+        if (PREC == TGNH_PREC_MIXED) { x += (mixed)c.x; y += (mixed)c.y; z += (mixed)c.z; }
+        const uint32_t role = b & 3u;
+        const int off = (int)(b >> 3) - 16;
+        const int pl = lane + off;
+        const int src = (pl >= 0 && pl < 64) ? pl : lane;
+        mixed ox = __shfl(x, src, 64), oy = __shfl(y, src, 64), oz = __shfl(z, src, 64);
+        mixed fx = 0, fy = 0, fz = 0;
+        if (in) {
+            if (tethered) { fx = -kt * (x - (mixed)s0); fy = -kt * (y - (mixed)s1); fz = -kt * (z - (mixed)s2); }
+            if (role != ROLE_NORMAL) {
+                if (src != pl) {
+                    const int j = i + off;
+                    const real4 q = posq[j];
+                    ox = q.x; oy = q.y; oz = q.z;
+                    if (PREC == TGNH_PREC_MIXED) { const float4 cq = pcorr[j]; ox += (mixed)cq.x; oy += (mixed)cq.y; oz += (mixed)cq.z; }
+                }
+                const bool is_d = role == ROLE_DRUDE;
+                const mixed sgn = is_d ? (mixed)-1 : (mixed)1;
+                const mixed sx = is_d ? x - ox : ox - x, sy = is_d ? y - oy : oy - y, sz = is_d ? z - oz : oz - z;
+                fx += sgn * kd * sx; fy += sgn * kd * sy; fz += sgn * kd * sz;
+            }
+            a.force[i] = (long long)(fx * (mixed)4294967296.0);
+            a.force[i + a.padded] = (long long)(fy * (mixed)4294967296.0);
+            a.force[i + 2 * a.padded] = (long long)(fz * (mixed)4294967296.0);
+        }
+    }
+}
+
+hipError_t launch_force(int precision, const ForceArgs& a, hipStream_t s) {
+    int grid = (a.n + BLOCK - 1) / BLOCK;
+    if (grid > 4096) grid = 4096;
+    if (grid < 1) grid = 1;
+    if (a.lat_tab) TGNH_LAUNCH_PREC(force_lattice_kernel, precision, dim3(grid), dim3(BLOCK), 0, s, a);
+    else if (a.sflag) TGNH_LAUNCH_PREC(force_packed_kernel, precision, dim3(grid), dim3(BLOCK), 0, s, a);
+    else TGNH_LAUNCH_PREC(force_kernel, precision, dim3(grid), dim3(BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// call-outs of the constrained path
+// ---------------------------------------------------------------------------
 struct ClusterArgs {
     const int4* atoms;        // [n] slot indices, -1 = unused
     const double* dist;       // [n][6]
@@ -33,9 +240,9 @@ __device__ constexpr int PB[6] = {1, 2, 3, 2, 3, 3};
 
 template <int PREC, bool VELOCITY>
 __global__ __launch_bounds__(BLOCK) void shake_kernel(const ClusterArgs a) {
-    typedef typename HPrec<PREC>::real4 real4;
-    typedef typename HPrec<PREC>::mixed mixed;
-    typedef typename HPrec<PREC>::mixed4 mixed4;
+    typedef typename Prec<PREC>::real4 real4;
+    typedef typename Prec<PREC>::mixed mixed;
+    typedef typename Prec<PREC>::mixed4 mixed4;
     const real4* __restrict__ posq = reinterpret_cast<const real4*>(a.posq);
     const float4* __restrict__ pcorr = reinterpret_cast<const float4*>(a.posq_corr);
     mixed4* __restrict__ velm = reinterpret_cast<mixed4*>(a.velm);
@@ -120,9 +327,9 @@ struct SiteArgs {
 
 template <int PREC>
 __global__ __launch_bounds__(BLOCK) void site_kernel(const SiteArgs a) {
-    typedef typename HPrec<PREC>::real real;
-    typedef typename HPrec<PREC>::real4 real4;
-    typedef typename HPrec<PREC>::mixed mixed;
+    typedef typename Prec<PREC>::real real;
+    typedef typename Prec<PREC>::real4 real4;
+    typedef typename Prec<PREC>::mixed mixed;
     real4* __restrict__ posq = reinterpret_cast<real4*>(a.posq);
     float4* __restrict__ pcorr = reinterpret_cast<float4*>(a.posq_corr);
     for (int k = blockIdx.x * BLOCK + threadIdx.x; k < a.n; k += gridDim.x * BLOCK) {
@@ -154,29 +361,20 @@ static int grid_of(int n) { int g = (n + BLOCK - 1) / BLOCK; return g < 1 ? 1 : 
 template <bool VEL>
 static hipError_t launch_shake(int precision, const ClusterArgs& a, hipStream_t s) {
     const int g = grid_of(a.n);
-    switch (precision) {
-        case TGNH_PREC_SINGLE: TGNH_LAUNCH((shake_kernel<TGNH_PREC_SINGLE, VEL>), dim3(g), dim3(BLOCK), 0, s, a); break;
-        case TGNH_PREC_MIXED: TGNH_LAUNCH((shake_kernel<TGNH_PREC_MIXED, VEL>), dim3(g), dim3(BLOCK), 0, s, a); break;
-        case TGNH_PREC_DOUBLE: TGNH_LAUNCH((shake_kernel<TGNH_PREC_DOUBLE, VEL>), dim3(g), dim3(BLOCK), 0, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
+    auto fn = with_precision(precision, [](auto P) { return &shake_kernel<decltype(P)::value, VEL>; });
+    if (!fn) return hipErrorInvalidValue;
+    TGNH_LAUNCH(fn, dim3(g), dim3(BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
 static hipError_t launch_sites(int precision, const SiteArgs& a, hipStream_t s) {
     const int g = grid_of(a.n);
-    switch (precision) {
-        case TGNH_PREC_SINGLE: TGNH_LAUNCH((site_kernel<TGNH_PREC_SINGLE>), dim3(g), dim3(BLOCK), 0, s, a); break;
-        case TGNH_PREC_MIXED: TGNH_LAUNCH((site_kernel<TGNH_PREC_MIXED>), dim3(g), dim3(BLOCK), 0, s, a); break;
-        case TGNH_PREC_DOUBLE: TGNH_LAUNCH((site_kernel<TGNH_PREC_DOUBLE>), dim3(g), dim3(BLOCK), 0, s, a); break;
-        default: return hipErrorInvalidValue;
-    }
+    TGNH_LAUNCH_PREC(site_kernel, precision, dim3(g), dim3(BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
-}  // namespace tgnh
 
-namespace tgnh {
+
 // ---------------------------------------------------------------------------
 // The force field and the CMMotionRemover of the reference's testWater (TestReferenceDrudeTGNHIntegrator.cpp:111-166), as
 // harness call-outs: what that test asks OpenMM for (reaction-field NonbondedForce, cutoff 1 nm, + DrudeForce + the M site's
@@ -191,6 +389,7 @@ struct WaterArgs {
     double box, cutoff;
 };
 
+// (not wave_sum: its additions run in another order -- other bits in the forces the water tests compare -- and other ISA)
 __device__ __forceinline__ double h_wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -199,7 +398,7 @@ __device__ __forceinline__ double h_wave_sum(double v) {
 
 template <int PREC>
 __global__ __launch_bounds__(BLOCK) void water_force_kernel(const WaterArgs a) {
-    typedef typename HPrec<PREC>::real4 real4;
+    typedef typename Prec<PREC>::real4 real4;
     const real4* __restrict__ posq = reinterpret_cast<const real4*>(a.posq);
     const float4* __restrict__ pcorr = reinterpret_cast<const float4*>(a.posq_corr);
     __shared__ double sred[BLOCK / 64][15];
@@ -267,8 +466,8 @@ __global__ __launch_bounds__(BLOCK) void water_force_kernel(const WaterArgs a) {
 // OpenMM's CMMotionRemover (frequency 1): subtract the centre-of-mass velocity from every massive particle.  One work-group.
 template <int PREC>
 __global__ __launch_bounds__(BLOCK) void cmm_kernel(void* velm_, int n) {
-    typedef typename HPrec<PREC>::mixed mixed;
-    typedef typename HPrec<PREC>::mixed4 mixed4;
+    typedef typename Prec<PREC>::mixed mixed;
+    typedef typename Prec<PREC>::mixed4 mixed4;
     mixed4* __restrict__ velm = reinterpret_cast<mixed4*>(velm_);
     __shared__ double sred[BLOCK / 64][4];
     __shared__ double vcm[3];
@@ -402,11 +601,9 @@ extern "C" tgnh_status tgnh_harness_water_force(tgnh_handle h, double box, doubl
     a.posq = h->bound.posq; a.posq_corr = h->bound.posq_corr; a.force = reinterpret_cast<long long*>(force_out);
     a.n_mol = h->d.num_particles / 5; a.padded = h->d.padded_num_particles; a.box = box; a.cutoff = cutoff;
     hipStream_t s = (hipStream_t)stream;
-    switch (h->d.precision) {
-        case TGNH_PREC_SINGLE: TGNH_LAUNCH((water_force_kernel<TGNH_PREC_SINGLE>), dim3(a.n_mol), dim3(BLOCK), 0, s, a); break;
-        case TGNH_PREC_MIXED: TGNH_LAUNCH((water_force_kernel<TGNH_PREC_MIXED>), dim3(a.n_mol), dim3(BLOCK), 0, s, a); break;
-        default: TGNH_LAUNCH((water_force_kernel<TGNH_PREC_DOUBLE>), dim3(a.n_mol), dim3(BLOCK), 0, s, a); break;
-    }
+    auto fn = with_precision(h->d.precision, [](auto P) { return &water_force_kernel<decltype(P)::value>; });
+    if (!fn) H_FAIL(TGNH_ERR_ARG, "unknown precision");
+    TGNH_LAUNCH(fn, dim3(a.n_mol), dim3(BLOCK), 0, s, a);
     H_HIP(hipGetLastError());
     return TGNH_OK;
 }
@@ -416,11 +613,9 @@ extern "C" tgnh_status tgnh_harness_remove_cm_motion(tgnh_handle h, void* stream
     h->owed.ke_carry = false;                 // (OpenMM's CMMotionRemover does not tell the integrator: the glue does not set TRUST_STATE_CHANGED beside one)
     H_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    switch (h->d.precision) {
-        case TGNH_PREC_SINGLE: TGNH_LAUNCH((cmm_kernel<TGNH_PREC_SINGLE>), dim3(1), dim3(BLOCK), 0, s, h->bound.velm, h->d.num_particles); break;
-        case TGNH_PREC_MIXED: TGNH_LAUNCH((cmm_kernel<TGNH_PREC_MIXED>), dim3(1), dim3(BLOCK), 0, s, h->bound.velm, h->d.num_particles); break;
-        default: TGNH_LAUNCH((cmm_kernel<TGNH_PREC_DOUBLE>), dim3(1), dim3(BLOCK), 0, s, h->bound.velm, h->d.num_particles); break;
-    }
+    auto fn = with_precision(h->d.precision, [](auto P) { return &cmm_kernel<decltype(P)::value>; });
+    if (!fn) H_FAIL(TGNH_ERR_ARG, "unknown precision");
+    TGNH_LAUNCH(fn, dim3(1), dim3(BLOCK), 0, s, h->bound.velm, h->d.num_particles);
     H_HIP(hipGetLastError());
     return TGNH_OK;
 }

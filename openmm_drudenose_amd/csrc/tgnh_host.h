@@ -1,6 +1,6 @@
 // tgnh_host.h -- what the host units behind the C ABI (include/drude_tgnh.h) share: tgnh_topology.cpp, tgnh_lifecycle.cpp,
 // tgnh_exchange.cpp, tgnh_step.cpp, tgnh_queries.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
-// live in tgnh_kernels.hip, tgnh_gather.hip and tgnh_harness.hip.
+// live in tgnh_kernels.hip (tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h), tgnh_gather.hip and tgnh_harness.hip.
 //
 // Reference semantics followed (scychon/openmm_drudeNose):
 //   Ref = platforms/reference/src/ReferenceDrudeTGNHKernels.cpp

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/drude_tgnh.h"
 
@@ -285,11 +286,36 @@ struct GatherArgs {
 // abandoned) is read off first.
 #define TGNH_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 
-// launchers (tgnh_kernels.hip)
+// The run-time precision as a template argument: f(std::integral_constant<int, PREC>{}); an unknown precision gives f's result type
+// value-initialised (nullptr where f picks a kernel).
+template <typename F>
+auto with_precision(const int precision, F&& f) -> decltype(f(std::integral_constant<int, TGNH_PREC_SINGLE>{})) {
+    switch (precision) {
+        case TGNH_PREC_SINGLE: return f(std::integral_constant<int, TGNH_PREC_SINGLE>{});
+        case TGNH_PREC_MIXED: return f(std::integral_constant<int, TGNH_PREC_MIXED>{});
+        case TGNH_PREC_DOUBLE: return f(std::integral_constant<int, TGNH_PREC_DOUBLE>{});
+        default: return {};
+    }
+}
+// ... and a launcher's usual use of it: kernel<PREC> with these arguments, hipErrorInvalidValue for an unknown precision
+#define TGNH_LAUNCH_PREC(kernel, precision, grid, block, lds, s, ...) do {                                        \
+        auto fn_ = tgnh::with_precision(precision, [](auto P) { return &kernel<decltype(P)::value>; });           \
+        if (!fn_) return hipErrorInvalidValue;                                                                     \
+        TGNH_LAUNCH(fn_, grid, block, lds, s, __VA_ARGS__);                                                        \
+    } while (0)
+// work-groups of `threads` threads and `lds` bytes of dynamic LDS of kernel fn that fit a compute unit (0: no such kernel)
+template <typename FN> int blocks_per_cu(FN fn, const int threads, const size_t lds) {
+    int n = 0;
+    if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(fn), threads, lds) != hipSuccess) return 0;
+    return n;
+}
+
+typedef void (*tile_fn_t)(const TileArgs);       // a kernel over tiles, as the dispatch tables of tgnh_kernels.hip hand it out
+// launchers (tgnh_kernels.hip: tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h; launch_force: tgnh_harness.hip)
 hipError_t launch_tile(int precision, int ops, int gb, const TileArgs& a, int grid, size_t lds, hipStream_t s);
 int tile_blocks_per_cu(int precision, int ops, int gb, size_t lds, bool multi = false);   // occupancy of that instantiation (multi: its in-kernel chain has 2-4 links)
 // step_kernel; kind: 0 a whole deferred step, 1 / 2 the begin / end half of the reference's pass structure, 3 / 4 the same
-// around the constraint call-outs (tgnh_kernels.hip: STEP_*)
+// around the constraint call-outs (tgnh_tile_kernels.h: STEP_*)
 hipError_t launch_step(int precision, int gb, int kind, const TileArgs& a, int grid, size_t lds, hipStream_t s);
 int step_blocks_per_cu(int precision, int gb, int kind, size_t lds);
 int step_kind_ops2(int kind);       // operations of the kind's second pass (its LDS needs)

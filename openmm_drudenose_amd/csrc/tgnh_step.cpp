@@ -98,7 +98,7 @@ static int wave_grid_for(tgnh_handle h, int ops) {
 static tgnh_status commit_stage(tgnh_handle h, hipStream_t s);
 
 // words of the tagged-row area (TileArgs::rows) and what a launch of `grid` work-groups with NT thermostats writes there
-// (row_word in tgnh_kernels.hip: rows in blocks of 64, word-major inside a block, two words per thermostat)
+// (row_word in tgnh_xchg_device.h: rows in blocks of 64, word-major inside a block, two words per thermostat)
 static size_t tagged_words_allocated() { return (size_t)2 * GRID_CAP * CHAIN_INLINE_SUM_NT; }
 static size_t tagged_words_touched(int grid, int NT) {
     if (grid < 1) return 0;

@@ -1,93 +1,22 @@
-// tgnh_tile_device.h -- device code shared by the streaming kernels' translation units (tgnh_kernels.hip today):
-// precision traits, the 64-lane sums, the kinetic-energy bins and their work-group reduction, the tagged rows and the meeting
-// of the one-launch step kernels (step_meet), and the per-tile work of the wave-tile step kernels (WaveStep).
-// Included by .hip files only.  Reference semantics: see tgnh_kernels.hip.
+// tgnh_tile_device.h -- device code of the 512-slot tiles (tile_kernel, step_kernel: tgnh_tile_kernels.h): the LDS carve and the
+// kinetic-energy bins of a work-group (TileEnv; the wave-tile step kernel keeps its bins in the same shape) with their work-group
+// reduction, a tile's global loads and the work on one tile (tile_body).  Included by .hip files only.
+// Reference semantics followed (scychon/openmm_drudeNose):
+//   K  = platforms/cuda/src/kernels/drudeTGNH.cu
+//   Cu = platforms/cuda/src/CudaDrudeTGNHKernels.cpp
+//   Ref= platforms/reference/src/ReferenceDrudeTGNHKernels.cpp
 #ifndef TGNH_TILE_DEVICE_H_
 #define TGNH_TILE_DEVICE_H_
-#include "tgnh_internal.h"
-
-namespace tgnh {
-__device__ __forceinline__ double wave_sum(double v);
-#ifdef TGNH_TRACE
-// Phase timestamps of the streaming kernels (tuning builds only: tools/trace_probe.py, tools/step_trace.py).  16 slots per
-// work-group, constant 100 MHz clock, written by thread 0.  One table per translation unit (static: the readers below see
-// their own unit's), read by tgnh_debug_read_trace (tgnh_kernels.hip).
-static __device__ unsigned long long g_trace[GRID_CAP * 16];
-#define TRACE(slot) do { if (threadIdx.x == 0 && (slot) < 16) g_trace[blockIdx.x * 16 + (slot)] = wall_clock64(); } while (0)
-#define TRACE_WAIT() __builtin_amdgcn_s_waitcnt(0)
-#define TGNH_TRACE_READERS(read_name, clear_name)                                                            \
-    extern "C" int read_name(unsigned long long* out) {                                                      \
-        return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(tgnh::g_trace), sizeof(unsigned long long) * tgnh::GRID_CAP * 16); \
-    }                                                                                                        \
-    extern "C" int clear_name() {                                                                            \
-        void* p = nullptr;                                                                                   \
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(tgnh::g_trace)) != hipSuccess) return 1;                      \
-        return (int)hipMemset(p, 0, sizeof(unsigned long long) * tgnh::GRID_CAP * 16);                       \
-    }
-// chain_kernel's own clocks (tools/micro/chain_inside.py): wall_clock64 and clock64 at entry, after the prologue and at exit
-static __device__ __attribute__((unused)) unsigned long long g_chain_trace[8];
-#define CHAIN_TRACE(slot) do { if (threadIdx.x == 0) { g_chain_trace[2 * (slot)] = wall_clock64(); g_chain_trace[2 * (slot) + 1] = clock64(); } } while (0)
-#else
-#define TRACE(slot) do {} while (0)
-#define TRACE_WAIT() do {} while (0)
-#define CHAIN_TRACE(slot) do {} while (0)
-#endif
-}
-#include "tgnh_chain_device.h"
+#include "tgnh_device_math.h"
+#include "tgnh_trace.h"
+#include "tgnh_xchg_device.h"
+#include "tgnh_slot_device.h"
 
 namespace tgnh {
 
-template <int PREC> struct Prec;
-template <> struct Prec<TGNH_PREC_SINGLE> { typedef float real; typedef float mixed; typedef float4 real4; typedef float4 mixed4; };
-template <> struct Prec<TGNH_PREC_MIXED>  { typedef float real; typedef double mixed; typedef float4 real4; typedef double4 mixed4; };
-template <> struct Prec<TGNH_PREC_DOUBLE> { typedef double real; typedef double mixed; typedef double4 real4; typedef double4 mixed4; };
-
-__device__ __forceinline__ float4 mk4(float x, float y, float z, float w) { return make_float4(x, y, z, w); }
-__device__ __forceinline__ double4 mk4(double x, double y, double z, double w) { return make_double4(x, y, z, w); }
-__device__ __forceinline__ float rcp_(float x) { return 1.0f / x; }
-// fp64 reciprocal of a normal, non-zero number (masses and their sums): hardware seed + two Newton steps, 5
-// instructions and <= 1-2 ulp, where the IEEE division is 11 (it also scales denormals and fixes up specials).
-__device__ __forceinline__ double rcp_(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    r = fma(fma(-x, r, 1.0), r, r);
-    r = fma(fma(-x, r, 1.0), r, r);
-    return r;
-}
-__device__ __forceinline__ float sqrt_(float x) { return sqrtf(x); }
-__device__ __forceinline__ double sqrt_(double x) { return sqrt(x); }
-__device__ __forceinline__ float abs_(float x) { return fabsf(x); }
-__device__ __forceinline__ double abs_(double x) { return fabs(x); }
-
-// Sum over the 64 lanes of a wavefront, the same value (and the same bits) in every lane.  Data-parallel-primitive moves
-// inside the vector ALU -- quads, then rows of 16 (row_shr 4, 8), then row broadcasts; the total lands in lane 63 and is read
-// back as a scalar -- instead of six __shfl_xor butterflies: a shuffle is two ds_bpermute_b32 through the LDS crossbar per
-// double, ~100 cycles of latency per step, and these sums (the kinetic-energy bins at the end of a pass, the rows collected by
-// work-group 0) sit on the path every work-group of a launch waits for.  The order of the additions is fixed.
-#ifndef TGNH_WAVE_SUM_DPP
-#define TGNH_WAVE_SUM_DPP 1
+#ifndef TGNH_MINWAVES
+#define TGNH_MINWAVES 1
 #endif
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_add(const double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);   // lanes without a source: +0.0
-    return v + __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#if TGNH_WAVE_SUM_DPP
-    v = dpp_add<0xb1, 0xf>(v);       // quad_perm:[1,0,3,2]
-    v = dpp_add<0x4e, 0xf>(v);       // quad_perm:[2,3,0,1]: every lane of a quad holds the quad's sum
-    v = dpp_add<0x114, 0xf>(v);      // row_shr:4
-    v = dpp_add<0x118, 0xf>(v);      // row_shr:8: lane 15 of every row holds the row's sum
-    v = dpp_add<0x142, 0xa>(v);      // row_bcast:15 into rows 1 and 3
-    v = dpp_add<0x143, 0xc>(v);      // row_bcast:31 into rows 2 and 3: lane 63 holds the total
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-#else
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-#endif
-}
-
 
 // What a work-group carries through a launch: the LDS carve, its KE accumulators, launch constants.
 template <int PREC, int GB> struct TileEnv {
@@ -136,14 +65,6 @@ template <int PREC, int GB> struct TileEnv {
     }
 };
 
-// step_kernel's tagged rows: word j (two per thermostat) of row r.  Rows come in blocks of 64 -- the rows one wavefront of the
-// collecting work-group reads with one load -- and inside a block word-major: the 64 lanes of a load read 512 contiguous
-// bytes (one request per 64-byte line instead of one per lane: the collection is bound by the requests a single compute
-// unit issues), and the words of a row lie 512 bytes apart, within reach of a load's immediate offset (one address per row).
-__device__ __forceinline__ size_t row_word(const int r, const int j) {
-    return ((size_t)(r >> 6) * (2 * CHAIN_INLINE_SUM_NT) + j) * 64 + (r & 63);
-}
-
 // Work-group reduction of the fp64 KE bins: 64-lane sums (wave_sum), then one LDS hop; one row of `partials` per work-group.
 // TAGGED: the row is read by another work-group of the SAME launch (step_kernel): every sum goes out as a cell of two
 // 8-byte words {32 bits of the double, tag} into a.rows -- data and "it is there" in one atomic store, as in the mailboxes.
@@ -157,9 +78,7 @@ __device__ __forceinline__ void ke_reduce(const TileArgs& a, TileEnv<PREC, GB>& 
     auto put = [&](const int b, double v) {
         if (TAGGED) {
             unsigned long long* cell = a.rows + row_word((int)blockIdx.x, 2 * b);
-            const unsigned long long bits = (unsigned long long)__double_as_longlong(v), t = (unsigned long long)tag << 32;
-            __hip_atomic_store(cell, t | (bits & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(cell + 64, t | (bits >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            store_tagged(cell, cell + 64, (unsigned long long)tag << 32, v);
         } else a.partials[(size_t)blockIdx.x * (G + 2) + b] = v;
     };
     double* sred = scratch ? scratch : reinterpret_cast<double*>(e.smem);   // [TBLOCK/64][GB+2]
@@ -194,385 +113,308 @@ __device__ __forceinline__ void ke_reduce(const TileArgs& a, TileEnv<PREC, GB>& 
     }
 }
 
-// (mixed)force: the fixed-point force as a floating-point number, rounded once.  For doubles hi 2^32 + lo in one fma --
-// both parts are exact, so this is the correctly rounded conversion (the bits of the cast) in 3 instructions instead of 4.
-__device__ __forceinline__ double force_as(const long long f, double) {
-    return fma((double)(int)(f >> 32), 4294967296.0, (double)(unsigned)f);
-}
-__device__ __forceinline__ float force_as(const long long f, float) { return (float)f; }
-
-// Wave tiles of identical molecules (PATTERN_WORDS, tgnh_internal.h): a lane's position in the pattern is the same in every such
-// tile (they all start on a molecule), so the lane keeps its word in a register and fetches it again only when a tile of another
-// pattern comes by -- for a water box once per launch.  pat = period | pattern << 8, 0 = this tile's words are read from wmeta.
-struct PatternWord {
-    uint32_t pat = 0u, word = 0u;
-    __device__ __forceinline__ bool of(const TileArgs& a, const uint32_t p, const int lane) {     // wavefront-uniform
-        if ((p & 255u) == 0u) return false;
-        if (p != pat) {
-            const int period = (int)(p & 255u);
-            const int q = (int)(((float)lane + 0.5f) * __builtin_amdgcn_rcpf((float)period));     // lane div period (never within rounding of an integer)
-            word = a.wpattern[(p >> 8) * PATTERN_WORDS + (uint32_t)(lane - q * period)];
-            pat = p;
-        }
-        return true;
-    }
+// Raw register image of one tile's global loads.
+template <int PREC> struct TileIn {
+    int ts, te, rs, nres;
+    typename Prec<PREC>::mixed4 v[SPT];
+    uint32_t meta[SPT];
+    long long fx[SPT], fy[SPT], fz[SPT];
+    typename Prec<PREC>::real4 p[SPT];
+    float4 c[SPT];
+    typename Prec<PREC>::mixed4 pd[SPT];
+    int2 rt;                 // this lane's molecule entry (lane r < nres): fetched with the tile, not after the first barrier
 };
 
-// Work-group 0 collects the tagged rows of a launch (ke_reduce<TAGGED>): thread t owns rows t, t + NTH, ...: it polls their cells
-// until all carry `want` and adds them in row order into acc[] (fixed order: reproducible bits).  Returns false when a row
-// never came (bounded polling).
-template <int GB, bool LEAN, int NTH>
-__device__ __forceinline__ bool collect_rows(const TileArgs& a, const int tid, const int grid, const int NT, const unsigned long long want,
-                                             double (&acc)[GB + 2]) {
-    constexpr int NTM = GB + 2;
-    bool ok = true;
-    // RB rows of this thread per batch of loads (all of them for the resident grid of 768 when G = 1): once the last row
-        // is there, one more round trip sees everything -- polled row after row, a thread whose first row came last paid
-        // a round trip for each of the others behind it.  CH thermostats of a row per batch: the registers a batch takes
-        // (2 x CH x RB words) do not grow with the number of temperature groups.  A row seen complete is not read again: a
-        // round waits for all of its loads together (~1 us with everything polled), and the round that finally sees the last
-        // row is a short one when it polls the stragglers only (last row -> all seen 1.6 instead of 2.3 us at 625 k slots).
-        constexpr int RB = (GB == 1 && !LEAN) ? 3 : 1, CH = 3;
-#pragma unroll 1
-        for (int r0 = tid; r0 < grid && ok; r0 += RB * NTH) {
-#pragma unroll 1
-            for (int b0 = 0; b0 < NT && ok; b0 += CH) {
-                unsigned long long w[RB][2 * CH];
-                bool have[RB];                              // a row seen complete is not read again: later rounds poll the stragglers only
-#pragma unroll
-                for (int k = 0; k < RB; k++) have[k] = r0 + k * NTH >= grid;
-                unsigned n = 0;
-                for (;;) {
-#pragma unroll
-                    for (int k = 0; k < RB; k++) {
-                        if (!have[k]) {
-                            const unsigned long long* cell = a.rows + row_word(r0 + k * NTH, 2 * b0);   // the lanes of a load read consecutive words
-#pragma unroll
-                            for (int b = 0; b < 2 * CH; b++) if (b0 + b / 2 < NT) w[k][b] = xchg_ld(cell + b * 64);
-                        }
-                    }
-                    bool all = true;
-#pragma unroll
-                    for (int k = 0; k < RB; k++) {
-                        if (!have[k]) {
-                            bool row = true;
-#pragma unroll
-                            for (int b = 0; b < 2 * CH; b++) if (b0 + b / 2 < NT) row = row && (w[k][b] >> 32) == want;
-                            have[k] = row;
-                        }
-                        all = all && have[k];
-                    }
-                    if (all) break;
-                    if (++n > XCHG_SPIN_LIMIT) { ok = false; break; }
-                }
-#pragma unroll
-                for (int k = 0; k < RB; k++)                // row order: r0, r0 + 256, ...
-#pragma unroll
-                    for (int b = 0; b < CH; b++)
-                        if (b0 + b < NT && r0 + k * NTH < grid) {
-                            const double v = __longlong_as_double((long long)((w[k][2 * b + 1] << 32) | (w[k][2 * b] & 0xffffffffull)));
-#pragma unroll
-                            for (int t = 0; t < NTM; t++) acc[t] += (t == b0 + b) ? v : 0.0;
-                        }
-            }
-        }
-    return ok;
-}
-
-// The meeting of step_kernel / wstep_kernel: every work-group hands in its row of kinetic-energy sums (tagged cells), work-group 0
-// collects them in a fixed order and sends the sums to the mailbox of every rank, one wavefront of every work-group waits for all
-// ranks' sums and runs both chain halves (the scale factors land in sh.s_scale).  `prefetch` is called between handing in the
-// row and the wait: the loads the second pass will need.  Returns false when an exchange timed out (nothing may be stored).
-struct MeetShared {
-    double* s_scale;                                  // [MAX_GROUPS + 2]
-    double (*s_part)[CHAIN_INLINE_SUM_NT];            // [TBLOCK / 64]
-    double* s_x;                                      // [64 + XCHG_MAX_WORLD * CHAIN_INLINE_SUM_NT]
-    int* s_go_p; unsigned* s_gen_p; unsigned long long* s_seq1_p;
-    const double* s_block;                            // MULTI: the thermostat block as it was at kernel entry (chains of 2-4 links)
-};
-template <int PREC, int GB, bool LEAN = false, int NTH = TBLOCK, bool MULTI = false, typename Prefetch>
-__device__ __forceinline__ bool step_meet(const TileArgs& a, TileEnv<PREC, GB>& e, const unsigned gen0, const unsigned long long seq0,
-                                          Chain1Regs& creg, const MeetShared& sh, Prefetch&& prefetch) {
-    double* const s_scale = sh.s_scale; double (*const s_part)[CHAIN_INLINE_SUM_NT] = sh.s_part; double* const s_x = sh.s_x;
-    int& s_go = *sh.s_go_p; unsigned& s_gen = *sh.s_gen_p; unsigned long long& s_seq1 = *sh.s_seq1_p;
-    const int tid = threadIdx.x, G = a.num_groups, NT = G + 2, grid = (int)gridDim.x;
-    const bool chain_wave = tid < 64, leader = blockIdx.x == 0;
-    const int itg = tid & 63;
-    const ChainLayout& L = a.chain.L;
-    // the thermostat block has been read (its values are in registers) before this work-group's row is stored
-    if (chain_wave) asm volatile("" :: "v"(creg.eta), "v"(creg.etaDot0), "v"(creg.etaDot1), "v"(creg.etaDotDot), "v"(creg.etaMass), "v"(creg.nkbt) : "memory");
-    ke_reduce<PREC, GB, true, NTH>(a, e, gen0 + 1u, s_x);
-    TRACE(2);
-    // what the second pass needs of the held tile beyond what is in registers (its positions): issued now, needed after the meeting
-    prefetch();
-    // ... and what the chain can form without the sums (index map, constants, 1/Q, expfac): done while the others still work
-    // (single precision: its 16 registers there would cost the kernel its fourth work-group per compute unit)
-    constexpr bool EARLY_PRE = PREC != TGNH_PREC_SINGLE && !LEAN;      // (LEAN: wstep_kernel, which lives on a small register count: with it 130 VGPRs, one work-group per compute unit)
-    Chain1Pre cpre{};
-    if (EARLY_PRE && chain_wave && !L.c1_quirk && !(MULTI && L.C > 1)) cpre = chain1_prepare(a.chain, creg, itg);
-
-    // ---- meet: work-group 0 collects the rows.  Thread t owns rows t, t + 256, ...: it polls their cells until all
-    // carry this launch's tag and adds them in row order; then 64-lane sums and one LDS hop, fixed order throughout.
-    if (tid == 0) { s_gen = gen0; s_seq1 = seq0 + 1ull; }
-    __syncthreads();
-    const unsigned long long want = (unsigned long long)(s_gen + 1u);
-    if (leader) {
-        unsigned long long* const my_peer = xchg_peer_of(a.chain.x, tid);   // for the send: fetched before the collection, not after
-        constexpr int NTM = GB + 2;                        // NT = G + 2 <= GB + 2: the register arrays follow the instantiation
-        double acc[NTM];
-#pragma unroll
-        for (int b = 0; b < NTM; b++) acc[b] = 0.0;
-        bool ok = true;
-        TRACE(6);
-        ok = collect_rows<GB, LEAN, NTH>(a, tid, grid, NT, want, acc);
-        TRACE(10);
-        if (!ok) {                                         // a work-group never handed in its row: nobody goes on (no send below)
-            atomicOr(a.status, 8u);
-            __hip_atomic_store(a.chain.x.dead, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        const double* big = a.partials + (size_t)GRID_CAP * NT;               // rows of big_com_kernel (an earlier launch)
-        for (int r = tid; r < a.chain.nbig; r += NTH)
-#pragma unroll
-            for (int b = 0; b < NTM; b++) if (b < NT) acc[b] += big[(size_t)r * NT + b];
-#pragma unroll
-        for (int b = 0; b < NTM; b++) {
-            if (b < NT) {
-                const double t = wave_sum(acc[b]);
-                if ((tid & 63) == 0) s_part[tid >> 6][b] = t;
-            }
-        }
-        // (the barrier of the hand-over doubles as the vote: one thread that gave up on a row stops the whole send -- incomplete
-        // sums under a valid tag would let every waiter, here and on the peer ranks, integrate with wrong scale factors; without
-        // the send they time out or see the latch, and nothing is stored)
-        const bool all_ok = __syncthreads_and(ok ? 1 : 0) != 0;
-        TRACE(7);
-        // the send (xchg_send's stores, tgnh_chain_device.h), straight from the four wavefronts' partial sums: every storing
-        // thread adds them itself, in wavefront order -- no second hand-over through LDS, no second barrier on this path
-        const XchgArgs& x = a.chain.x;
-        const unsigned long long seq = s_seq1, stag = (seq & 0xffffffffull) << 32;
-        if (tid == 0) { a.sync[1] = s_gen + 1u; *x.seq = seq; }      // the next launch's rows carry the next tag
-        const int tpp = NTH / x.world;
-        if (all_ok && tid < tpp * x.world) {
-            unsigned long long* const base = my_peer + xchg_cell(x, (unsigned)(seq & 1ull), x.rank, 0, 0);
-            for (int q = tid / x.world; q < NT * XCHG_REPLICAS; q += tpp) {
-                const int copy = q / NT, i = q - copy * NT;
-                double v = 0.0;
-#pragma unroll
-                for (int w = 0; w < NTH / 64; w++) v += s_part[w][i];
-                const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
-                unsigned long long* cell = base + (size_t)copy * XCHG_REPLICA_U64 + (size_t)i * XCHG_CELL_U64;
-                __hip_atomic_store(cell, stag | (bits & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(cell + 1, stag | (bits >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-        TRACE(13);
-    }
-    if (chain_wave) {
-        bool dead = false;                                 // an exchange has timed out, now or earlier (the latch)
-        const double mine = xchg_wait_sum<true>(a.chain.x, NT, itg, s_x + 64, seq0 + 1ull, &dead);
-        TRACE(8);
-        if (itg == 0) s_go = dead ? 0 : 1;
-        if (!dead) {
-            const bool write = leader;
-            creg.ke = mine;
-            if (write && itg < NT) a.st_out[L.off_ke_red + itg] = mine;
-            if (write) {                                   // Cu :493-497 (work-group 0 only: the others go straight on to the chain)
-                const double kesum = wave_sum(itg < NT ? mine : 0.0);
-                if (itg == 63) a.st_out[L.off_kesum] = 0.5 * kesum;
-            }
-            if (MULTI && L.C > 1) chainN_run<false>(a.chain, sh.s_block, a.st_out, write, s_scale, itg, mine);
-            else if (itg < NT) {
-                if (L.c1_quirk) chain1q_run(a.chain, creg, a.st_out, write, s_scale, itg);
-                else chain1_finish(a.chain, creg, EARLY_PRE ? cpre : chain1_prepare(a.chain, creg, itg), a.st_out, write, s_scale, itg);
-            }
-        }
-    }
-    __syncthreads();
-    return s_go != 0;
-}
-
-template <int PREC> struct WStepIn {
-    typename Prec<PREC>::mixed4 v;
-    uint32_t meta;
-    long long fx, fy, fz;
-    typename Prec<PREC>::real4 p;
-    float4 c;
-    // formed by the first half of the work on a tile (prepare): mass, centre-of-mass velocity of the slot's molecule
-    typename Prec<PREC>::mixed mass, cx, cy, cz;
+// Tiles of identical molecules (PATTERN_WORDS, tgnh_internal.h): a thread's slots sit at the same positions in every tile, so the
+// words it forms for one tile of a pattern are the words of the next -- kept in registers, formed again when the pattern changes
+// (a water box: once per launch; the pattern's lines would otherwise be fetched by every wavefront of the chip for every tile).
+struct TilePattern {
+    uint32_t pat = 0u;
+    uint32_t word[SPT] = {};
 };
 
-// ---------------------------------------------------------------------------
-// The per-tile work of the one-launch step over WAVE tiles (wstep_kernel): a wavefront owns <= 64 consecutive
-// slots and a private LDS image (velocity x, y, z, mass; position x, y, z for the hard wall); nothing here waits for another
-// wavefront.  load_vf / load_x issue a tile's global loads, prepare forms mass, the half kick (KICK), the image and the
-// molecule's centre-of-mass velocity and -- ke -- adds the tile's kinetic energies to the bins (pass 1); finish is pass 2:
-// rescale, half kick, drift, hard wall, stores.  The arithmetic per slot is tile_body's / wke_kernel's, expression for expression.
-// Reference: K :82-113, :138-200 (COM, bins), :249-301 (rescale), :307-365 (kick), :435-466 (drift), :471-574 (hard wall).
-// ---------------------------------------------------------------------------
-struct WaveBounds { int ws, y, n; };        // first slot; the tile's largest molecule | pattern word << 8; slots
+// which arrays a pass touches
+template <int OPS> struct OpsOf {
+    static constexpr bool DO_SCALE = OPS & OP_SCALE, DO_KICK = OPS & OP_KICK, DO_DRIFT = OPS & OP_DRIFT;
+    static constexpr bool DO_KE = OPS & OP_KE, DO_PD = OPS & OP_POSDELTA, DO_MOVE = OPS & OP_MOVE;
+    // OP_PREKICK: the half kick a kick+KE pass of the previous step formed for its sums but did not store
+    // (OP_NOSTORE) is applied first -- same force buffer, same expression, same bits (DESIGN.md "deferred kick")
+    static constexpr bool DO_PREKICK = OPS & OP_PREKICK, NOSTORE = OPS & OP_NOSTORE;
+    static constexpr bool NEED_F = DO_KICK || DO_PREKICK;
+    static constexpr bool POS = DO_DRIFT || DO_MOVE;            // positions are read and written
+    static constexpr bool VEL_W = (DO_SCALE || DO_KICK || DO_MOVE) && !NOSTORE;   // velocities are written
+};
 
-template <int PREC, int GB> struct WaveStep {
+// issue the global loads of tile t for a pass with operations OPS.  HAVE != 0: `in` already holds what a pass with
+// operations HAVE loaded for this very tile (velocities, index words, and its forces if it needed them): fetch the rest.
+// PATTERN = false: always the per-slot words (tile_kernel's read-only KE passes, at their register budget of 5 work-groups per CU).
+template <int PREC, int OPS, int HAVE = 0, bool PATTERN = true>
+__device__ __forceinline__ void tile_load(const TileArgs& a, const int t, TileIn<PREC>& in, TilePattern& tp) {
+    constexpr bool KEEP_VF = HAVE != 0;
+    constexpr bool LOAD_F = OpsOf<OPS>::NEED_F && !(KEEP_VF && OpsOf<HAVE>::NEED_F);
+    typedef typename Prec<PREC>::mixed mixed;
+    typedef typename Prec<PREC>::real4 real4;
+    typedef typename Prec<PREC>::mixed4 mixed4;
+    typedef OpsOf<OPS> O;
+    const int tid = threadIdx.x;
+    const mixed4* __restrict__ velm = reinterpret_cast<const mixed4*>(a.velm);
+    const real4* __restrict__ posq = reinterpret_cast<const real4*>(a.posq);
+    const float4* __restrict__ pcorr = reinterpret_cast<const float4*>(a.posq_corr);
+    const mixed4* __restrict__ pdelta = reinterpret_cast<const mixed4*>(a.pos_delta);
+    if (!KEEP_VF) {
+        in.ts = a.tile_start[t]; in.te = a.tile_start[t + 1];
+        in.rs = a.tile_res[t]; in.nres = a.tile_res[t + 1] - in.rs;
+        if ((O::DO_SCALE || O::DO_KE) && a.use_com && tid < in.nres) in.rt = a.res_table[in.rs + tid];
+    }
+    // a tile of identical molecules: the slot's word from its position (TilePattern), no 4 B per slot from HBM
+    const uint32_t pat = (KEEP_VF || !PATTERN) ? 0u : a.tile_pat[t];
+    if (pat != 0u && pat != tp.pat) {                             // (work-group-uniform)
+        const int period = (int)(pat & 255u), mols = (int)((pat >> 8) & 255u);
+        const uint32_t* __restrict__ words = a.pattern + (size_t)(pat >> 16) * PATTERN_WORDS;
+        const float rperiod = __builtin_amdgcn_rcpf((float)period);
+#pragma unroll
+        for (int k = 0; k < SPT; k++) {
+            const int pos = k * TBLOCK + tid;
+            const int q = (int)(((float)pos + 0.5f) * rperiod);          // pos div period (pos < 512, period <= 64: never within rounding of an integer)
+            tp.word[k] = words[pos - q * period] + (a.use_com ? (uint32_t)(q * mols) << 21 : 0u);
+        }
+        tp.pat = pat;
+    }
+#pragma unroll
+    for (int k = 0; k < SPT; k++) {
+        const int idx = in.ts + k * TBLOCK + tid;
+        if (idx < in.te) {
+            if (!KEEP_VF) {
+                in.v[k] = velm[idx];
+                if (pat == 0u) in.meta[k] = a.meta[idx];
+                else in.meta[k] = tp.word[k];
+            }
+            if (LOAD_F) {
+                in.fx[k] = a.force[idx];
+                in.fy[k] = a.force[idx + a.padded];
+                in.fz[k] = a.force[idx + 2 * a.padded];
+            }
+            if (O::POS) {
+                in.p[k] = posq[idx];
+                if (PREC == TGNH_PREC_MIXED) in.c[k] = pcorr[idx];       // K :443-445
+            }
+            if (O::DO_MOVE) in.pd[k] = pdelta[idx];
+        } else if (!KEEP_VF) {
+            in.v[k] = mk4((mixed)0, (mixed)0, (mixed)0, (mixed)0);       // w = 0: treated as massless, never stored
+            in.meta[k] = 0u;
+        }
+    }
+}
+
+// One tile, loaded into `cur`, through the operations OPS (A3/A4, A6, A7, A8, A10).  Ends with the LDS images free.
+// reuse_img (step_kernel): the velocity image and the COM table of this very tile are still in LDS from the pass before.
+template <int PREC, int OPS, int GB>
+__device__ __forceinline__ void tile_body(const TileArgs& a, TileEnv<PREC, GB>& e, const TileIn<PREC>& cur, const int trace_tile,
+                                          const bool reuse_img = false) {
     typedef typename Prec<PREC>::real real;
     typedef typename Prec<PREC>::mixed mixed;
     typedef typename Prec<PREC>::real4 real4;
     typedef typename Prec<PREC>::mixed4 mixed4;
-    const TileArgs& a;
-    TileEnv<PREC, GB>* e;                   // the kinetic-energy bins, in the shape ke_reduce takes them
-    const double* s_scale;
-    mixed *ix, *iy, *iz, *im, *jx, *jy, *jz;
-    mixed4* __restrict__ velm; real4* __restrict__ posq; float4* __restrict__ pcorr;
-    int lane, G, nw;
-    bool use_com, hardwall;
-    mixed dt, fscale;
-    PatternWord pw;
-    // img: this wavefront's [7][WAVE_SLOTS] LDS image
-    __device__ __forceinline__ WaveStep(const TileArgs& a_, TileEnv<PREC, GB>* e_, const double* s_scale_, mixed* img, const int lane_)
-        : a(a_), e(e_), s_scale(s_scale_), ix(img), iy(img + WAVE_SLOTS), iz(img + 2 * WAVE_SLOTS), im(img + 3 * WAVE_SLOTS),
-          jx(img + 4 * WAVE_SLOTS), jy(img + 5 * WAVE_SLOTS), jz(img + 6 * WAVE_SLOTS),
-          velm(reinterpret_cast<mixed4*>(a_.velm)), posq(reinterpret_cast<real4*>(a_.posq)), pcorr(reinterpret_cast<float4*>(a_.posq_corr)),
-          lane(lane_), G(a_.num_groups), nw(a_.num_wtiles), use_com(a_.use_com != 0), hardwall(a_.hardwall != 0),
-          dt((mixed)a_.dt), fscale((mixed)(0.5 * a_.dt / 4294967296.0)) {}     // Cu :295
-    __device__ __forceinline__ static void wfence() {      // a wavefront's LDS operations are processed in order: only the compiler is held
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    __device__ __forceinline__ void bounds(const int ww, WaveBounds& b) const {      // (wavefront-uniform: scalar loads)
-        const int2* t = a.wave_tile + (a.reverse ? nw - 1 - ww : ww);
-        b.ws = t[0].x; b.y = t[0].y; b.n = t[1].x - b.ws;
-    }
-    __device__ __forceinline__ void load_vf(const WaveBounds& b, WStepIn<PREC>& in) {          // what pass 1 needs
-        const int idx = b.ws + lane;
-        const bool patterned = pw.of(a, (uint32_t)b.y >> 8, lane);
-        mixed4 v = mk4((mixed)0, (mixed)0, (mixed)0, (mixed)0);
-        uint32_t meta = 64u << 10;
-        long long fx = 0, fy = 0, fz = 0;
-        if (lane < b.n) {
-            v = reinterpret_cast<const mixed4*>(a.velm)[idx];
-            if (!patterned) meta = a.wmeta[idx];
-            fx = a.force[idx]; fy = a.force[idx + a.padded]; fz = a.force[idx + 2 * a.padded];
-        }
-        if (patterned && lane < b.n) meta = pw.word;
-        in.v = v; in.meta = meta; in.fx = fx; in.fy = fy; in.fz = fz;
-    }
-    __device__ __forceinline__ void load_x(const WaveBounds& b, WStepIn<PREC>& in) const {           // ... and what pass 2 needs on top
-        const int idx = b.ws + lane;
-        if (lane < b.n) {
-            in.p = reinterpret_cast<const real4*>(a.posq)[idx];
-            if (PREC == TGNH_PREC_MIXED) in.c = reinterpret_cast<const float4*>(a.posq_corr)[idx];      // K :443-445
-        }
-    }
-    // first half of the work on a tile: mass, the pending half kick, the wavefront's image, the molecule's centre-of-mass
-    // velocity; KE: this tile's kinetic energies go into the bins (pass 1)
-    template <bool KICK = true>
-    __device__ __forceinline__ void prepare(WStepIn<PREC>& t, const WaveBounds& bd, const bool ke) {
-        mixed4& v = t.v;
-        const uint32_t m = t.meta;
-        t.mass = v.w != 0 ? rcp_(v.w) : (mixed)0;
-        if (KICK) {                                                      // A7 (Cu :384-388), per particle; w = 0: c = 0, v unchanged
-            const mixed c = fscale * v.w;
-            v.x += c * force_as(t.fx, (mixed)0);
-            v.y += c * force_as(t.fy, (mixed)0);
-            v.z += c * force_as(t.fz, (mixed)0);
-        }
-        ix[lane] = v.x; iy[lane] = v.y; iz[lane] = v.z; im[lane] = t.mass;
-        wfence();
-        mixed cx = 0, cy = 0, cz = 0;
-        if (use_com) {                                                   // K :86-111: every lane sums its own molecule, in slot order
-            const int j = (int)((m >> 17) & 63u), n1 = (int)((m >> 23) & 63u);
-            const int first = lane - j;
-            mixed px = 0, py = 0, pz = 0, pm = 0;
-            for (int k = 0; k < (bd.y & 255); k++) {
-                if (k <= n1) {
-                    const mixed um = im[first + k];
-                    px += ix[first + k] * um; py += iy[first + k] * um; pz += iz[first + k] * um; pm += um;
-                }
-            }
-            const mixed wq = rcp_(pm);
-            cx = px * wq; cy = py * wq; cz = pz * wq;
-            if (ke && j == 0 && lane < bd.n)                             // M v_com^2 (K :154)
-                e->ke_com += ((double)cx * cx + (double)cy * cy + (double)cz * cz) * (double)pm;
-        }
-        t.cx = cx; t.cy = cy; t.cz = cz;
-        if (ke) {                                                        // bins, as wke_kernel (K :138-200)
-            const uint32_t role = m & 3u, g = (m >> 2) & 255u;
-            const double rx = v.x - cx, ry = v.y - cy, rz = v.z - cz;
-            double val = v.w != 0 ? (rx * rx + ry * ry + rz * rz) * (double)t.mass : 0.0;
-            if (role == ROLE_DRUDE) {
-                const int pl = lane + (int)((m >> 10) & 127u) - 64;
-                const double dx = ix[pl] - v.x, dy = iy[pl] - v.y, dz = iz[pl] - v.z;
-                const double mass1 = t.mass, mass2 = im[pl];
-                const double mu = mass1 * mass2 * rcp_(mass1 + mass2);
-                const double d = (dx * dx + dy * dy + dz * dz) * mu;
-                e->ke_drude += d;
-                val -= d;
-            }
+    typedef OpsOf<OPS> O;
+    typedef TileEnv<PREC, GB> E;
+    constexpr bool DO_SCALE = O::DO_SCALE, DO_KICK = O::DO_KICK, DO_DRIFT = O::DO_DRIFT, DO_KE = O::DO_KE, DO_PD = O::DO_PD;
+    constexpr bool DO_MOVE = O::DO_MOVE, DO_PREKICK = O::DO_PREKICK, NEED_F = O::NEED_F, POS = O::POS, VEL_W = O::VEL_W;
+    (void)trace_tile;
+    mixed4* const sv = e.sv; mixed4* const scom = e.scom; mixed4* const sx = e.sx;
+    const double* const s_scale = e.s_scale;
+    const int tid = e.tid, G = e.G;
+    const bool use_com = e.use_com;
+    const bool hardwall = POS && (a.hardwall != 0);
+    const mixed dt = e.dt, fscale = e.fscale, s_com = e.s_com, s_drude = e.s_drude;
+    double (&ke_g)[E::GBR] = e.ke_g;
+    double& ke_com = e.ke_com; double& ke_drude = e.ke_drude;
+    double* const wbins = e.wbins0 + (tid >> 6) * G;
+    mixed4* __restrict__ velm = reinterpret_cast<mixed4*>(a.velm);
+    real4* __restrict__ posq = reinterpret_cast<real4*>(a.posq);
+    float4* __restrict__ pcorr = reinterpret_cast<float4*>(a.posq_corr);
+    mixed4* __restrict__ pdelta = reinterpret_cast<mixed4*>(a.pos_delta);
+    auto st_img = [&](mixed4* img, int i, const mixed4& u) { E::st_img(img, i, u); };
+    auto ld_img = [&](const mixed4* img, int i) -> mixed4 { return E::ld_img(img, i); };
+    (void)G; (void)s_com; (void)s_drude; (void)dt; (void)fscale; (void)wbins; (void)ke_com; (void)ke_drude; (void)ke_g;
+    (void)posq; (void)pcorr; (void)pdelta; (void)velm; (void)s_scale;
+
+    const int ts = cur.ts, te = cur.te;
+    const int rs = cur.rs, nres = cur.nres;
+    TRACE_WAIT(); TRACE(3 + 4 * trace_tile);
+
+    mixed4 v[SPT];
+    uint32_t meta[SPT];
+    long long fx[SPT], fy[SPT], fz[SPT];
+    mixed px[SPT], py[SPT], pz[SPT];
+    real pq[SPT];
+    mixed4 pd[SPT];
+    bool ok[SPT];
 #pragma unroll
-            for (int b = 0; b < GB; b++) e->ke_g[b] += (g == (uint32_t)b) ? val : 0.0;
+    for (int k = 0; k < SPT; k++) {
+        ok[k] = ts + k * TBLOCK + tid < te;
+        v[k] = cur.v[k];
+        meta[k] = cur.meta[k];
+        if (NEED_F) { fx[k] = cur.fx[k]; fy[k] = cur.fy[k]; fz[k] = cur.fz[k]; }
+        if (POS) {
+            px[k] = cur.p[k].x; py[k] = cur.p[k].y; pz[k] = cur.p[k].z; pq[k] = cur.p[k].w;
+            if (PREC == TGNH_PREC_MIXED) { px[k] += (mixed)cur.c[k].x; py[k] += (mixed)cur.c[k].y; pz[k] += (mixed)cur.c[k].z; }
+        }
+        if (DO_MOVE) pd[k] = cur.pd[k];
+    }
+    // One fp64 division per slot: the mass.  The LDS images carry it in .w (0 = massless), so the per-molecule walk
+    // and the pair arithmetic multiply by masses instead of dividing by inverse masses again (K forms RECIP(w) in
+    // every kernel; an fp64 reciprocal is ~15 VALU instructions and these launches are VALU-heavy at small sizes).
+    mixed mass[SPT];
+#pragma unroll
+    for (int k = 0; k < SPT; k++) mass[k] = v[k].w != 0 ? rcp_(v[k].w) : (mixed)0;
+    if (DO_PREKICK) {                                            // the pending half kick (A7), as below
+#pragma unroll
+        for (int k = 0; k < SPT; k++) {
+            if (v[k].w != 0) half_kick<ForceCast>(v[k].x, v[k].y, v[k].z, v[k].w, fscale, fx[k], fy[k], fz[k]);
         }
     }
-    // second half (pass 2): rescale, half kick, drift, hard wall, stores.  The image holds the tile's kicked velocities and masses.
-    __device__ __forceinline__ void finish(WStepIn<PREC>& t, const WaveBounds& bd) {
-        mixed4 v = t.v;
-        const uint32_t m = t.meta;
-        const uint32_t role = m & 3u, g = (m >> 2) & 255u;
-        const int pl = lane + (int)((m >> 10) & 127u) - 64;
-        const mixed mass = t.mass, cx = t.cx, cy = t.cy, cz = t.cz;
-        const mixed s_com = (mixed)s_scale[G], s_drude = (mixed)s_scale[G + 1], s_g = (mixed)s_scale[g];
-        mixed px = t.p.x, py = t.p.y, pz = t.p.z;
-        const real pq = t.p.w;
-        if (PREC == TGNH_PREC_MIXED) { px += (mixed)t.c.x; py += (mixed)t.c.y; pz += (mixed)t.c.z; }
-        // ---- A6: rescale (K :249-301 ; Ref :516-541), tile_body's expressions
-        if (role == ROLE_NORMAL) {
-            if (v.w != 0) {
-                const mixed rx = v.x - cx, ry = v.y - cy, rz = v.z - cz;
-                v.x = s_g * rx + s_com * (v.x - rx);
-                v.y = s_g * ry + s_com * (v.y - ry);
-                v.z = s_g * rz + s_com * (v.z - rz);
+    auto img = [&](int k) { return mk4(v[k].x, v[k].y, v[k].z, mass[k]); };
+
+    bool lds_read = false;   // some lane may still be reading sv/scom of this tile
+
+    // ---------------- A6: rescale (K :249-301 ; Ref :516-541) ----------------
+    if (DO_SCALE) {
+      if (!reuse_img) {
+#pragma unroll
+        for (int k = 0; k < SPT; k++) st_img(sv, k * TBLOCK + tid, img(k));
+        __syncthreads();
+        if (use_com) {
+            for (int r = tid; r < nres; r += TBLOCK) {            // K :86-111
+                const int2 rt = r == tid ? cur.rt : a.res_table[rs + r];
+                if (rt.x < 0) { scom[r] = reinterpret_cast<const mixed4*>(a.big_com)[-rt.x - 1]; continue; }   // molecule longer than a tile
+                const int first = rt.y - ts;
+                mixed cx = 0, cy = 0, cz = 0, cm = 0;
+                for (int j = 0; j < rt.x; j++) {
+                    const mixed4 u = ld_img(sv, first + j);
+                    const mixed m = u.w;                       // mass (0 for massless sites)
+                    cx += u.x * m; cy += u.y * m; cz += u.z * m; cm += m;
+                }
+                const mixed w = rcp_(cm);
+                scom[r] = mk4(cx * w, cy * w, cz * w, w);
             }
-        } else {
-            const mixed ux = ix[pl], uy = iy[pl], uz = iz[pl], um = im[pl];      // partner velocity and mass
-            const mixed rsx = v.x - cx, rsy = v.y - cy, rsz = v.z - cz;
-            const mixed rpx = ux - cx, rpy = uy - cy, rpz = uz - cz;
-            const mixed invTot = rcp_(mass + um);
-            const mixed msf = invTot * mass, mpf = invTot * um;
-            const mixed sdp = s_drude * mpf;
-            v.x = s_g * (rsx * msf + rpx * mpf) + sdp * (rsx - rpx) + s_com * (v.x - rsx);
-            v.y = s_g * (rsy * msf + rpy * mpf) + sdp * (rsy - rpy) + s_com * (v.y - rsy);
-            v.z = s_g * (rsz * msf + rpz * mpf) + sdp * (rsz - rpz) + s_com * (v.z - rsz);
+            __syncthreads();
         }
-        // ---- A7: half kick (K :307-365) and A8: drift (Ref :253-258 ; K :322-324, :450-452)
-        if (v.w != 0) {
-            const mixed c = fscale * v.w;
-            v.x += c * force_as(t.fx, (mixed)0);
-            v.y += c * force_as(t.fy, (mixed)0);
-            v.z += c * force_as(t.fz, (mixed)0);
-            px += dt * v.x; py += dt * v.y; pz += dt * v.z;
+      }
+#pragma unroll
+        for (int k = 0; k < SPT; k++) {
+            const uint32_t m = meta[k];
+            const uint32_t role = m & 3u, g = (m >> 2) & 255u;
+            mixed cx = 0, cy = 0, cz = 0;
+            if (use_com) { const mixed4 c = scom[m >> 21]; cx = c.x; cy = c.y; cz = c.z; }
+            const mixed s_g = (mixed)s_scale[g];
+            if (role == ROLE_NORMAL) {
+                if (v[k].w != 0) {                               // K :260-265
+                    const mixed rx = v[k].x - cx, ry = v[k].y - cy, rz = v[k].z - cz;
+                    v[k].x = s_g * rx + s_com * (v[k].x - rx);
+                    v[k].y = s_g * ry + s_com * (v[k].y - ry);
+                    v[k].z = s_g * rz + s_com * (v[k].z - rz);
+                }
+            } else {                                             // K :270-300
+                // Written from the lane's own point of view (self s, partner p), which needs no role selects:
+                // with cm = (r_s m_s + r_p m_p)/M and K's rel = r_parent - r_drude, both
+                //   v_drude'  = s_g cm - s_D rel m_parent/M + s_COM v_com      (K :292-294)
+                //   v_parent' = s_g cm + s_D rel m_drude/M  + s_COM v_com      (K :295-297)
+                // read  v_s' = s_g cm + s_D (r_s - r_p) m_p/M + s_COM (v_s - r_s).
+                const int pl = k * TBLOCK + tid + (int)((m >> 10) & 2047u) - 1024;
+                const mixed4 u = ld_img(sv, pl);           // partner velocity, .w = partner mass
+                const mixed rsx = v[k].x - cx, rsy = v[k].y - cy, rsz = v[k].z - cz;
+                const mixed rpx = u.x - cx, rpy = u.y - cy, rpz = u.z - cz;
+                const mixed invTot = rcp_(mass[k] + u.w);
+                const mixed msf = invTot * mass[k], mpf = invTot * u.w;
+                const mixed sdp = s_drude * mpf;
+                v[k].x = s_g * (rsx * msf + rpx * mpf) + sdp * (rsx - rpx) + s_com * (v[k].x - rsx);
+                v[k].y = s_g * (rsy * msf + rpy * mpf) + sdp * (rsy - rpy) + s_com * (v[k].y - rsy);
+                v[k].z = s_g * (rsz * msf + rpz * mpf) + sdp * (rsz - rpz) + s_com * (v[k].z - rsz);
+            }
         }
-        // ---- A10: hard wall (K :471-574 ; Ref :298-363), tile_body's arithmetic from the lane's own point of view
-        if (hardwall) {
-            wfence();                                                    // every lane has read its partner's old velocity
-            ix[lane] = v.x; iy[lane] = v.y; iz[lane] = v.z;
-            jx[lane] = px; jy[lane] = py; jz[lane] = pz;
-            wfence();
+        lds_read = true;
+    }
+
+    TRACE(4 + 4 * trace_tile);
+    // ---------------- A8 (constrained path): x += posDelta, v = posDelta/dt (K :435-466) ---
+    if (DO_MOVE) {
+        const double invStep = 1.0 / a.dt;                       // K :436
+#pragma unroll
+        for (int k = 0; k < SPT; k++) {
+            if (v[k].w != 0) {
+                px[k] += pd[k].x; py[k] += pd[k].y; pz[k] += pd[k].z;
+                v[k].x = (mixed)(invStep * pd[k].x);
+                v[k].y = (mixed)(invStep * pd[k].y);
+                v[k].z = (mixed)(invStep * pd[k].z);
+            }
+        }
+    }
+
+    // ---------------- A7: half kick (K :307-365 ; Ref :548-584) ----------------
+    // Per-particle form v += (dt/2) F/m.  The reference writes the pair kick in
+    // COM/relative coordinates; that is algebraically the same update
+    // (tests/test_oracle.py::test_pair_kick_identity), so no partner access is needed here.
+    if (DO_KICK) {
+#pragma unroll
+        for (int k = 0; k < SPT; k++) {
+            if (v[k].w != 0) half_kick<ForceCast>(v[k].x, v[k].y, v[k].z, v[k].w, fscale, fx[k], fy[k], fz[k]);
+        }
+    }
+
+    // ---------------- A8: drift (Ref :253-258 ; K :322-324, :450-452) ----------------
+    if (DO_DRIFT) {
+#pragma unroll
+        for (int k = 0; k < SPT; k++) {
+            if (v[k].w != 0) {
+                px[k] += dt * v[k].x; py[k] += dt * v[k].y; pz[k] += dt * v[k].z;
+            }
+        }
+    }
+    if (DO_PD) {
+#pragma unroll
+        for (int k = 0; k < SPT; k++) {
+            const int idx = ts + k * TBLOCK + tid;
+            if (ok[k]) {
+                const bool mv = v[k].w != 0;
+                pdelta[idx] = mk4(mv ? dt * v[k].x : (mixed)0, mv ? dt * v[k].y : (mixed)0, mv ? dt * v[k].z : (mixed)0, (mixed)0);
+            }
+        }
+    }
+
+    // ---------------- A10: hard wall (K :471-574 ; Ref :298-363) ----------------
+    if (POS && hardwall) {
+        if (lds_read) __syncthreads();
+#pragma unroll
+        for (int k = 0; k < SPT; k++) {
+            st_img(sv, k * TBLOCK + tid, img(k));
+            st_img(sx, k * TBLOCK + tid, mk4(px[k], py[k], pz[k], (mixed)0));
+        }
+        __syncthreads();
+        const mixed maxd = (mixed)a.max_dist, hws = (mixed)a.hw_scale;
+#pragma unroll
+        for (int k = 0; k < SPT; k++) {
+            const uint32_t m = meta[k];
+            const uint32_t role = m & 3u;
             if (role != ROLE_NORMAL) {
-                const mixed maxd = (mixed)a.max_dist, hws = (mixed)a.hw_scale;
-                const mixed sxd = px - jx[pl], syd = py - jy[pl], szd = pz - jz[pl];     // self - partner
+                const int pl = k * TBLOCK + tid + (int)((m >> 10) & 2047u) - 1024;
+                const mixed4 ux = ld_img(sx, pl);
+                const mixed sxd = px[k] - ux.x, syd = py[k] - ux.y, szd = pz[k] - ux.z;     // self - partner
                 const mixed d2 = sxd * sxd + syd * syd + szd * szd;
-                if (d2 > maxd * maxd) {
-                    const mixed4 uv = mk4(ix[pl], iy[pl], iz[pl], im[pl]);
+                if (d2 > maxd * maxd) {                           // r > max  <=>  rInv*max < 1 (K :490): the rest only for violators
+                    const mixed4 uv = ld_img(sv, pl);
                     const bool is_d = role == ROLE_DRUDE;
-                    const mixed4 vel1 = is_d ? v : uv, vel2 = is_d ? uv : v;
+                    const mixed4 vel1 = is_d ? v[k] : uv, vel2 = is_d ? uv : v[k];
                     const mixed dx = is_d ? sxd : -sxd, dy = is_d ? syd : -syd, dz = is_d ? szd : -szd;   // Drude - parent (K :487)
                     const mixed r = sqrt_(d2);
                     const mixed rInv = rcp_(r);
                     if (rInv * maxd < (mixed)0.5) atomicOr(a.status, 1u);     // Ref :311-312
                     const mixed bx = dx * rInv, by = dy * rInv, bz = dz * rInv;
-                    const mixed mass1 = is_d ? mass : uv.w, mass2 = is_d ? uv.w : mass;
+                    const mixed mass1 = is_d ? mass[k] : uv.w, mass2 = is_d ? uv.w : mass[k];   // image .w = mass
                     const mixed deltaR = r - maxd;
                     mixed deltaT = dt;
                     mixed dotvr1 = vel1.x * bx + vel1.y * by + vel1.z * bz;
                     const mixed vp1x = vel1.x - bx * dotvr1, vp1y = vel1.y - by * dotvr1, vp1z = vel1.z - bz * dotvr1;
+                    // K :527-571 (a massless parent, K :504-526, cannot occur: tgnh_create rejects massless pair members)
                     const mixed invTot = rcp_(mass1 + mass2);
                     mixed dotvr2 = vel2.x * bx + vel2.y * by + vel2.z * bz;
                     const mixed vp2x = vel2.x - bx * dotvr2, vp2y = vel2.y - by * dotvr2, vp2z = vel2.z - bz * dotvr2;
@@ -589,29 +431,100 @@ template <int PREC, int GB> struct WaveStep {
                     dotvr1 += vbCMass;
                     dotvr2 += vbCMass;
                     if (is_d) {
-                        px += bx * dr1; py += by * dr1; pz += bz * dr1;
-                        v.x = vp1x + bx * dotvr1; v.y = vp1y + by * dotvr1; v.z = vp1z + bz * dotvr1;
+                        px[k] += bx * dr1; py[k] += by * dr1; pz[k] += bz * dr1;
+                        v[k].x = vp1x + bx * dotvr1; v[k].y = vp1y + by * dotvr1; v[k].z = vp1z + bz * dotvr1;
                     } else {
-                        px += bx * dr2; py += by * dr2; pz += bz * dr2;
-                        v.x = vp2x + bx * dotvr2; v.y = vp2y + by * dotvr2; v.z = vp2z + bz * dotvr2;
+                        px[k] += bx * dr2; py[k] += by * dr2; pz[k] += bz * dr2;
+                        v[k].x = vp2x + bx * dotvr2; v[k].y = vp2y + by * dotvr2; v[k].z = vp2z + bz * dotvr2;
                     }
                 }
             }
         }
-        wfence();                                                        // the next tile's image comes after this tile's reads
-        if (lane < bd.n) {
-            const int idx = bd.ws + lane;
-            velm[idx] = v;
-            if (PREC == TGNH_PREC_MIXED) {                               // K :457-458
-                const float hx = (float)px, hy = (float)py, hz = (float)pz;
-                posq[idx] = mk4((real)hx, (real)hy, (real)hz, pq);
-                pcorr[idx] = make_float4((float)(px - hx), (float)(py - hy), (float)(pz - hz), 0.0f);
-            } else {
-                posq[idx] = mk4((real)px, (real)py, (real)pz, pq);
-            }
+        lds_read = true;
+    }
+
+    TRACE(5 + 4 * trace_tile);
+    // ---------------- stores ----------------
+#pragma unroll
+    for (int k = 0; k < SPT; k++) {
+        const int idx = ts + k * TBLOCK + tid;
+        if (ok[k]) {
+            if (VEL_W || (POS && hardwall)) velm[idx] = v[k];
+            if (POS) store_position<PREC>(posq, pcorr, idx, px[k], py[k], pz[k], pq[k]);
         }
     }
-};
+
+    // ---------------- A3/A4: kinetic energies (K :82-200 ; Ref :439-460) ----------------
+    if (DO_KE) {
+        if (lds_read) __syncthreads();
+#pragma unroll
+        for (int k = 0; k < SPT; k++) st_img(sv, k * TBLOCK + tid, img(k));
+        __syncthreads();
+        if (use_com) {
+            for (int r = tid; r < nres; r += TBLOCK) {            // K :86-111, :152-158
+                const int2 rt = r == tid ? cur.rt : a.res_table[rs + r];
+                if (rt.x < 0) { scom[r] = reinterpret_cast<const mixed4*>(a.big_com)[-rt.x - 1]; continue; }   // its M v_com^2 comes from big_com_kernel
+                const int first = rt.y - ts;
+                mixed cx = 0, cy = 0, cz = 0, cm = 0;
+                for (int j = 0; j < rt.x; j++) {
+                    const mixed4 u = ld_img(sv, first + j);
+                    const mixed m = u.w;                       // mass (0 for massless sites)
+                    cx += u.x * m; cy += u.y * m; cz += u.z * m; cm += m;
+                }
+                const mixed w = rcp_(cm);
+                cx *= w; cy *= w; cz *= w;
+                scom[r] = mk4(cx, cy, cz, w);
+                ke_com += ((double)cx * cx + (double)cy * cy + (double)cz * cz) * (double)cm;     // M v_com^2 (K :154)
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int k = 0; k < SPT; k++) {
+            const uint32_t m = meta[k];
+            const uint32_t role = m & 3u, g = (m >> 2) & 255u;
+            double cx = 0, cy = 0, cz = 0;
+            if (use_com) { const mixed4 c = scom[m >> 21]; cx = c.x; cy = c.y; cz = c.z; }
+            double val = 0.0;
+            if (role == ROLE_NORMAL) {
+                if (v[k].w != 0) {                               // K :161-168
+                    const double rx = v[k].x - cx, ry = v[k].y - cy, rz = v[k].z - cz;
+                    val = (rx * rx + ry * ry + rz * rz) * (double)mass[k];
+                }
+            } else if (role == ROLE_DRUDE) {                     // K :171-186 (one lane per pair)
+                const int pl = k * TBLOCK + tid + (int)((m >> 10) & 2047u) - 1024;
+                const mixed4 u = ld_img(sv, pl);
+                const double r1x = v[k].x - cx, r1y = v[k].y - cy, r1z = v[k].z - cz;
+                const double r2x = u.x - cx, r2y = u.y - cy, r2z = u.z - cz;
+                const double mass1 = mass[k], mass2 = u.w;               // image .w = mass
+                const double invTot = rcp_(mass1 + mass2);
+                const double m1f = invTot * mass1, m2f = invTot * mass2;
+                const double cmx = r1x * m1f + r2x * m2f, cmy = r1y * m1f + r2y * m2f, cmz = r1z * m1f + r2z * m2f;
+                const double rlx = r2x - r1x, rly = r2y - r1y, rlz = r2z - r1z;
+                val = (cmx * cmx + cmy * cmy + cmz * cmz) * (mass1 + mass2);
+                ke_drude += (rlx * rlx + rly * rly + rlz * rlz) * (mass1 * mass2 * invTot);   // reduced mass = 1/invReducedMass (K :178, :185)
+            }
+            if constexpr (GB > 0) {
+#pragma unroll
+                for (int b = 0; b < GB; b++) ke_g[b] += (g == (uint32_t)b) ? val : 0.0;
+            } else {
+                // one pass per distinct group present in this wavefront (usually 1-3): butterfly-sum the lanes of
+                // that group, lane 0 adds the sum to the wave's LDS bin.  The order depends on the data only.
+                const bool has = role == ROLE_DRUDE || (role == ROLE_NORMAL && v[k].w != 0);
+                unsigned long long rem = __ballot(has);
+                while (rem) {
+                    const int src = __ffsll((long long)rem) - 1;
+                    const uint32_t g0 = __shfl(g, src, 64);
+                    const bool mine = has && g == g0;
+                    const double sg = wave_sum(mine ? val : 0.0);
+                    if ((tid & 63) == 0) wbins[g0] += sg;
+                    rem &= ~__ballot(mine);
+                }
+            }
+        }
+        lds_read = true;
+    }
+    if (lds_read) __syncthreads();       // LDS image is reused by the next tile
+}
 
 }  // namespace tgnh
 #endif

@@ -114,7 +114,7 @@ def _wave_tile_system(name):
 @pytest.mark.parametrize("name", ["testwater", "water", "nacl", "il", "mixed", "pnm"] + [f"ragged{k}" for k in range(8)])
 def test_every_access_of_the_wave_tile_kernels_stays_inside_its_buffers(name, mode, com):
     """What wke_kernel / wstep_kernel touch, re-derived on the CPU from the tables a handle hands its launches
-    (wave_load, load_vf, work / prepare / finish in tgnh_kernels.hip; launch sizes in tgnh_step.cpp):
+    (wave_load, load_vf, work / prepare / finish in tgnh_wave_kernels.h and tgnh_wave_device.h; launch sizes in tgnh_step.cpp):
 
       global   slot ws + lane for lane < n of every wave tile: inside [0, N); the table has num_wtiles + 1 entries, the last
                one N; velocities, index words and forces are read there and nowhere else;

@@ -39,7 +39,7 @@ def test_hot_kernels_keep_their_occupancy():
                 assert rows[f"wke_kernel<{prec},{ops},{gb}>"][0] <= 102, rows[f"wke_kernel<{prec},{ops},{gb}>"]
             assert rows[f"wstep_kernel<{prec},{gb},false>"][0] <= 128, rows[f"wstep_kernel<{prec},{gb},false>"]
             assert rows[f"wstep_kernel<{prec},{gb},true>"][0] <= 256, rows[f"wstep_kernel<{prec},{gb},true>"]
-            # ... and the occupancies the comments in tgnh_kernels.hip, DESIGN.md and profiles/ rely on, as the compiler reports
+            # ... and the occupancies the comments in tgnh_wave_kernels.h, DESIGN.md and profiles/ rely on, as the compiler reports
             # them (wavefronts per SIMD): wstep_kernel 4 = two 512-thread work-groups per compute unit = 512 work-groups = 262 144
             # slots resident at once on 256 CUs, whose LDS (images + pattern constants) must fit twice into a CU's 160 KiB;
             # the KE passes at >= 5

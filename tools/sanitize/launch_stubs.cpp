@@ -1,4 +1,4 @@
-// Host-only sanitizer build: the kernel launchers of tgnh_kernels.hip / tgnh_harness.hip replaced by stubs that
+// Host-only sanitizer build: the kernel launchers of the .hip units replaced by stubs that
 // fail, so that the host units (csrc/tgnh_*.cpp: topology, tiles, dof, orchestration) can be compiled with g++ -fsanitize and
 // exercised through host-only handles (device -1) on a machine without a GPU.  Nothing here ships.
 #include "../../openmm_drudenose_amd/csrc/tgnh_internal.h"
