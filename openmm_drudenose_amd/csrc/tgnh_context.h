@@ -130,6 +130,7 @@ struct tgnh_context {
             return end_pending | scale_pending << 1 | kick_pending << 2 | first_half_done << 3 | chain_pending << 4 | sum_pending << 5 |
                    xwait_pending << 6 | stage_pending << 7 | ke_carry << 9;
         }
+        void chain_owed(bool twice) { chain_pending = true; chain_pending_twice = twice; }           // (whoever leaves it says what else the rescale launch does: sum_pending, xwait_pending, carry_pending)
         void chain_ran() { chain_pending = sum_pending = xwait_pending = carry_pending = false; }     // (whoever ran it says where the block now lies: stage_pending)
         void velocities_current() { scale_pending = kick_pending = false; }
         void end_half_deferred(bool kick) { scale_pending = first_half_done = true; kick_pending = kick; }   // DEFER_SCALE: both chain halves are in scale[], velm lags

@@ -27,6 +27,9 @@ inline tgnh_status fail(tgnh_status code, const std::string& msg) {
 #define HIP_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(TGNH_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 #define CHECK_H(h) do { if (!(h)) return fail(TGNH_ERR_ARG, "null handle"); } while (0)
 
+// what a description says about its handle, for every unit that asks
+inline bool com_thermostat_on(const tgnh_desc& d) { return d.mode == TGNH_MODE_TGNH && d.use_com_temp_group; }
+inline int pass_kind(const tgnh_desc& d) { return (d.flags & TGNH_FLAG_DEFER_SCALE) ? 0 : 1; }   // step_kernel's kind of the pass structure: 0 a whole deferred step, 1 the reference's halves
 // tgnh_topology.cpp
 void make_layout(tgnh_context* c);
 tgnh_status build_topology(tgnh_context* c, const tgnh_desc* d);
@@ -38,6 +41,7 @@ tgnh_status deferred_guard(tgnh_handle h, const char* what);
 void note_status(tgnh_handle h, uint32_t flags);
 tgnh_status entry(tgnh_handle h, bool need_bufs);
 bool resident_now(tgnh_handle h);
+tgnh_status allreduce_hook(tgnh_handle h, hipStream_t s);      // the hook, if one is set, on the summed kinetic energies
 tgnh_status run_tile(tgnh_handle h, int ops, int kid, hipStream_t s, const double* scale = nullptr);
 GatherArgs gather_args(tgnh_handle h, const double* scale);
 ChainArgs chain_args(tgnh_handle h);

@@ -65,7 +65,7 @@ static tgnh_status decide_policy(tgnh_context* c, const tgnh_desc* d, bool long_
     {   // s^2 KE is the exact post-rescale KE only if no molecule spans two temperature groups: v_rel = v - v_com of such a
         // molecule is scaled by two different factors, which moves its centre of mass (K :260-300)
         bool inside = true;
-        if (d->mode == TGNH_MODE_TGNH && d->use_com_temp_group) {
+        if (com_thermostat_on(*d)) {
             std::vector<int> g0(d->num_residues, -1);      // (by particle, not by (first, count): a residue may come in several runs)
             for (int i = 0; i < d->num_particles && inside; i++) {
                 if (c->topo.mass[i] == 0.0) continue;
@@ -169,7 +169,7 @@ template <typename Launch> static tgnh_status census(tgnh_context* c, int per_cu
 static tgnh_status resident_census(tgnh_context* c) {
     if (!(c->d.flags & TGNH_FLAG_RESIDENT_STEP) || c->cfg.gb == 0 || !c->cfg.inline_chain || c->thermo.L.NT > CHAIN_INLINE_SUM_NT) return TGNH_OK;
     // (the kind with the largest footprint this handle will launch: a whole deferred step, or the plain begin half)
-    const int kind = (c->d.flags & TGNH_FLAG_DEFER_SCALE) ? 0 : 1;
+    const int kind = pass_kind(c->d);
     const size_t lds = tile_lds_bytes(c->d.precision, step_kind_ops2(kind), true, true);
     // (step_kernel runs one-link chains only; longer ones have wstep_kernel below, or the launches)
     tgnh_status rc = census(c, c->thermo.L.C == 1 ? step_blocks_per_cu(c->d.precision, c->cfg.gb, kind, lds) : 0,

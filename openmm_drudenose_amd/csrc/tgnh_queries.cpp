@@ -170,8 +170,7 @@ extern "C" tgnh_status tgnh_compute_kinetic_energies(tgnh_handle h, void* stream
         if (h->xchg.on) { a.x_send = 1; a.x_wait = 1; }
         if (!h->owed.tail_summed) HIP_OK(launch_chain(a, s));       // (summed by the KE launch itself where the step's own KE launch is: the same bits)
         h->owed.tail_summed = false;
-        if (!h->xchg.on && h->xchg.allreduce && h->xchg.allreduce(h->thermo.d_state + h->thermo.L.off_ke_red, h->thermo.L.NT, (void*)s, h->xchg.allreduce_user) != 0)
-            return fail(TGNH_ERR_HIP, "all-reduce hook failed");
+        if (!h->xchg.on) { rc = allreduce_hook(h, s); if (rc) return rc; }
     }
     HIP_OK(hipMemcpyAsync(h->thermo.d_state + h->thermo.L.off_ke, h->thermo.d_state + h->thermo.L.off_ke_red, sizeof(double) * h->thermo.L.NT,
                           hipMemcpyDeviceToDevice, s));

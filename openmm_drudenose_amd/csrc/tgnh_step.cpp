@@ -1,4 +1,4 @@
-// tgnh_step.cpp -- step orchestration (A11): device-reported failures, launch sizing, run_tile / run_gather / run_chain / run_resident, tgnh_step_*, flush, clock
+// tgnh_step.cpp -- step orchestration (A11): device-reported failures, the launch decisions by name, launch sizing, run_tile / run_gather / run_chain / run_resident, tgnh_step_*, flush, clock
 #include "tgnh_host.h"
 
 // ---------------------------------------------------------------------------
@@ -44,22 +44,48 @@ static tgnh_status need_buffers(tgnh_handle h) {
     return TGNH_OK;
 }
 
-static TileArgs tile_args(tgnh_handle h, const double* scale) {
-    TileArgs a{};
+// ---- what the handle's configuration decides, each fact once ----
+// The next rescale launch sums `rows` partial rows in its prologue and runs the chain itself: nothing is launched between a KE
+// pass and it.  Asked by both who-sums-the-rows decisions: the KE launch's tail sum (ke_pass_prologue) and run_chain.
+static bool rescale_sums_rows(tgnh_handle h, int rows) {
+    return h->cfg.inline_chain && !h->xchg.on && !h->xchg.allreduce && h->thermo.L.NT <= CHAIN_INLINE_SUM_NT &&
+           (rows + h->topo.num_big <= h->cfg.inline_sum_rows || h->cfg.inline_sum_all);
+}
+// After this end half the stored velocities have the bins ke_post, until somebody writes velocities (unsharded only: a rank that
+// recomputes while its peers carry over would enter a collective alone)
+static bool ke_carries(tgnh_handle h) { return h->cfg.carry_ok && !h->xchg.allreduce && !h->xchg.on; }
+// molecules longer than a tile whose centre-of-mass velocities the rescale launches read from a table (run_big_com)
+static bool big_com_on(tgnh_handle h) { return h->topo.num_big && com_thermostat_on(h->d); }
+tgnh_status allreduce_hook(tgnh_handle h, hipStream_t s) {
+    if (h->xchg.allreduce && h->xchg.allreduce(h->thermo.d_state + h->thermo.L.off_ke_red, h->thermo.L.NT, (void*)s, h->xchg.allreduce_user) != 0)
+        return fail(TGNH_ERR_HIP, "all-reduce hook failed");
+    return TGNH_OK;
+}
+static tgnh_status timed_chain(tgnh_handle h, const ChainArgs& a, hipStream_t s) { Timed t(h, s, KID_CHAIN); HIP_OK(launch_chain(a, s)); return TGNH_OK; }
+
+// the fields TileArgs and GatherArgs share by name
+template <typename Args> static Args common_args(tgnh_handle h, const double* scale) {
+    Args a{};
     a.posq = h->bound.posq; a.posq_corr = h->bound.posq_corr; a.velm = h->bound.velm;
     a.force = reinterpret_cast<const long long*>(h->bound.force); a.pos_delta = h->bound.pos_delta;
-    a.meta = h->topo.d_meta; a.tile_start = h->topo.d_tile_start; a.tile_res = h->topo.d_tile_res; a.res_table = h->topo.d_res_table;
-    a.big_com = h->topo.d_big_com;
     a.scale = scale ? scale : h->thermo.d_state + h->thermo.L.off_scale;
     a.partials = h->thermo.d_partials; a.status = h->status.d_word;
-    a.num_tiles = h->topo.num_tiles; a.padded = h->d.padded_num_particles; a.num_groups = h->thermo.L.G;
-    a.reverse = h->run.sweep_reverse;
-    a.wave_tile = h->topo.d_wave_tile; a.wmeta = h->topo.d_wmeta; a.num_wtiles = h->topo.num_wtiles;
-    a.tile_pat = h->topo.d_tile_pat; a.pattern = h->topo.d_pattern; a.wpattern = h->topo.d_wpattern;
-    a.use_com = (h->d.mode == TGNH_MODE_TGNH && h->d.use_com_temp_group) ? 1 : 0;
+    a.padded = h->d.padded_num_particles;
+    a.use_com = com_thermostat_on(h->d) ? 1 : 0;
     a.hardwall = h->d.max_drude_distance > 0 ? 1 : 0;                         // Ref :299, Cu :372
     a.dt = h->d.step_size; a.max_dist = h->d.max_drude_distance;
     a.hw_scale = std::sqrt(h->d.kB * h->d.drude_temperature);                 // Ref :300, Cu :299
+    return a;
+}
+
+static TileArgs tile_args(tgnh_handle h, const double* scale) {
+    TileArgs a = common_args<TileArgs>(h, scale);
+    a.meta = h->topo.d_meta; a.tile_start = h->topo.d_tile_start; a.tile_res = h->topo.d_tile_res; a.res_table = h->topo.d_res_table;
+    a.big_com = h->topo.d_big_com;
+    a.num_tiles = h->topo.num_tiles; a.num_groups = h->thermo.L.G;
+    a.reverse = h->run.sweep_reverse;
+    a.wave_tile = h->topo.d_wave_tile; a.wmeta = h->topo.d_wmeta; a.num_wtiles = h->topo.num_wtiles;
+    a.tile_pat = h->topo.d_tile_pat; a.pattern = h->topo.d_pattern; a.wpattern = h->topo.d_wpattern;
     return a;
 }
 
@@ -152,21 +178,13 @@ static tgnh_status run_big_com(tgnh_handle h, bool kick, hipStream_t s) {
 
 // ---- the gather path (tgnh_gather.hip): the same operation masks, by global index ----
 GatherArgs gather_args(tgnh_handle h, const double* scale) {
-    GatherArgs a{};
-    a.posq = h->bound.posq; a.posq_corr = h->bound.posq_corr; a.velm = h->bound.velm;
-    a.force = reinterpret_cast<const long long*>(h->bound.force); a.pos_delta = h->bound.pos_delta;
+    GatherArgs a = common_args<GatherArgs>(h, scale);
     a.group = h->gather.d_group; a.resid = h->gather.d_resid;
     a.res_table = h->gather.d_res_table; a.partner = h->gather.d_partner; a.com = h->gather.d_com;
-    a.scale = scale ? scale : h->thermo.d_state + h->thermo.L.off_scale;
-    a.partials = h->thermo.d_partials; a.status = h->status.d_word;
-    a.n = h->d.num_particles; a.padded = h->d.padded_num_particles;
+    a.n = h->d.num_particles;
     a.com_lanes = h->gather.com_lanes;
-    a.use_com = (h->d.mode == TGNH_MODE_TGNH && h->d.use_com_temp_group) ? 1 : 0;
     a.n_res = a.use_com ? (int)h->gather.res_table.size() : 0;
     a.G = h->thermo.L.G; a.NT = h->thermo.L.NT;
-    a.hardwall = h->d.max_drude_distance > 0 ? 1 : 0;                         // Ref :299, Cu :372
-    a.dt = h->d.step_size; a.max_dist = h->d.max_drude_distance;
-    a.hw_scale = std::sqrt(h->d.kB * h->d.drude_temperature);                 // Ref :300, Cu :299
     return a;
 }
 
@@ -207,67 +225,71 @@ tgnh_status run_chain_gather(tgnh_handle h, hipStream_t s, bool sum_only) {
     ChainArgs a = chain_args(h);
     Timed t(h, s, KID_CHAIN);
     HIP_OK(launch_gather_rowsum(h->thermo.d_partials, h->run.ke_parts, h->thermo.L.NT, h->thermo.d_state + h->thermo.L.off_ke_red, s));
-    if (h->xchg.allreduce && h->xchg.allreduce(h->thermo.d_state + h->thermo.L.off_ke_red, h->thermo.L.NT, (void*)s, h->xchg.allreduce_user) != 0)
-        return fail(TGNH_ERR_HIP, "all-reduce hook failed");
+    { tgnh_status rc = allreduce_hook(h, s); if (rc) return rc; }
     if (!sum_only) HIP_OK(launch_gather_chain(a, h->gather.d_scratch, s));
     return TGNH_OK;
 }
 
+// run_tile, part 1.  A rescale launch that finds a chain waiting runs it itself: its chain wavefronts read the thermostat block
+// st_in, work-group 0 leaves the advanced one in st_out: d_state -> d_stage, for whoever comes next to commit.  A carried chain
+// (no KE pass before it: nothing has committed the staged block on the way) reads the thermostat where the last in-kernel chain
+// left it and writes the other copy: the two blocks differ only in what a chain writes, and a chain writes all of that every time
+// (eta, etaDot, etaDotDot, KE before / after, the scale factors, KESum)
+static tgnh_status adopt_chain(tgnh_handle h, TileArgs& a, hipStream_t s) {
+    const bool pingpong = h->owed.carry_pending && h->owed.stage_pending;
+    if (h->owed.stage_pending && !pingpong) { tgnh_status rc = commit_stage(h, s); if (rc) return rc; }
+    a.chain_on = 1;
+    a.chain = chain_args(h);                                    // (takes note of the staged block: cleared there)
+    a.chain.chain_twice = h->owed.chain_pending_twice ? 1 : 0;
+    a.chain.ke_carry = h->owed.carry_pending ? 1 : 0;
+    a.sum_rows = h->owed.sum_pending ? (h->run.ke_parts + h->topo.num_big <= h->cfg.inline_sum_rows ? 1 : 2) : 0;
+    a.x_wait = h->owed.xwait_pending ? 1 : 0;
+    a.st_in = pingpong ? h->thermo.d_stage : h->thermo.d_state;
+    a.st_out = pingpong ? h->thermo.d_state : h->thermo.d_stage;
+    return TGNH_OK;
+}
+
+// run_tile, part 2.  What a KE pass of `grid` work-groups does besides reducing: it commits a staged thermostat block on the
+// way; on wave tiles its work-group 0 sums the rows where a launch that only did that would follow (an all-reduce waits for the
+// sums, or the next rescale launch does not sum them); the COM velocities of the big molecules are tabulated first, for the
+// velocities this launch reduces: the current ones, or the kicked ones (the kick is linear, so sum m v' = sum (m v + dt/2 F)
+// needs no second pass).  The rescale launches that follow reuse the table: velocities do not change between a KE pass and its rescale.
+static tgnh_status ke_pass_prologue(tgnh_handle h, TileArgs& a, int ops, bool wave, int grid, hipStream_t s) {
+    if (h->owed.stage_pending && !a.chain_on) {
+        a.commit_len = h->thermo.L.total; a.commit_src = h->thermo.d_stage; a.commit_dst = h->thermo.d_state;
+        a.commit_skip = h->thermo.L.off_ke_red; a.commit_skip_n = h->thermo.L.NT;
+        h->owed.stage_pending = false;
+    }
+    h->owed.tail_summed = wave && h->meet.d_rows && !h->xchg.on && h->thermo.L.NT <= CHAIN_INLINE_SUM_NT && !rescale_sums_rows(h, grid);
+    if (h->owed.tail_summed) { a.tail_sum = 1; a.rows = h->meet.d_rows; a.sync = h->meet.d_sync; a.ke_red = h->thermo.d_state + h->thermo.L.off_ke_red; }
+    h->run.ke_parts = grid;
+    return big_com_on(h) ? run_big_com(h, (ops & OP_KICK) != 0, s) : TGNH_OK;
+}
+
+// run_tile, part 3: the launch, its sizes checked first
+static tgnh_status launch_pass(tgnh_handle h, int ops, int kid, const TileArgs& a, bool wave, int grid, size_t lds, hipStream_t s) {
+    tgnh_status rc = check_launch(h, a, grid, TBLOCK, wave, a.tail_sum != 0); if (rc) return rc;
+    Timed t(h, s, kid);
+    if (wave) HIP_OK(launch_wke(h->d.precision, ops, h->cfg.gb, a, grid, s));
+    else HIP_OK(launch_tile(h->d.precision, ops, h->cfg.gb, a, grid, lds, s));
+    return TGNH_OK;
+}
+
+// One streaming launch with the operation mask `ops` (scale != nullptr: these factors, and no chain is adopted)
 tgnh_status run_tile(tgnh_handle h, int ops, int kid, hipStream_t s, const double* scale) {
     if (h->gather.generic) return run_gather(h, ops, kid, s, scale);
+    tgnh_status rc;
     TileArgs a = tile_args(h, scale);
-    bool inline_chain = false;
-    bool pingpong = false;
-    if ((ops & OP_SCALE) && h->owed.chain_pending && !scale) {           // this rescale launch runs the chain itself
-        // A carried chain (no KE pass before it: nothing has committed the staged block on the way) reads the thermostat where the
-        // last in-kernel chain left it and writes the other copy: the two blocks differ only in what a chain writes, and a
-        // chain writes all of that every time (eta, etaDot, etaDotDot, KE before / after, the scale factors, KESum)
-        pingpong = h->owed.carry_pending && h->owed.stage_pending;
-        if (h->owed.stage_pending && !pingpong) { tgnh_status rc = commit_stage(h, s); if (rc) return rc; }
-        a.chain_on = 1;
-        a.chain = chain_args(h);                                    // (takes note of the staged block: cleared there)
-        a.chain.chain_twice = h->owed.chain_pending_twice ? 1 : 0;
-        a.chain.ke_carry = h->owed.carry_pending ? 1 : 0;
-        a.sum_rows = h->owed.sum_pending ? (h->run.ke_parts + h->topo.num_big <= h->cfg.inline_sum_rows ? 1 : 2) : 0;
-        a.x_wait = h->owed.xwait_pending ? 1 : 0;
-        a.st_in = pingpong ? h->thermo.d_stage : h->thermo.d_state;
-        a.st_out = pingpong ? h->thermo.d_state : h->thermo.d_stage;
-        inline_chain = true;
-    }
+    if ((ops & OP_SCALE) && h->owed.chain_pending && !scale) { rc = adopt_chain(h, a, s); if (rc) return rc; }
     if ((ops & (OP_POSDELTA | OP_MOVE)) && !h->bound.pos_delta) return fail(TGNH_ERR_STATE, "posDelta buffer not bound");
     size_t lds = tile_lds_bytes(h->d.precision, ops, a.hardwall != 0, a.use_com != 0);
     if ((ops & OP_KE) && h->cfg.gb == 0) lds += sizeof(double) * (TBLOCK / 64) * h->thermo.L.G;   // per-wave group bins
     // the pure KE passes (KE, kick+KE, kick+KE unstored) run over the wave tiles when the topology has them
     const bool wave = h->cfg.wave_ke && (ops & OP_KE) && !(ops & ~(OP_KE | OP_KICK | OP_NOSTORE));
     const int grid = wave ? wave_grid_for(h, ops) : grid_for(h, ops, a.hardwall != 0, lds);
-    if ((ops & OP_KE) && h->owed.stage_pending && !inline_chain) {      // commit the staged thermostat block on the way
-        a.commit_len = h->thermo.L.total; a.commit_src = h->thermo.d_stage; a.commit_dst = h->thermo.d_state;
-        a.commit_skip = h->thermo.L.off_ke_red; a.commit_skip_n = h->thermo.L.NT;
-        h->owed.stage_pending = false;
-    }
-    if (ops & OP_KE) {
-        // wave tiles: where a launch that only sums the partial rows would follow (an all-reduce waits for the sums, or the
-        // system is too large for the next rescale launch to sum them in its prologue), work-group 0 of this launch does it
-        h->owed.tail_summed = wave && h->meet.d_rows && !h->xchg.on && h->thermo.L.NT <= CHAIN_INLINE_SUM_NT &&
-                         !(h->cfg.inline_chain && !h->xchg.allreduce && (grid + h->topo.num_big <= h->cfg.inline_sum_rows || h->cfg.inline_sum_all));
-        if (h->owed.tail_summed) { a.tail_sum = 1; a.rows = h->meet.d_rows; a.sync = h->meet.d_sync; a.ke_red = h->thermo.d_state + h->thermo.L.off_ke_red; }
-        h->run.ke_parts = grid;
-        if (h->topo.num_big && a.use_com) {
-            // COM velocity of every big molecule for the velocities this launch reduces: the current ones, or the
-            // kicked ones (the kick is linear, so sum m v' = sum (m v + dt/2 F) needs no second pass).  The rescale
-            // launches that follow reuse the table: velocities do not change between a KE pass and its rescale.
-            tgnh_status rc = run_big_com(h, (ops & OP_KICK) != 0, s); if (rc) return rc;
-        }
-    }
-    { tgnh_status rc = check_launch(h, a, grid, TBLOCK, wave, a.tail_sum != 0); if (rc) return rc; }
-    {
-        Timed t(h, s, kid);
-        if (wave) HIP_OK(launch_wke(h->d.precision, ops, h->cfg.gb, a, grid, s));
-        else HIP_OK(launch_tile(h->d.precision, ops, h->cfg.gb, a, grid, lds, s));
-    }
-    if (inline_chain) {            // the advanced thermostat now lies in d_stage (carried from a staged block: back in d_state)
-        h->owed.chain_ran(); h->owed.stage_pending = !pingpong;
-    }
+    if (ops & OP_KE) { rc = ke_pass_prologue(h, a, ops, wave, grid, s); if (rc) return rc; }
+    rc = launch_pass(h, ops, kid, a, wave, grid, lds, s); if (rc) return rc;
+    if (a.chain_on) { h->owed.chain_ran(); h->owed.stage_pending = a.st_out == h->thermo.d_stage; }    // the advanced thermostat lies where the launch wrote it
     if (h->cfg.alternate_sweeps) h->run.sweep_reverse ^= 1;      // the next streaming launch starts where this one ends
     return TGNH_OK;
 }
@@ -281,7 +303,6 @@ ChainArgs chain_args(tgnh_handle h) {
     a.realkbT = h->thermo.realkbT; a.drudekbT = h->thermo.drudekbT;
     // chains of 5-16 links: chain_long_kernel<C>, the links in registers (round 3 ran them a link per lane, chain_lanes_run: kept
     // behind a switch for the comparison in profiles/r04_chain_cost.md)
-    a.lanes = 0;
 #ifdef TGNH_TUNING
     if (const char* e = getenv("TGNH_CHAIN_LANES")) a.lanes = e[0] != '0';
 #endif
@@ -302,57 +323,45 @@ static tgnh_status commit_stage(tgnh_handle h, hipStream_t s) {
     return TGNH_OK;
 }
 
-// sum the work-group partials, all-reduce across ranks when sharded, run the chain
+// Between a KE pass and the rescale that uses its factors: sum the work-group partials, exchange the sums across ranks when
+// sharded, run the chain.  Three answers, settled first, say what of that is launched here:
+//   who sums the rows     the KE launch's tail sum did (ke_pass_prologue) | a launch now | the next rescale launch (rescale_sums_rows)
+//   which exchange        none | the hook, after the sums | the mailboxes: the row-sum launch sends, whoever runs the chain waits
+//   where the chain runs  in a launch now | inside the next rescale launch (cfg.inline_chain: 1-4 links)
+//   handle                                rows              exchange    chain
+//   1-4 links, unsharded, <= 8 groups     next rescale      none        next rescale      (nothing launched: 3 launches per step)
+//   1-4 links, unsharded, more groups     tail sum | now    none        next rescale
+//   1-4 links, hook                       tail sum | now    hook        next rescale
+//   1-4 links, mailboxes                  now               mailboxes   next rescale
+//   5+ links, unsharded                   tail sum | now    none        now, in the row-sum launch (one launch also after a tail sum)
+//   5+ links, hook                        tail sum | now    hook        now, in a launch of its own behind the hook
+//   5+ links, mailboxes                   now               mailboxes   now, in the row-sum launch
+// (After a tail sum ke_red is complete, and nothing is staged: a KE launch commits.  The gather path's own chain: run_chain_gather.)
+// Where the rescale launch sums: up to 256 rows its chain wavefront reads them alone (one batch of loads); more rows are read by
+// all four wavefronts, a quarter each, ahead of their tile loads (read by one wavefront they were a chain of L2 misses on the
+// critical path, +7-9 us) -- that up to 2 M slots (inline_sum_all).  +4 % steps/s at 625 k slots, +7-17 % for small systems
+// (profiles/r01_tuning_sweep.log).
 static tgnh_status run_chain(tgnh_handle h, hipStream_t s, bool twice) {
     if (h->gather.chain) return run_chain_gather(h, s, false);
+    const bool sum_next = rescale_sums_rows(h, h->run.ke_parts), sum_now = !sum_next && !h->owed.tail_summed;
+    const bool mailbox = h->xchg.on, hook = !mailbox && h->xchg.allreduce;
+    const bool chain_next = h->cfg.inline_chain;                                  // (sum_next implies it)
+    const bool chain_with_sum = !chain_next && !hook, chain_alone = !chain_next && hook;
+    h->owed.tail_summed = false;
+    tgnh_status rc;
     ChainArgs a = chain_args(h);
     a.chain_twice = twice ? 1 : 0;
-    if (h->xchg.on) {                // sharded, mailbox exchange: the sum launch sends; whoever runs the chain waits
-        a.do_sum = 1; a.x_send = 1;
-        if (h->cfg.inline_chain) {
-            a.do_chain = 0;
-            { Timed t(h, s, KID_CHAIN); HIP_OK(launch_chain(a, s)); }
-            h->owed.chain_pending = true; h->owed.chain_pending_twice = twice; h->owed.xwait_pending = true;
-        } else {
-            a.do_chain = 1; a.x_wait = 1;
-            Timed t(h, s, KID_CHAIN);
-            HIP_OK(launch_chain(a, s));
-        }
-        return TGNH_OK;
+    if (sum_now || chain_with_sum) {
+        a.do_sum = sum_now ? 1 : 0; a.x_send = mailbox ? 1 : 0;
+        a.do_chain = chain_with_sum ? 1 : 0; a.x_wait = mailbox && chain_with_sum ? 1 : 0;
+        rc = timed_chain(h, a, s); if (rc) return rc;
     }
-    if (h->cfg.inline_chain && !h->xchg.allreduce && h->thermo.L.NT <= CHAIN_INLINE_SUM_NT &&
-        (h->run.ke_parts + h->topo.num_big <= h->cfg.inline_sum_rows || h->cfg.inline_sum_all)) {
-        // Unsharded, one-link chains, G <= 8: nothing to launch -- the next rescale launch sums the partial rows and
-        // runs the chain in its prologue (3 launches per step).  Up to 256 rows its chain wavefront reads them alone
-        // (one batch of loads); more rows are read by all four wavefronts, a quarter each, ahead of their tile
-        // loads (read by one wavefront they were a chain of L2 misses on the critical path, +7-9 us) -- that up to 2 M
-        // slots (inline_sum_all).  +4 % steps/s at 625 k slots, +7-17 % for small systems
-        // (profiles/r01_tuning_sweep.log).
-        h->owed.chain_pending = true; h->owed.sum_pending = true; h->owed.chain_pending_twice = twice;
-        return TGNH_OK;
-    }
-    const bool summed = h->owed.tail_summed;       // wke_kernel's tail sum: ke_red is complete, no row-sum launch (and nothing staged: a KE launch commits)
-    h->owed.tail_summed = false;
-    if (h->cfg.inline_chain) {           // sum (and all-reduce) now, the chain itself inside the next rescale launch
-        a.do_sum = 1; a.do_chain = 0;
-        if (!summed) { Timed t(h, s, KID_CHAIN); HIP_OK(launch_chain(a, s)); }
-        if (h->xchg.allreduce && h->xchg.allreduce(h->thermo.d_state + h->thermo.L.off_ke_red, h->thermo.L.NT, (void*)s, h->xchg.allreduce_user) != 0)
-            return fail(TGNH_ERR_HIP, "all-reduce hook failed");
-        h->owed.chain_pending = true; h->owed.chain_pending_twice = twice;
-        return TGNH_OK;
-    }
-    if (h->xchg.allreduce) {
-        a.do_sum = 1; a.do_chain = 0;
-        if (!summed) { Timed t(h, s, KID_CHAIN); HIP_OK(launch_chain(a, s)); }
-        if (h->xchg.allreduce(h->thermo.d_state + h->thermo.L.off_ke_red, h->thermo.L.NT, (void*)s, h->xchg.allreduce_user) != 0)
-            return fail(TGNH_ERR_HIP, "all-reduce hook failed");
+    if (hook) { rc = allreduce_hook(h, s); if (rc) return rc; }
+    if (chain_alone) {
         a.do_sum = 0; a.do_chain = 1; a.commit = 0;
-        { Timed t(h, s, KID_CHAIN); HIP_OK(launch_chain(a, s)); }
-    } else {
-        a.do_sum = summed ? 0 : 1; a.do_chain = 1;
-        Timed t(h, s, KID_CHAIN);
-        HIP_OK(launch_chain(a, s));
+        rc = timed_chain(h, a, s); if (rc) return rc;
     }
+    if (chain_next) { h->owed.chain_owed(twice); h->owed.sum_pending |= sum_next; h->owed.xwait_pending |= mailbox; }
     return TGNH_OK;
 }
 
@@ -364,7 +373,7 @@ tgnh_status materialize_chain(tgnh_handle h, hipStream_t s) {
     a.do_sum = h->owed.sum_pending ? 1 : 0; a.do_chain = 1; a.chain_twice = h->owed.chain_pending_twice ? 1 : 0;
     a.x_wait = h->owed.xwait_pending ? 1 : 0;
     a.ke_carry = h->owed.carry_pending ? 1 : 0;
-    { Timed t(h, s, KID_CHAIN); HIP_OK(launch_chain(a, s)); }
+    { tgnh_status rc = timed_chain(h, a, s); if (rc) return rc; }
     h->owed.chain_ran();
     return TGNH_OK;
 }
@@ -372,15 +381,14 @@ tgnh_status materialize_chain(tgnh_handle h, hipStream_t s) {
 // ---- TGNH_FLAG_RESIDENT_STEP: one launch per time step (step_kernel) ----
 // Eligible: deferred pass structure, one-link chains (the chain runs inside the launch), at most 8 temperature groups,
 // and an exchange the kernel can do itself (none, or the mailboxes -- a collective hook is a launch of its own).
-static bool resident_kind(tgnh_handle h, int kind) {
+// -> 0: none (the launches), 1: step_kernel, 2: wstep_kernel
+static int resident_kernel(tgnh_handle h, int kind) {
     if (!((h->d.flags & TGNH_FLAG_RESIDENT_STEP) && h->cfg.inline_chain && h->cfg.gb != 0 && h->thermo.L.NT <= CHAIN_INLINE_SUM_NT &&
-          (h->xchg.on || !h->xchg.allreduce))) return false;
-    if (kind == 0 && h->cfg.wresident_per_cu > 0) return true;           // wstep_kernel: a whole deferred step, chains of 1-4 links
-    return h->cfg.resident_per_cu > 0 && h->thermo.L.C == 1;                    // step_kernel: every kind, one-link chains
+          (h->xchg.on || !h->xchg.allreduce))) return 0;
+    if (kind == 0 && h->cfg.wresident_per_cu > 0) return 2;              // wstep_kernel: a whole deferred step over wave tiles, chains of 1-4 links
+    return h->cfg.resident_per_cu > 0 && h->thermo.L.C == 1 ? 1 : 0;           // step_kernel: every kind, one-link chains
 }
-bool resident_now(tgnh_handle h) {
-    return resident_kind(h, (h->d.flags & TGNH_FLAG_DEFER_SCALE) ? 0 : 1);
-}
+bool resident_now(tgnh_handle h) { return resident_kernel(h, pass_kind(h->d)) != 0; }
 
 extern "C" tgnh_status tgnh_get_step_path(tgnh_handle h, int* gather, const char** reason) {
     CHECK_H(h);
@@ -392,8 +400,7 @@ extern "C" tgnh_status tgnh_get_step_path(tgnh_handle h, int* gather, const char
 extern "C" tgnh_status tgnh_get_resident_kernel(tgnh_handle h, int* which) {
     CHECK_H(h);
     if (!which) return fail(TGNH_ERR_ARG, "null out");
-    const int kind = (h->d.flags & TGNH_FLAG_DEFER_SCALE) ? 0 : 1;
-    *which = !resident_kind(h, kind) ? 0 : (kind == 0 && h->cfg.wresident_per_cu > 0) ? 2 : 1;
+    *which = resident_kernel(h, pass_kind(h->d));
     return TGNH_OK;
 }
 
@@ -406,8 +413,9 @@ static tgnh_status run_resident(tgnh_handle h, hipStream_t s, int kind) {
     if ((ops2 & OP_POSDELTA) && !h->bound.pos_delta) return fail(TGNH_ERR_STATE, "posDelta buffer not bound");
     const bool hw = a.hardwall != 0 && (ops2 & (OP_DRIFT | OP_MOVE));
     const size_t lds = tile_lds_bytes(h->d.precision, ops2, hw, a.use_com != 0);
+    const bool wstep = resident_kernel(h, kind) == 2;
     int& grid = h->cfg.resident_grid[kind][hw ? 1 : 0];
-    if (grid == 0 && !(kind == 0 && h->cfg.wresident_per_cu > 0)) {       // the work-groups that are resident at once (counted at create; never more than this kind's own occupancy)
+    if (grid == 0 && !wstep) {       // the work-groups that are resident at once (counted at create; never more than this kind's own occupancy)
         int per_cu = std::min(h->cfg.resident_per_cu, step_blocks_per_cu(h->d.precision, h->cfg.gb, kind, lds));
         if (per_cu < 1) return fail(TGNH_ERR_HIP, "step_kernel: occupancy query failed");
         grid = std::max(1, std::min(std::min(h->topo.num_tiles, per_cu * h->cfg.num_cus / h->cfg.resident_share), GRID_CAP));
@@ -415,27 +423,23 @@ static tgnh_status run_resident(tgnh_handle h, hipStream_t s, int kind) {
     a.chain_on = 1;
     a.chain = chain_args(h);
     a.chain.chain_twice = kind == 0 ? 1 : 0;
-    a.chain.nparts = grid;
     a.x_wait = 1;
     if (!h->xchg.on) a.chain.x = h->meet.self_x;            // unsharded: the private one-rank mailbox
     a.st_in = h->thermo.d_state; a.st_out = h->thermo.d_state;       // advanced in place by work-group 0 after everybody has read it
     a.sync = h->meet.d_sync; a.rows = h->meet.d_rows;
-    if (h->topo.num_big && a.use_com) { tgnh_status rc = run_big_com(h, kind == 0 || kind == 2, s); if (rc) return rc; }
-    if (kind == 0 && h->cfg.wresident_per_cu > 0) {            // a whole deferred step over wave tiles (wstep_kernel)
-        if (h->cfg.wresident_grid == 0) {
-            const int need = (h->topo.num_wtiles + WBLOCK / 64 - 1) / (WBLOCK / 64);
-            h->cfg.wresident_grid = std::max(1, std::min(std::min(need, h->cfg.wresident_per_cu * h->cfg.num_cus / h->cfg.resident_share), GRID_CAP));
-        }
-        a.chain.nparts = h->cfg.wresident_grid;
-        h->run.ke_parts = h->cfg.wresident_grid;
-        { tgnh_status rc = check_launch(h, a, h->cfg.wresident_grid, WBLOCK, true, true); if (rc) return rc; }
+    if (big_com_on(h)) { tgnh_status rc = run_big_com(h, kind == 0 || kind == 2, s); if (rc) return rc; }
+    if (wstep && h->cfg.wresident_grid == 0) {                 // a whole deferred step over wave tiles (wstep_kernel)
+        const int need = (h->topo.num_wtiles + WBLOCK / 64 - 1) / (WBLOCK / 64);
+        h->cfg.wresident_grid = std::max(1, std::min(std::min(need, h->cfg.wresident_per_cu * h->cfg.num_cus / h->cfg.resident_share), GRID_CAP));
+    }
+    const int g = wstep ? h->cfg.wresident_grid : grid;
+    a.chain.nparts = g;
+    h->run.ke_parts = g;
+    { tgnh_status rc = check_launch(h, a, g, wstep ? WBLOCK : TBLOCK, wstep, true); if (rc) return rc; }
+    {
         Timed t(h, s, KID_STEP);
-        HIP_OK(launch_wstep(h->d.precision, h->cfg.gb, h->thermo.L.C > 1, a, h->cfg.wresident_grid, s));
-    } else {
-        h->run.ke_parts = grid;
-        { tgnh_status rc = check_launch(h, a, grid, TBLOCK, false, true); if (rc) return rc; }
-        Timed t(h, s, KID_STEP);
-        HIP_OK(launch_step(h->d.precision, h->cfg.gb, kind, a, grid, lds, s));
+        if (wstep) HIP_OK(launch_wstep(h->d.precision, h->cfg.gb, h->thermo.L.C > 1, a, g, s));
+        else HIP_OK(launch_step(h->d.precision, h->cfg.gb, kind, a, g, lds, s));
     }
     // the first pass walked the tiles in direction sweep_reverse, the second one back: the next launch starts here
     h->owed.resident_settled();
@@ -450,20 +454,16 @@ static tgnh_status first_half(tgnh_handle h, hipStream_t s) {
         // of the stored velocities is s^2 times the bin that chain started from -- the ke_post it left (Cu :574 tracks exactly
         // that product) -- so this half's KE pass (Cu :474-488) and its row sum are not run: the chain starts from ke_post
         h->owed.ke_carry = false;
-        if (h->topo.num_big && h->d.mode == TGNH_MODE_TGNH && h->d.use_com_temp_group) {
-            // (molecules longer than a tile: the KE pass that is not run would have left their centre-of-mass velocities in
-            // the table the rescale launch reads -- the end half's rescale has changed them since)
-            tgnh_status rc = run_big_com(h, false, s); if (rc) return rc;
-        }
+        // (molecules longer than a tile: the KE pass that is not run would have left their centre-of-mass velocities in
+        // the table the rescale launch reads -- the end half's rescale has changed them since)
+        if (big_com_on(h)) { tgnh_status rc = run_big_com(h, false, s); if (rc) return rc; }
         if (h->cfg.inline_chain) {                            // ... inside the rescale launch that follows: this half step is ONE launch
-            h->owed.chain_pending = true; h->owed.chain_pending_twice = false; h->owed.sum_pending = false; h->owed.carry_pending = true;
+            h->owed.chain_owed(false); h->owed.sum_pending = false; h->owed.carry_pending = true;
             return TGNH_OK;
         }
         ChainArgs a = chain_args(h);
         a.do_sum = 0; a.do_chain = 1; a.ke_carry = 1;
-        Timed t(h, s, KID_CHAIN);
-        HIP_OK(launch_chain(a, s));
-        return TGNH_OK;
+        return timed_chain(h, a, s);
     }
     tgnh_status rc = run_tile(h, OP_KE, KID_KE, s); if (rc) return rc;
     return run_chain(h, s, false);
@@ -503,6 +503,11 @@ static tgnh_status poll_status_async(tgnh_handle h, hipStream_t s) {
 static void start_of_step(tgnh_handle h) {
     if (h->cfg.alternate_sweeps) h->run.sweep_reverse = (int)(h->run.step_count & 1);
 }
+// ... and the end of one                                                          Cu :405-406 ; Ref :413-414
+static tgnh_status advance_clock(tgnh_handle h, hipStream_t s) {
+    h->run.time += h->d.step_size; h->run.step_count += 1;
+    return poll_status_async(h, s);
+}
 
 extern "C" tgnh_status tgnh_step_begin(tgnh_handle h, void* stream) {
     tgnh_status rc = entry(h, true); if (rc) return rc;
@@ -529,43 +534,31 @@ static tgnh_status second_half(tgnh_handle h, hipStream_t s, int kick_ops) {
     if (!defer && resident_now(h)) {
         // reference pass structure: kick, KE, chain, rescale (Cu :384-402) in one launch; velocities are final when it ends
         rc = run_resident(h, s, kick_ops ? 2 : 4); if (rc) return rc;
-        h->owed.ke_carry = h->cfg.carry_ok && !h->xchg.allreduce && !h->xchg.on;
-        h->run.time += h->d.step_size;
-        h->run.step_count += 1;
-        return poll_status_async(h, s);
-    }
-    if (kick_ops && resident_now(h)) {
+        h->owed.ke_carry = ke_carries(h);
+    } else if (kick_ops && resident_now(h)) {
         // TGNH_FLAG_RESIDENT_STEP: nothing is launched here -- the next tgnh_step_begin runs this end half and its own
         // begin half in one launch (step_kernel); anything that needs the state earlier settles it the classic way
         h->owed.end_pending = true;
-        h->run.time += h->d.step_size;
-        h->run.step_count += 1;
-        return poll_status_async(h, s);
-    }
-    // DEFER_SCALE, fused path: the kicked velocities only feed the sums (Cu :384-388 + :474-488); the next step's first
-    // launch -- or tgnh_flush -- forms them again from the same force buffer and goes on from there.
-    // The reference's own structure, fused path (round 4): the same unstored kick+KE pass, and the rescale launch of THIS call forms
-    // the kicked velocities again before it rescales them (OP_PREKICK: the same expression on the same force buffer, the same
-    // bits) -- V r, F r | V r/w, F r = 144 B per slot where kick+KE with a store and a plain rescale move 152, and the read-only
-    // pass runs at 62 us where the storing one takes 87-92 (5 M slots).  velm holds the reference's end-of-step velocities when
-    // tgnh_step_end returns, as before.  (The split path's halves work on stored velocities around the constraint call-outs.)
-    const bool fold = !defer && kick_ops != 0 && !h->gather.generic;           // (the gather path stores its kick: K's own structure)
-    const int nostore = kick_ops && !h->gather.generic ? OP_NOSTORE : 0;
-    h->owed.end_folded = fold;
-    rc = run_tile(h, kick_ops | OP_KE | nostore, kick_ops ? KID_KICK_KE : KID_KE, s); if (rc) return rc;
-    if (defer) {
-        rc = run_chain(h, s, true); if (rc) return rc;
-        h->owed.end_half_deferred(nostore != 0);
     } else {
-        rc = run_chain(h, s, false); if (rc) return rc;                            // Cu :394-395
-        rc = run_tile(h, (fold ? OP_PREKICK : 0) | OP_SCALE, KID_SCALE, s); if (rc) return rc;   // Cu :402 (and :384-388 again, see above)
-        // the velocities now stored have the bins ke_post; they stay that until somebody writes velocities (unsharded only: a
-        // rank that recomputes while its peers carry over would enter a collective alone)
-        h->owed.ke_carry = h->cfg.carry_ok && !h->xchg.allreduce && !h->xchg.on;
+        // DEFER_SCALE, fused path: the kicked velocities only feed the sums (Cu :384-388 + :474-488); the next step's first
+        // launch -- or tgnh_flush -- forms them again from the same force buffer and goes on from there.
+        // The reference's own structure, fused path (round 4): the same unstored kick+KE pass, and the rescale launch of THIS call forms
+        // the kicked velocities again before it rescales them (OP_PREKICK: the same expression on the same force buffer, the same
+        // bits) -- V r, F r | V r/w, F r = 144 B per slot where kick+KE with a store and a plain rescale move 152, and the read-only
+        // pass runs at 62 us where the storing one takes 87-92 (5 M slots).  velm holds the reference's end-of-step velocities when
+        // tgnh_step_end returns, as before.  (The split path's halves work on stored velocities around the constraint call-outs.)
+        const bool fold = !defer && kick_ops != 0 && !h->gather.generic;           // (the gather path stores its kick: K's own structure)
+        const int nostore = kick_ops && !h->gather.generic ? OP_NOSTORE : 0;
+        h->owed.end_folded = fold;
+        rc = run_tile(h, kick_ops | OP_KE | nostore, kick_ops ? KID_KICK_KE : KID_KE, s); if (rc) return rc;
+        rc = run_chain(h, s, defer); if (rc) return rc;                                // Cu :394-395
+        if (defer) h->owed.end_half_deferred(nostore != 0);
+        else {
+            rc = run_tile(h, (fold ? OP_PREKICK : 0) | OP_SCALE, KID_SCALE, s); if (rc) return rc;   // Cu :402 (and :384-388 again, see above)
+            h->owed.ke_carry = ke_carries(h);
+        }
     }
-    h->run.time += h->d.step_size;                                                     // Cu :405-406 ; Ref :413-414
-    h->run.step_count += 1;
-    return poll_status_async(h, s);
+    return advance_clock(h, s);
 }
 
 extern "C" tgnh_status tgnh_step_end(tgnh_handle h, void* stream) {
@@ -589,10 +582,17 @@ tgnh_status settle_end(tgnh_handle h, hipStream_t s) {
     return TGNH_OK;
 }
 
-extern "C" tgnh_status tgnh_step_begin_kick(tgnh_handle h, void* stream) {
+// ... so every one of them begins like this.  fresh_ke: what it is about to do writes velocities or positions behind the
+// carried kinetic energies' back
+static tgnh_status split_entry(tgnh_handle h, hipStream_t s, bool fresh_ke) {
     tgnh_status rc = entry(h, true); if (rc) return rc;
+    if (fresh_ke) h->owed.ke_carry = false;
+    return settle_kick(h, s);
+}
+
+extern "C" tgnh_status tgnh_step_begin_kick(tgnh_handle h, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    rc = settle_kick(h, s); if (rc) return rc;
+    tgnh_status rc = split_entry(h, s, false); if (rc) return rc;
     start_of_step(h);
     if (!(h->d.flags & TGNH_FLAG_DEFER_SCALE) && resident_now(h) && !h->owed.ke_carry) return run_resident(h, s, 3);
     rc = first_half(h, s); if (rc) return rc;
@@ -601,15 +601,11 @@ extern "C" tgnh_status tgnh_step_begin_kick(tgnh_handle h, void* stream) {
     return TGNH_OK;
 }
 extern "C" tgnh_status tgnh_step_begin_move(tgnh_handle h, void* stream) {
-    tgnh_status rc = entry(h, true); if (rc) return rc;
-    h->owed.ke_carry = false;
-    rc = settle_kick(h, (hipStream_t)stream); if (rc) return rc;
+    tgnh_status rc = split_entry(h, (hipStream_t)stream, true); if (rc) return rc;
     return run_tile(h, OP_MOVE, KID_OTHER, (hipStream_t)stream);                   // Cu :366-376
 }
 extern "C" tgnh_status tgnh_step_end_kick(tgnh_handle h, void* stream) {
-    tgnh_status rc = entry(h, true); if (rc) return rc;
-    h->owed.ke_carry = false;
-    rc = settle_kick(h, (hipStream_t)stream); if (rc) return rc;
+    tgnh_status rc = split_entry(h, (hipStream_t)stream, true); if (rc) return rc;
     return run_tile(h, OP_KICK, KID_OTHER, (hipStream_t)stream);                   // Cu :384-388
 }
 extern "C" tgnh_status tgnh_step_end_thermo(tgnh_handle h, void* stream) {
@@ -631,9 +627,7 @@ tgnh_status flush_impl(tgnh_handle h, hipStream_t s) {
     } else {
         rc = run_tile(h, OP_KICK, KID_OTHER, s); if (rc) return rc;
     }
-    if (h->topo.num_big && h->d.mode == TGNH_MODE_TGNH && h->d.use_com_temp_group) {
-        rc = run_big_com(h, false, s); if (rc) return rc;             // the velocities just changed: refresh the COM table
-    }
+    if (big_com_on(h)) { rc = run_big_com(h, false, s); if (rc) return rc; }   // the velocities just changed: refresh the COM table
     h->owed.velocities_current();      // first_half_done stays
     return TGNH_OK;
 }

@@ -14,7 +14,7 @@ static tgnh_status build_gather_topology(tgnh_context* c, const std::vector<int>
                                          const std::vector<int>& res_order) {
     const tgnh_desc& d = c->d;
     const int N = d.num_particles;
-    const bool com = d.mode == TGNH_MODE_TGNH && d.use_com_temp_group;
+    const bool com = com_thermostat_on(d);
     c->topo.tile_start.assign(1, N); c->topo.tile_res.assign(1, 0); c->topo.num_tiles = 0;
     c->topo.res_entries.assign(1, make_int2(0, 0));
     c->topo.meta.clear(); c->topo.wave_tile.clear(); c->topo.wmeta.clear(); c->topo.num_wtiles = 0;
@@ -56,7 +56,7 @@ static tgnh_status build_gather_topology(tgnh_context* c, const std::vector<int>
 tgnh_status build_topology(tgnh_context* c, const tgnh_desc* d) {
     const int N = d->num_particles, P = d->num_pairs;
     const bool tg = d->mode == TGNH_MODE_TGNH;
-    const bool com = tg && d->use_com_temp_group;
+    const bool com = com_thermostat_on(*d);
     c->topo.mass.assign(d->mass, d->mass + N);
     c->topo.pair_drude.assign(d->pair_drude, d->pair_drude + P);
     c->topo.pair_parent.assign(d->pair_parent, d->pair_parent + P);

@@ -190,7 +190,7 @@ CASES = [
     ("polymer", "TGNH", 1, True, True, 0.0),              # molecule longer than a tile: COM from big_com_kernel
     ("polymer", "TGNH", 3, True, True, 0.0),
     ("polymer", "dualNH", 1, True, True, 0.0),
-    ("mixed", "TGNH", 10, True, True, 0.0),               # chains of 5-16 links: a link per lane (chain_lanes_run); 10 = the reference test's value
+    ("mixed", "TGNH", 10, True, True, 0.0),               # chains of 5-16 links: the links in registers (chain_long_kernel); 10 = the reference test's value
     ("mixed", "TGNH", 6, False, True, 0.02),              # ... the Drude thermostat's higher links frozen
     ("groups12", "TGNH", 7, True, True, 0.0),             # ... 14 thermostats: one batch of 16 rows
     ("groups32", "TGNH", 5, True, False, 0.0),            # ... 34 thermostats: three batches; COM thermostat inert (Q = 0)
@@ -248,7 +248,7 @@ TRUST_CASES = [
     # sysname, mode, chains, drude_chains, flags
     ("mixed", "TGNH", 1, True, TRUST),                        # the chain inside the rescale launch, reading the staged block where it lies
     ("mixed", "TGNH", 3, True, TRUST),                        # 2-4 links inside the rescale launch
-    ("mixed", "TGNH", 10, True, TRUST),                       # chain_kernel (a link per lane) started from the carried sums
+    ("mixed", "TGNH", 10, True, TRUST),                       # chain_long_kernel started from the carried sums
     ("water1000", "TGNH", 1, True, TRUST | FLAG_RESIDENT_STEP),   # the end half as one step_kernel launch, the begin half the tile launch
     ("il40", "dualNH", 1, False, TRUST),                      # the Reference platform's coupled one-link chain
     ("mixed", "dualNH", 3, True, TRUST),
