@@ -18,6 +18,7 @@ integ = DrudeTGNHIntegrator(temperature, REALFREQ, 1.0, DRUDEFREQ, timestep, num
 integ.setMaxDrudeDistance(0.02)                                                              # nacl_tg.py:22
 system, group, ngroups = synth.nacl()
 context = HipContext(system, integ, mode="TGNH", precision="mixed")                          # 'CudaPrecision': 'mixed', nacl_tg.py:60
+context.setVelocitiesToTemperature(temperature)                                             # nacl_tg.py:80 (Drude motion at the integrator's 1 K)
 print("Simulating...")
 dof, nkt = context.dof()
 mean, n = 0.0, 0

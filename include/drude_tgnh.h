@@ -286,6 +286,45 @@ tgnh_status tgnh_set_time(tgnh_handle h, double time, int64_t step_count);
  * barostat): cached kinetic energies are stale.  DrudeTGNHIntegrator.cpp:166-170 */
 tgnh_status tgnh_state_changed(tgnh_handle h);
 
+/* Context::setVelocitiesToTemperature for a Drude system: draws x, y, z of EVERY slot of the bound velm on the device, one
+ * launch on `stream`; w stays bit for bit what it is, positions, forces and the thermostat are not touched.  A per-particle
+ * Maxwell-Boltzmann draw would put `temperature` into the Drude springs; here a pair's centre of mass is drawn at
+ * `temperature` and its relative (Drude) motion at `drude_temperature`.  Per slot, with m = 1 / w (as every step kernel reads
+ * masses), kB the descriptor's and z(i) three standard normals of global index i:
+ *   massless slot (w == 0)   v = 0
+ *   slot in no pair          v = sqrt(kB T / m) z(own index)
+ *   pair, Drude d, parent p  mt = m_d + m_p, mu = m_d m_p / mt,
+ *                            v_cm = sqrt(kB T / mt) z(p),  v_rel = sqrt(kB T_D / mu) z(d)      (v_rel = v_p - v_d)
+ *                            v_d = v_cm - v_rel (m_p / mt),  v_p = v_cm + v_rel (m_d / mt)
+ * Random numbers: z(i) depends on (seed, global index) alone, global index = first_particle + the slot's index in this handle
+ * (a shard passes the index of its first slot in the whole system).  Philox4x32-10 with key = (low word of seed, high word of
+ * seed) and counter = (low word of the global index, high word, 0, 0); its four output words x0..x3 become uniforms
+ * u_k = (x_k + 0.5) 2^-32 in fp64, and
+ *   z = ( r0 cos(2 pi u1), r0 sin(2 pi u1), r1 cos(2 pi u3) ),  r0 = sqrt(-2 ln u0),  r1 = sqrt(-2 ln u2)
+ * (the fourth normal is discarded).  Everything is computed in fp64 and stored in velm's type.  No state is kept between calls
+ * and nothing depends on tiling, step path, grid, device or sharding: a particle gets the same velocity wherever and however
+ * it is generated.  dualNH and TGNH handles draw alike (temperature groups play no part).
+ * NOT done, as in OpenMM: no removal of the total momentum, no rescale to the exact target, no constraint projection (under
+ * constraints run the velocity-constraint call-out afterwards).
+ * The call is a setVelocities: before anything is written it does what tgnh_state_changed does -- refused with that call's
+ * status between the steps of a TGNH_FLAG_DEFER_SCALE sequence (velm untouched); afterwards bit 9 of tgnh_get_pending_state is
+ * clear and a cached kinetic-energy sum is stale (ke_sum_valid = 0).
+ * TGNH_ERR_ARG: a temperature that is negative or not finite (0 is legal: exact zeros), first_particle < 0.  TGNH_ERR_STATE:
+ * buffers not bound, a host-only handle. */
+tgnh_status tgnh_set_velocities_to_temperature(tgnh_handle h, double temperature, double drude_temperature,
+                                               uint64_t seed, int64_t first_particle, void* stream);
+
+/* Retargets both baths of a live handle (heating, annealing, equilibration at one temperature and production at another):
+ * kB T and kB T_D -- the chain's launch arguments and the hard wall's thermal speed --, every N kT and every thermostat mass,
+ * all recomputed by the functions tgnh_create runs: bit for bit what a handle created at the new temperatures holds, uploaded
+ * on `stream`.  eta, etaDot and etaDotDot stay: the chains run on with their momenta, as a restored checkpoint's would.
+ * tgnh_get_dof reports the new N kT.  Refused where tgnh_state_changed is (between the steps of a TGNH_FLAG_DEFER_SCALE sequence
+ * a thermostat half has already run at the old temperature); invalidates what tgnh_set_thermostat_state invalidates.
+ * TGNH_ERR_ARG: a temperature that is negative or not finite.
+ * SHARDED RUNS: the chains are replicated -- every rank must call this with the same values between the same two steps.
+ * A hipGraph of steps recorded earlier holds the old kT in its launch arguments: record it again. */
+tgnh_status tgnh_set_temperatures(tgnh_handle h, double temperature, double drude_temperature, void* stream);
+
 /* Host-visible results (synchronise `stream`).
  * tgnh_get_kinetic_energy: TGNH mode = the cached 1/2 sum of the last thermostat half step's bins when ke_sum_valid,
  * else 1/2 sum m v^2 (CudaDrudeTGNHKernels.cpp:654-658).  DUALNH mode = 1/2 sum m (v + F dt/2m)^2, the Reference

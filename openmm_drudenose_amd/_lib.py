@@ -71,6 +71,9 @@ SIGNATURES = {
     "tgnh_step_end_thermo": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tgnh_flush": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tgnh_state_changed": (C.c_int, [C.c_void_p]),
+    # (seed: uint64_t in the header, handed over as the same 64 bits)
+    "tgnh_set_velocities_to_temperature": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_void_p]),
+    "tgnh_set_temperatures": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "tgnh_note_replayed_steps": (C.c_int, [C.c_void_p, C.c_int]),
     "tgnh_set_time": (C.c_int, [C.c_void_p, C.c_double, C.c_int64]),
     "tgnh_get_kinetic_energy": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, c_f64p]),

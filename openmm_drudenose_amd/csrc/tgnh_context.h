@@ -82,6 +82,9 @@ struct tgnh_context {
         tgnh::DeviceBytes d_com;
         tgnh::DeviceBuf<double> d_scratch;    // chains longer than 4 links of more than 34 thermostats: a row of 4 C + 1 doubles each
     } gather;
+    struct VelInit {                  // tgnh_set_velocities_to_temperature on a tiled handle: the gather path's partner table, built at the first call
+        tgnh::DeviceBuf<int> d_partner;
+    } velinit;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block
         std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction

@@ -1,6 +1,7 @@
 // tgnh_host.h -- what the host units behind the C ABI (include/drude_tgnh.h) share: tgnh_topology.cpp, tgnh_lifecycle.cpp,
 // tgnh_exchange.cpp, tgnh_step.cpp, tgnh_queries.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
-// live in tgnh_kernels.hip (tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h), tgnh_gather.hip and tgnh_harness.hip.
+// live in tgnh_kernels.hip (tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h), tgnh_gather.hip, tgnh_velinit.hip and
+// tgnh_harness.hip.
 //
 // Reference semantics followed (scychon/openmm_drudeNose):
 //   Ref = platforms/reference/src/ReferenceDrudeTGNHKernels.cpp
@@ -34,7 +35,11 @@ inline int pass_kind(const tgnh_desc& d) { return (d.flags & TGNH_FLAG_DEFER_SCA
 void make_layout(tgnh_context* c);
 tgnh_status build_topology(tgnh_context* c, const tgnh_desc* d);
 void local_dof_terms(tgnh_context* c);
+tgnh_status check_temperatures(double temperature, double drude_temperature);
+void set_bath_temperatures(tgnh_context* c, double temperature, double drude_temperature);
+void thermostat_targets(tgnh_context* c, std::vector<double>& st);
 tgnh_status finalize_thermostat(tgnh_context* c);
+std::vector<int> partner_table(const tgnh_context* c);
 // tgnh_lifecycle.cpp
 tgnh_status deferred_guard(tgnh_handle h, const char* what);
 // tgnh_step.cpp

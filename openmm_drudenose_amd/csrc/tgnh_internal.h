@@ -338,6 +338,9 @@ constexpr int PLAIN_KE_PARTS = 2048;         // work-group partials of the plain
 hipError_t launch_plain_ke(int precision, const void* velm, const long long* force, int n, int padded,
                            double time_shift, double* out /*[1 + PLAIN_KE_PARTS] device: out[0] = the result*/, hipStream_t s);
 size_t tile_lds_bytes(int precision, int ops, bool hardwall, bool use_com);
+// the velocity draw (tgnh_velinit.hip): velm [n] mixed4, partner [n] as GatherArgs::partner, kT / kTD = kB T / kB T_D
+hipError_t launch_velinit(int precision, void* velm, const int* partner, int n, double kT, double kTD,
+                          unsigned long long seed, long long first_particle, hipStream_t s);
 
 }  // namespace tgnh
 

@@ -209,8 +209,7 @@ extern "C" tgnh_status tgnh_create(const tgnh_desc* d, tgnh_handle* out) {
     c->host_only = host_only;
     c->d = *d;
     c->device = d->device;
-    c->thermo.realkbT = d->kB * d->temperature;                                      // Ref :107-108, Cu :80-81
-    c->thermo.drudekbT = d->kB * d->drude_temperature;
+    set_bath_temperatures(c, d->temperature, d->drude_temperature);
     make_layout(c);
     c->cfg.gb = c->thermo.L.G <= 1 ? 1 : (c->thermo.L.G <= 4 ? 4 : (c->thermo.L.G <= 8 ? 8 : 0));   // 0: KE bins in LDS
     if (long_chain) { c->gather.generic = true; c->gather.reason = "a chain too long for the LDS-resident form"; }
@@ -303,6 +302,32 @@ extern "C" tgnh_status tgnh_set_max_drude_distance(tgnh_handle h, double dist) {
     CHECK_H(h);
     if (!(dist >= 0)) return fail(TGNH_ERR_ARG, "setMaxDrudeDistance: Distance cannot be negative");   // API :98-99 (NaN neither)
     h->d.max_drude_distance = dist;
+    return TGNH_OK;
+}
+
+// Both baths of a live handle.  Everything the temperatures decide is formed again by what tgnh_create ran
+// (set_bath_temperatures, thermostat_targets): the handle holds what one created at these temperatures holds; of the block only
+// N kT and the thermostat masses go to the device -- eta, etaDot, etaDotDot are the run's.
+extern "C" tgnh_status tgnh_set_temperatures(tgnh_handle h, double temperature, double drude_temperature, void* stream) {
+    CHECK_H(h);
+    tgnh_status rc = check_temperatures(temperature, drude_temperature); if (rc) return rc;
+    rc = deferred_guard(h, "tgnh_set_temperatures"); if (rc) return rc;
+    const ChainLayout& L = h->thermo.L;
+    hipStream_t s = (hipStream_t)stream;
+    rc = entry(h, false); if (rc) return rc;
+    if (!h->host_only) { rc = materialize_chain(h, s); if (rc) return rc; }   // (a chain still owed runs at the temperature it was owed at; a staged block is committed)
+    h->owed.ke_carry = false;
+    set_bath_temperatures(h, temperature, drude_temperature);
+    std::vector<double> st(L.total, 0.0);
+    thermostat_targets(h, st);
+    const int sections[2][2] = {{L.off_etaMass, L.len_etaMass}, {L.off_nkbt, L.NT}};
+    for (const auto& sec : sections) std::copy(st.begin() + sec[0], st.begin() + sec[0] + sec[1], h->thermo.h_state.begin() + sec[0]);
+    if (h->host_only) return TGNH_OK;
+    for (const auto& sec : sections) {                           // both copies, as tgnh_set_thermostat_state
+        HIP_OK(hipMemcpyAsync(h->thermo.d_state + sec[0], st.data() + sec[0], sizeof(double) * sec[1], hipMemcpyHostToDevice, s));
+        HIP_OK(hipMemcpyAsync(h->thermo.d_stage + sec[0], st.data() + sec[0], sizeof(double) * sec[1], hipMemcpyHostToDevice, s));
+    }
+    HIP_OK(hipStreamSynchronize(s));                             // (st is pageable and about to go)
     return TGNH_OK;
 }
 

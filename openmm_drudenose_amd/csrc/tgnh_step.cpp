@@ -671,3 +671,23 @@ extern "C" tgnh_status tgnh_state_changed(tgnh_handle h) {
     h->owed.ke_carry = false;              // TRUST_STATE_CHANGED: the next thermostat half step sums the kinetic energies again (Cu :474-488)
     return TGNH_OK;
 }
+
+// Context::setVelocitiesToTemperature (include/drude_tgnh.h has the contract; tgnh_velinit.hip the kernel).  A setVelocities:
+// tgnh_state_changed's refusal and its effect come first, then one launch by global index whatever path the handle steps on.
+extern "C" tgnh_status tgnh_set_velocities_to_temperature(tgnh_handle h, double temperature, double drude_temperature,
+                                                          uint64_t seed, int64_t first_particle, void* stream) {
+    CHECK_H(h);
+    tgnh_status rc = check_temperatures(temperature, drude_temperature); if (rc) return rc;
+    if (first_particle < 0) return fail(TGNH_ERR_ARG, "tgnh_set_velocities_to_temperature: negative first_particle");
+    rc = entry(h, true); if (rc) return rc;                     // (buffers bound, not a host-only handle)
+    rc = tgnh_state_changed(h); if (rc) return rc;
+    const int* partner = h->gather.d_partner;
+    if (!partner) {                                              // a tiled handle: the gather path's table, from the pair lists, once
+        if (!h->velinit.d_partner) HIP_OK(h->velinit.d_partner.upload(partner_table(h)));
+        partner = h->velinit.d_partner;
+    }
+    Timed t(h, (hipStream_t)stream, KID_OTHER);
+    HIP_OK(launch_velinit(h->d.precision, h->bound.velm, partner, h->d.num_particles, h->d.kB * temperature, h->d.kB * drude_temperature,
+                          (unsigned long long)seed, (long long)first_particle, (hipStream_t)stream));
+    return TGNH_OK;
+}

@@ -10,8 +10,18 @@
 // the residue table (count, first) and nothing else: no tiles, no per-slot words.  Taken by build_topology for what the tiles
 // cannot hold (c->gather.reason says what).
 // ---------------------------------------------------------------------------
-static tgnh_status build_gather_topology(tgnh_context* c, const std::vector<int>& role, const std::vector<int>& partner,
-                                         const std::vector<int>& res_order) {
+// per particle: the other member of its pair | is-Drude << 31, -1 in no pair -- from the pair lists build_topology checked
+// (the gather kernels' table; the velocity draw's on every handle)
+std::vector<int> partner_table(const tgnh_context* c) {
+    std::vector<int> t(c->d.num_particles, -1);
+    for (size_t k = 0; k < c->topo.pair_drude.size(); k++) {
+        const int p = c->topo.pair_drude[k], p1 = c->topo.pair_parent[k];
+        t[p] = (int)((unsigned)p1 | 0x80000000u); t[p1] = p;
+    }
+    return t;
+}
+
+static tgnh_status build_gather_topology(tgnh_context* c, const std::vector<int>& res_order) {
     const tgnh_desc& d = c->d;
     const int N = d.num_particles;
     const bool com = com_thermostat_on(d);
@@ -33,9 +43,7 @@ static tgnh_status build_gather_topology(tgnh_context* c, const std::vector<int>
         c->gather.com_lanes = 1;
         while (c->gather.com_lanes < 64 && (size_t)c->gather.com_lanes < mean) c->gather.com_lanes *= 2;
     }
-    c->gather.partner.assign(N, -1);                                  // the other member of a particle's pair | is-Drude << 31
-    for (int i = 0; i < N; i++)
-        if (partner[i] >= 0) c->gather.partner[i] = role[i] == (int)ROLE_DRUDE ? (int)((unsigned)partner[i] | 0x80000000u) : partner[i];
+    c->gather.partner = partner_table(c);
     if (c->host_only) return TGNH_OK;
     HIP_OK(c->gather.d_group.upload(c->topo.group));
     HIP_OK(c->gather.d_resid.upload(c->gather.resid));
@@ -223,7 +231,7 @@ tgnh_status build_topology(tgnh_context* c, const tgnh_desc* d) {
     }
     c->topo.tile_start.push_back(N);
     c->topo.num_tiles = (int)c->topo.tile_start.size() - 1;
-    if (c->gather.generic) return build_gather_topology(c, role, partner, res_order);
+    if (c->gather.generic) return build_gather_topology(c, res_order);
 
     // per-tile residue entries (count, first slot) -- count < 0: big molecule, COM at table index -count-1 --
     // and the packed per-slot words
@@ -399,17 +407,26 @@ void local_dof_terms(tgnh_context* c) {
     c->thermo.local_terms[G + 1] = 3.0 * P;                                          // Cu :149, :201
 }
 
-tgnh_status finalize_thermostat(tgnh_context* c) {
+// The two bath temperatures of a handle: tgnh_create's, and tgnh_set_temperatures' later.  (OpenMM's setTemperature checks
+// nothing and neither does tgnh_create; the setter of a live handle and the velocity draw refuse what cannot be a temperature.)
+tgnh_status check_temperatures(double temperature, double drude_temperature) {
+    if (!(temperature >= 0) || !std::isfinite(temperature) || !(drude_temperature >= 0) || !std::isfinite(drude_temperature))
+        return fail(TGNH_ERR_ARG, "a temperature must be finite and not negative");
+    return TGNH_OK;
+}
+void set_bath_temperatures(tgnh_context* c, double temperature, double drude_temperature) {
+    c->d.temperature = temperature; c->d.drude_temperature = drude_temperature;      // (the hard wall's thermal speed reads the latter)
+    c->thermo.realkbT = c->d.kB * temperature;                                       // Ref :107-108, Cu :80-81
+    c->thermo.drudekbT = c->d.kB * drude_temperature;
+}
+
+// What the bath temperatures decide of the thermostat block -- every N kT (thermo.nkbt too) and every thermostat mass, and the
+// etaDotDot a chain STARTS with -- written into st (the block's layout, zero elsewhere) from thermo.dof and kT, kT_D.
+void thermostat_targets(tgnh_context* c, std::vector<double>& st) {
     const tgnh_desc& d = c->d;
-    ChainLayout& L = c->thermo.L;
+    const ChainLayout& L = c->thermo.L;
     const int NT = L.NT, C = L.C;
-    c->thermo.dof = c->thermo.global_terms;
-    if (d.has_cm_motion_remover) {
-        if (d.mode == TGNH_MODE_DUALNH) c->thermo.dof[0] -= 3;                       // Ref :158-165
-        else if (d.use_com_temp_group) c->thermo.dof[L.G] -= 3;                      // Cu :204-212
-    }
     c->thermo.nkbt.assign(NT, 0.0);
-    std::vector<double> st(L.total, 0.0);
     const double tau2 = std::pow(d.coupling_time, 2), tauD2 = std::pow(d.drude_coupling_time, 2);
     if (d.mode == TGNH_MODE_DUALNH) {
         const double realNkbT = c->thermo.dof[0] * c->thermo.realkbT, drudeNkbT = c->thermo.dof[2] * c->thermo.drudekbT;   // Ref :168-169
@@ -453,8 +470,21 @@ tgnh_status finalize_thermostat(tgnh_context* c) {
             if (L.use_drude_chains) edd[ich] = (em[ich - 1] * 0.0 - c->thermo.drudekbT) / em[ich];
         }
     }
+    for (int i = 0; i < NT; i++) st[L.off_nkbt + i] = c->thermo.nkbt[i];
+}
+
+tgnh_status finalize_thermostat(tgnh_context* c) {
+    const tgnh_desc& d = c->d;
+    ChainLayout& L = c->thermo.L;
+    const int NT = L.NT;
+    c->thermo.dof = c->thermo.global_terms;
+    if (d.has_cm_motion_remover) {
+        if (d.mode == TGNH_MODE_DUALNH) c->thermo.dof[0] -= 3;                       // Ref :158-165
+        else if (d.use_com_temp_group) c->thermo.dof[L.G] -= 3;                      // Cu :204-212
+    }
+    std::vector<double> st(L.total, 0.0);
+    thermostat_targets(c, st);
     for (int i = 0; i < NT; i++) {
-        st[L.off_nkbt + i] = c->thermo.nkbt[i];
         st[L.off_scale + i] = 1.0; st[L.off_scale_a + i] = 1.0; st[L.off_scale_b + i] = 1.0;
     }
     c->thermo.h_state = st;

@@ -58,11 +58,28 @@ class DrudeTGNHIntegrator:
 
     # --- scalar properties (DrudeTGNHIntegrator.h:77-211) ---
     def getTemperature(self): return self._temperature
-    def setTemperature(self, temp): self._temperature = float(temp)
+
+    def setTemperature(self, temp):
+        self._set_bath("_temperature", temp)
     def getCouplingTime(self): return self._couplingTime
     def setCouplingTime(self, tau): self._couplingTime = float(tau)
     def getDrudeTemperature(self): return self._drudeTemperature
-    def setDrudeTemperature(self, temp): self._drudeTemperature = float(temp)
+
+    def setDrudeTemperature(self, temp):
+        self._set_bath("_drudeTemperature", temp)
+
+    def _set_bath(self, name, temp):
+        """A bound integrator retargets its handle (tgnh_set_temperatures); where the handle refuses -- between the steps of a
+        deferred sequence, or a value that is no temperature -- the integrator keeps the value the handle runs at."""
+        old = getattr(self, name)
+        setattr(self, name, float(temp))
+        if self._context is not None:
+            try:
+                self._context._push_scalars()
+            except TgnhError:
+                setattr(self, name, old)
+                raise
+
     def getDrudeCouplingTime(self): return self._drudeCouplingTime
     def setDrudeCouplingTime(self, tau): self._drudeCouplingTime = float(tau)
     def getMaxDrudeDistance(self): return self._maxDrudeDistance
@@ -285,6 +302,9 @@ class HipContext(_HandleQueries):
             h = create_handle(self.lib, system, integrator, group, ngroups, self.mode, self.precision, device, flags, kB,
                               self.padded)
         self.h = h
+        self._pushed_baths = (integrator.getTemperature(), integrator.getDrudeTemperature())   # what the handle was created at
+        self._bath_epoch = 0
+        self.first_particle = 0                              # a shard: the index of its first slot in the whole system (setVelocitiesToTemperature)
         self._hook = None
         if global_dof_sum is not None:                       # particle sharding: dof terms are additive over ranks
             self.set_global_dof_terms(global_dof_sum(self.local_dof_terms()))
@@ -313,7 +333,8 @@ class HipContext(_HandleQueries):
         self.state_hook = None
         self.ke_sum_valid = False
         self.constrained = False
-        if system.cluster_atoms is not None and len(system.cluster_atoms):
+        self._has_clusters = system.cluster_atoms is not None and len(system.cluster_atoms) > 0
+        if self._has_clusters:
             _check(self.lib.tgnh_harness_set_clusters(self.h, len(system.cluster_atoms),
                                                       system.cluster_atoms.ctypes.data_as(_lib.c_i32p),
                                                       system.cluster_dist.ctypes.data_as(_lib.c_f64p)))
@@ -340,6 +361,11 @@ class HipContext(_HandleQueries):
         _check(self.lib.tgnh_set_step_size(self.h, i.getStepSize()))
         _check(self.lib.tgnh_set_drude_steps_per_real_step(self.h, i.getDrudeStepsPerRealStep()))
         _check(self.lib.tgnh_set_max_drude_distance(self.h, i.getMaxDrudeDistance()))
+        baths = (i.getTemperature(), i.getDrudeTemperature())
+        if baths != self._pushed_baths:                      # (only then: a run that never retargets makes no such call)
+            _check(self.lib.tgnh_set_temperatures(self.h, baths[0], baths[1], self._stream()))
+            self._pushed_baths = baths
+            self._bath_epoch += 1                            # (capture_steps: a recorded step holds the old kT)
 
     def close(self):
         if getattr(self, "h", None):
@@ -549,6 +575,25 @@ class HipContext(_HandleQueries):
         self._state_changed()                                # (first: refused between the steps of a deferred sequence, and then nothing is written)
         self.velm[:, :3] = self.torch.from_numpy(np.ascontiguousarray(vel, np.float64)).to(self.dev, self.mdt)
 
+    def setVelocitiesToTemperature(self, temperature, randomSeed=None, drudeTemperature=None):
+        """OpenMM's Context.setVelocitiesToTemperature, Drude-aware and drawn on the device (tgnh_set_velocities_to_temperature):
+        pair centres of mass and ordinary particles at `temperature`, the relative Drude motion at `drudeTemperature` (default:
+        the integrator's).  randomSeed=None takes one from os.urandom; the same seed gives the same velocities on any handle,
+        path or sharding (self.first_particle places a shard in the whole system).  With constraint clusters set, the harness'
+        velocity-constraint stage runs afterwards, as OpenMM projects after its draw."""
+        if drudeTemperature is None:
+            drudeTemperature = self.integrator.getDrudeTemperature()
+        if randomSeed is None:
+            import os
+            randomSeed = int.from_bytes(os.urandom(8), "little")
+        seed = int(randomSeed) & 0xFFFFFFFFFFFFFFFF
+        seed = seed - (1 << 64) if seed >> 63 else seed      # (the same 64 bits as a c_int64)
+        _check(self.lib.tgnh_set_velocities_to_temperature(self.h, float(temperature), float(drudeTemperature), seed,
+                                                           int(self.first_particle), self._stream()))
+        self.ke_sum_valid = False
+        if self._has_clusters:
+            _check(self.lib.tgnh_harness_shake_velocities(self.h, self.integrator.getConstraintTolerance(), self._stream()))
+
     def _state_changed(self):                                # DrudeTGNHIntegrator.cpp:166-170
         self.ke_sum_valid = False
         _check(self.lib.tgnh_state_changed(self.h))
@@ -687,8 +732,12 @@ class HipContext(_HandleQueries):
         self.set_time(*clock)
         self._captured_not_run = int(steps)
         turn = [0]
+        baths = self._bath_epoch
 
         def replay():
+            if self._bath_epoch != baths:
+                raise TgnhError(_lib.ERR_STATE, "capture_steps: the temperatures were changed after these steps were recorded "
+                                "(their launches hold the old kT): capture them again")
             graphs[turn[0] & 1].replay()
             turn[0] += 1
             if self._captured_not_run:

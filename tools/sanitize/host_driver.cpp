@@ -1,0 +1,59 @@
+// Stand-alone driver of the host-only sanitizer build (run_host_driver_asan.sh): the host side of tgnh_set_temperatures and
+// tgnh_set_velocities_to_temperature through a host-only handle (device -1), no Python in the process.  What needs a device --
+// the upload of the retargeted block, the partner table's first use and the launch -- is not reached here.
+#include <cmath>
+#include <cstdio>
+#include <vector>
+
+#include "../../include/drude_tgnh.h"
+
+#define EXPECT(cond) do { if (!(cond)) { std::fprintf(stderr, "host_driver: %s failed (line %d): %s\n", #cond, __LINE__, tgnh_last_error()); return 1; } } while (0)
+
+static int run(int mode, int chains, int drude_chains) {
+    const int mols = 37, N = 5 * mols;                          // SWM4 water: O, D, H1, H2, M (massless)
+    std::vector<double> mass;
+    std::vector<int32_t> pd, pp, group(N, 0), resid;
+    for (int m = 0; m < mols; m++) {
+        const double mm[5] = {15.6, 0.4, 1.0, 1.0, 0.0};
+        for (int k = 0; k < 5; k++) { mass.push_back(mm[k]); resid.push_back(m); }
+        pd.push_back(5 * m + 1); pp.push_back(5 * m);
+    }
+    tgnh_desc d{};
+    d.struct_size = sizeof(d); d.mode = mode; d.precision = TGNH_PREC_MIXED; d.device = -1;
+    d.num_particles = N; d.padded_num_particles = (N + 31) / 32 * 32; d.num_pairs = mols; d.num_groups = 1; d.num_residues = mols;
+    d.mass = mass.data(); d.pair_drude = pd.data(); d.pair_parent = pp.data(); d.group = group.data(); d.resid = resid.data();
+    d.kB = 8.31446261815324e-3; d.temperature = 300; d.coupling_time = 0.1; d.drude_temperature = 1; d.drude_coupling_time = 0.005;
+    d.step_size = 0.001; d.drude_steps_per_real_step = 20; d.num_nh_chains = chains; d.use_drude_nh_chains = drude_chains; d.use_com_temp_group = 1;
+    tgnh_handle a = nullptr, b = nullptr;
+    EXPECT(tgnh_create(&d, &a) == TGNH_OK);
+    d.temperature = 350; d.drude_temperature = 2;
+    EXPECT(tgnh_create(&d, &b) == TGNH_OK);
+    EXPECT(tgnh_set_temperatures(a, NAN, 1, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_set_temperatures(a, 300, -1, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_set_temperatures(nullptr, 300, 1, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_set_temperatures(a, 350, 2, nullptr) == TGNH_OK);
+    int nt = 0, len = 0;
+    EXPECT(tgnh_get_num_thermostats(a, &nt) == TGNH_OK && nt >= 3);
+    std::vector<double> da(nt), na(nt), db(nt), nb(nt);
+    EXPECT(tgnh_get_dof(a, da.data(), na.data()) == TGNH_OK && tgnh_get_dof(b, db.data(), nb.data()) == TGNH_OK);
+    for (int i = 0; i < nt; i++) EXPECT(da[i] == db[i] && na[i] == nb[i]);
+    for (int which = 0; which < 4; which++) {                    // untouched chains are still the initial ones: all four arrays agree
+        EXPECT(tgnh_get_thermostat_len(a, which, &len) == TGNH_OK);
+        std::vector<double> xa(len), xb(len);
+        EXPECT(tgnh_get_thermostat_state(a, which, nullptr, xa.data()) == TGNH_OK && tgnh_get_thermostat_state(b, which, nullptr, xb.data()) == TGNH_OK);
+        if (which == 3) for (int i = 0; i < len; i++) EXPECT(xa[i] == xb[i]);
+    }
+    EXPECT(tgnh_set_velocities_to_temperature(a, -1, 1, 1, 0, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_set_velocities_to_temperature(a, 300, INFINITY, 1, 0, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_set_velocities_to_temperature(a, 300, 1, 1, -1, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_set_velocities_to_temperature(nullptr, 300, 1, 1, 0, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_set_velocities_to_temperature(a, 300, 1, ~0ull, 1ll << 40, nullptr) == TGNH_ERR_STATE);      // host-only: nothing launches
+    EXPECT(tgnh_destroy(a) == TGNH_OK && tgnh_destroy(b) == TGNH_OK);
+    return 0;
+}
+
+int main() {
+    if (run(TGNH_MODE_TGNH, 3, 1) || run(TGNH_MODE_DUALNH, 3, 1) || run(TGNH_MODE_DUALNH, 2, 0) || run(TGNH_MODE_TGNH, 1, 1)) return 1;
+    std::puts("host_driver: ok");
+    return 0;
+}
