@@ -346,6 +346,49 @@ tgnh_status tgnh_get_status_flags(tgnh_handle h, void* stream, uint32_t* flags);
 tgnh_status tgnh_get_time(tgnh_handle h, double* time, int64_t* step_count);
 tgnh_status tgnh_get_dof(tgnh_handle h, double* dof, double* nkt);
 
+/* How the Drude oscillators are doing, from the bound positions as they are: one read-only pass on `stream` over posq (and
+ * posq_correction) plus a one-work-group sum, then one small copy to the host.  Per pair (Drude d, parent p), everything in fp64:
+ *   coordinate   x(i) = (double)posq[i].x                                   single and double precision
+ *                x(i) = (double)posq[i].x + (double)posq_correction[i].x    mixed precision (likewise y, z)
+ *   dx = x(d) - x(p), dy, dz likewise;   d2 = dx dx + dy dy + dz dz   (each product and each sum rounded on its own, left to
+ *   right: no fused multiply-add);   d = sqrt(d2);   q_D = (double)posq[d].w
+ * NO minimum image is applied: the library knows no periodic box, and OpenMM keeps the atoms of a molecule -- a Drude particle and
+ * its parent among them -- in one periodic image.  The fields of *out:
+ *   pairs           pairs looked at (= num_pairs)
+ *   over            pairs with d2 > threshold * threshold
+ *   max_distance    sqrt of the largest d2; 0 when there is no pair
+ *   worst_particle  slot index, local to this handle, of the Drude particle of the pair with the largest d2 (ties: the lowest
+ *                   slot index); -1 when there is no pair
+ *   sum_d2          sum of d2 over the pairs (the caller forms rms = sqrt(sum_d2 / pairs))
+ *   dipole[3]       sum of q_D dx, q_D dy, q_D dz over the pairs: the induced dipole.  Only the Drude particles' charges enter.
+ *   hist            with t = (d * TGNH_DRUDE_HIST_BINS) / hist_max (in fp64): hist[k], k < BINS, counts the pairs with
+ *                   floor(t) == k, hist[BINS] those with t >= BINS (that is d >= hist_max).  hist_max == 0 switches the histogram
+ *                   off: all entries 0.
+ * A query: it reads positions only, so it needs no tgnh_flush (only velm ever lags) and changes nothing of the trajectory nor of
+ * tgnh_get_pending_state.  It synchronises `stream`, as every tgnh_get_* does, and follows tgnh_get_status_flags' rule for sticky
+ * failures.  Its scratch (a few hundred KiB) is allocated at the first call: a handle that never asks allocates nothing.
+ * Reproducible as the header's rules above have it: no floating-point atomic; the grid is a function of num_particles alone (not of
+ * the device, the flags or the step path) and every order of additions is fixed by it, so the same positions give the same bits
+ * from any handle over the same slots, tiled or TGNH_FLAG_GATHER, asked once or twice.
+ * SHARDED RUNS: the library does no exchange for this call; every rank answers for its own slots.  pairs, over, hist, sum_d2 and
+ * dipole are additive over ranks (the doubles then to rounding, not to the bits of an unsharded handle), max_distance is a maximum
+ * over ranks, worst_particle is local: the caller adds the index of the rank's first slot.
+ * TGNH_ERR_ARG: out is NULL, out->struct_size is not sizeof(tgnh_drude_stats) (set it before the call; nothing else of *out is
+ * read, and on an error nothing of it is written), threshold or hist_max negative or not finite.  TGNH_ERR_STATE: buffers not
+ * bound, a host-only handle.  A handle with num_pairs == 0: TGNH_OK, zeros, worst_particle -1. */
+#define TGNH_DRUDE_HIST_BINS 32
+typedef struct tgnh_drude_stats {
+    uint32_t struct_size;     /* in: sizeof(tgnh_drude_stats); anything else: TGNH_ERR_ARG */
+    int32_t  worst_particle;
+    int64_t  pairs;
+    int64_t  over;
+    double   max_distance;
+    double   sum_d2;
+    double   dipole[3];
+    int64_t  hist[TGNH_DRUDE_HIST_BINS + 1];
+} tgnh_drude_stats;
+tgnh_status tgnh_get_drude_statistics(tgnh_handle h, double threshold, double hist_max, void* stream, tgnh_drude_stats* out);
+
 /* Thermostat state (checkpoint/resume, absent in the reference: SURVEY.md 5).
  * which: 0 eta, 1 etaDot, 2 etaDotDot, 3 etaMass.  Layout: DUALNH = the
  * reference's interleaved vectors; TGNH = [thermostat][link], etaDot rows of C+1. */

@@ -34,6 +34,18 @@ class TgnhDesc(C.Structure):
     ]
 
 
+DRUDE_HIST_BINS = 32
+
+
+class TgnhDrudeStats(C.Structure):
+    """tgnh_drude_stats (tgnh_get_drude_statistics)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("worst_particle", C.c_int32), ("pairs", C.c_int64), ("over", C.c_int64),
+        ("max_distance", C.c_double), ("sum_d2", C.c_double), ("dipole", C.c_double * 3),
+        ("hist", C.c_int64 * (DRUDE_HIST_BINS + 1)),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p)
 
 # name -> (restype, argtypes); every symbol include/drude_tgnh.h declares
@@ -83,6 +95,8 @@ SIGNATURES = {
     "tgnh_get_status_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "tgnh_get_time": (C.c_int, [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]),
     "tgnh_get_dof": (C.c_int, [C.c_void_p, c_f64p, c_f64p]),
+    # (out: a TgnhDrudeStats by reference)
+    "tgnh_get_drude_statistics": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "tgnh_get_thermostat_len": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "tgnh_get_thermostat_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, c_f64p]),
     "tgnh_set_thermostat_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, c_f64p]),

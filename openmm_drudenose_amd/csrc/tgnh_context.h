@@ -82,9 +82,14 @@ struct tgnh_context {
         tgnh::DeviceBytes d_com;
         tgnh::DeviceBuf<double> d_scratch;    // chains longer than 4 links of more than 34 thermostats: a row of 4 C + 1 doubles each
     } gather;
-    struct VelInit {                  // tgnh_set_velocities_to_temperature on a tiled handle: the gather path's partner table, built at the first call
-        tgnh::DeviceBuf<int> d_partner;
-    } velinit;
+    struct ByIndex {                  // the passes by global index on a tiled handle (the velocity draw, the Drude statistics): the gather
+        tgnh::DeviceBuf<int> d_partner;   // path's partner table, built by whichever of them is called first (device_partner_table)
+    } by_index;
+    struct DrudeStats {               // tgnh_get_drude_statistics: allocated at its first call
+        tgnh::DeviceBuf<tgnh::DrudeStatsRow> d_rows;   // [rows_allocated]: a row per work-group of the pass, then the result
+        int rows_allocated = 0;
+        tgnh::DrudeStatsRow h_row{};      // where the result lands on the host
+    } dstats;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block
         std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction

@@ -1,7 +1,7 @@
 // tgnh_host.h -- what the host units behind the C ABI (include/drude_tgnh.h) share: tgnh_topology.cpp, tgnh_lifecycle.cpp,
 // tgnh_exchange.cpp, tgnh_step.cpp, tgnh_queries.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
-// live in tgnh_kernels.hip (tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h), tgnh_gather.hip, tgnh_velinit.hip and
-// tgnh_harness.hip.
+// live in tgnh_kernels.hip (tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h), tgnh_gather.hip, tgnh_velinit.hip,
+// tgnh_drude_stats.hip and tgnh_harness.hip.
 //
 // Reference semantics followed (scychon/openmm_drudeNose):
 //   Ref = platforms/reference/src/ReferenceDrudeTGNHKernels.cpp
@@ -40,6 +40,7 @@ void set_bath_temperatures(tgnh_context* c, double temperature, double drude_tem
 void thermostat_targets(tgnh_context* c, std::vector<double>& st);
 tgnh_status finalize_thermostat(tgnh_context* c);
 std::vector<int> partner_table(const tgnh_context* c);
+tgnh_status device_partner_table(tgnh_context* c, const int** out);
 // tgnh_lifecycle.cpp
 tgnh_status deferred_guard(tgnh_handle h, const char* what);
 // tgnh_step.cpp

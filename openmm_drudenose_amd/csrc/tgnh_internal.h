@@ -341,6 +341,19 @@ size_t tile_lds_bytes(int precision, int ops, bool hardwall, bool use_com);
 // the velocity draw (tgnh_velinit.hip): velm [n] mixed4, partner [n] as GatherArgs::partner, kT / kTD = kB T / kB T_D
 hipError_t launch_velinit(int precision, void* velm, const int* partner, int n, double kT, double kTD,
                           unsigned long long seed, long long first_particle, hipStream_t s);
+// Drude pair statistics (tgnh_drude_stats.hip): a read-only pass by global index over posq (+ posq_corr) and the partner table,
+// one row per work-group, then one work-group that adds the rows into rows[grid].  The grid is a function of n alone.
+constexpr int DRUDE_STATS_GRID_CAP = 1024;   // work-groups (= rows) of the pass: beyond 1024 x BLOCK = 262 144 slots its threads take the grid-stride loop again
+struct DrudeStatsRow {
+    double sum_d2, dipole[3];
+    unsigned long long max_key;              // bit pattern of the largest d2 (orders as the double does: d2 >= 0)
+    long long over, pairs;
+    int worst, pad;                          // slot of the Drude particle of that pair; 0x7fffffff: the row saw no pair
+    long long hist[TGNH_DRUDE_HIST_BINS + 1];
+};
+inline int drude_stats_grid(int n) { const long long g = ((long long)n + BLOCK - 1) / BLOCK; return (int)(g < DRUDE_STATS_GRID_CAP ? g : DRUDE_STATS_GRID_CAP); }
+hipError_t launch_drude_stats(int precision, const void* posq, const void* posq_corr, const int* partner, int n, double threshold,
+                              double hist_max, DrudeStatsRow* rows /*[grid + 1]: the work-groups' rows, then the result*/, int grid, hipStream_t s);
 
 }  // namespace tgnh
 

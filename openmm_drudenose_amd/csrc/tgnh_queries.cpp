@@ -177,6 +177,53 @@ extern "C" tgnh_status tgnh_compute_kinetic_energies(tgnh_handle h, void* stream
     return TGNH_OK;
 }
 
+// The Drude pairs as the bound positions have them (include/drude_tgnh.h has the contract; tgnh_drude_stats.hip the kernels).
+// A query: it reads posq (+ posq_corr) and nothing of what a step leaves owed -- only velm ever lags --, so there is nothing to
+// flush and nothing of the handle changes but the scratch it allocates at its first call.
+extern "C" tgnh_status tgnh_get_drude_statistics(tgnh_handle h, double threshold, double hist_max, void* stream, tgnh_drude_stats* out) {
+    CHECK_H(h);
+    if (!out) return fail(TGNH_ERR_ARG, "null out");
+    if (out->struct_size != sizeof(tgnh_drude_stats)) return fail(TGNH_ERR_ARG, "tgnh_drude_stats size mismatch (ABI)");
+    if (!(threshold >= 0.0) || !std::isfinite(threshold)) return fail(TGNH_ERR_ARG, "tgnh_get_drude_statistics: threshold is negative or not finite");
+    if (!(hist_max >= 0.0) || !std::isfinite(hist_max)) return fail(TGNH_ERR_ARG, "tgnh_get_drude_statistics: hist_max is negative or not finite");
+    tgnh_status rc = entry(h, true); if (rc) return rc;          // (buffers bound, not a host-only handle, no failure seen before)
+    hipStream_t s = (hipStream_t)stream;
+    DrudeStatsRow& r = h->dstats.h_row;                          // (the handle's: a copy still in flight when an error returns lands in live memory)
+    r = DrudeStatsRow{};
+    r.worst = 0x7fffffff;
+    if (h->d.num_pairs > 0) {
+        const int grid = drude_stats_grid(h->d.num_particles);
+        if (!h->dstats.d_rows) {
+            HIP_OK(h->dstats.d_rows.alloc((size_t)grid + 1, true));
+            h->dstats.rows_allocated = grid + 1;
+        }
+        if (grid < 1 || grid > DRUDE_STATS_GRID_CAP || grid + 1 > h->dstats.rows_allocated)
+            return fail(TGNH_ERR_STATE, "internal: the Drude statistics' grid exceeds its rows");
+        if (h->d.precision == TGNH_PREC_MIXED && !h->bound.posq_corr) return fail(TGNH_ERR_STATE, "internal: mixed precision without a position correction");
+        const int* partner = nullptr;
+        rc = device_partner_table(h, &partner); if (rc) return rc;
+        {
+            Timed t(h, s, KID_OTHER);
+            HIP_OK(launch_drude_stats(h->d.precision, h->bound.posq, h->bound.posq_corr, partner, h->d.num_particles, threshold, hist_max,
+                                      h->dstats.d_rows, grid, s));
+        }
+        HIP_OK(hipMemcpyAsync(&r, h->dstats.d_rows + grid, sizeof(r), hipMemcpyDeviceToHost, s));
+    }
+    HIP_OK(hipMemcpyAsync(h->status.h_seen, h->status.d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    note_status(h, *h->status.h_seen);
+    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);
+    double max_d2;
+    std::memcpy(&max_d2, &r.max_key, sizeof(max_d2));
+    out->worst_particle = r.worst == 0x7fffffff ? -1 : r.worst;
+    out->pairs = r.pairs; out->over = r.over;
+    out->max_distance = r.worst == 0x7fffffff ? 0.0 : std::sqrt(max_d2);
+    out->sum_d2 = r.sum_d2;
+    std::copy(r.dipole, r.dipole + 3, out->dipole);
+    std::copy(r.hist, r.hist + TGNH_DRUDE_HIST_BINS + 1, out->hist);
+    return TGNH_OK;
+}
+
 // ---------------------------------------------------------------------------
 // timing / roofline bookkeeping
 // ---------------------------------------------------------------------------

@@ -681,11 +681,8 @@ extern "C" tgnh_status tgnh_set_velocities_to_temperature(tgnh_handle h, double 
     if (first_particle < 0) return fail(TGNH_ERR_ARG, "tgnh_set_velocities_to_temperature: negative first_particle");
     rc = entry(h, true); if (rc) return rc;                     // (buffers bound, not a host-only handle)
     rc = tgnh_state_changed(h); if (rc) return rc;
-    const int* partner = h->gather.d_partner;
-    if (!partner) {                                              // a tiled handle: the gather path's table, from the pair lists, once
-        if (!h->velinit.d_partner) HIP_OK(h->velinit.d_partner.upload(partner_table(h)));
-        partner = h->velinit.d_partner;
-    }
+    const int* partner = nullptr;
+    rc = device_partner_table(h, &partner); if (rc) return rc;
     Timed t(h, (hipStream_t)stream, KID_OTHER);
     HIP_OK(launch_velinit(h->d.precision, h->bound.velm, partner, h->d.num_particles, h->d.kB * temperature, h->d.kB * drude_temperature,
                           (unsigned long long)seed, (long long)first_particle, (hipStream_t)stream));

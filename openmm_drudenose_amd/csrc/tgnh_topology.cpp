@@ -20,6 +20,13 @@ std::vector<int> partner_table(const tgnh_context* c) {
     }
     return t;
 }
+// ... on the device, for the passes by global index (GatherArgs::partner): the gather path's own table where the handle has one,
+// else one built from the pair lists at the first call and kept.  The handle's device is current (entry).
+tgnh_status device_partner_table(tgnh_context* c, const int** out) {
+    if (!c->gather.d_partner && !c->by_index.d_partner) HIP_OK(c->by_index.d_partner.upload(partner_table(c)));
+    *out = c->gather.d_partner ? c->gather.d_partner : c->by_index.d_partner;
+    return TGNH_OK;
+}
 
 static tgnh_status build_gather_topology(tgnh_context* c, const std::vector<int>& res_order) {
     const tgnh_desc& d = c->d;

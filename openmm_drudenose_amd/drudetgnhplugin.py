@@ -272,6 +272,36 @@ class HostTopology(_HandleQueries):
             pass
 
 
+class DrudeStatistics:
+    """What HipContext.drude_statistics returns (read-only): pairs, over (pairs beyond `threshold`), max_distance and rms_distance
+    (nm), worst_particle (slot of the Drude particle of the longest pair, -1: no pair), induced_dipole (e nm, 3 values), hist
+    (int64, 33 values: 32 bins of width hist_max / 32, then the pairs at or beyond hist_max; zeros when hist_max == 0) and
+    hist_edges (the 33 edges of the 32 bins; None when hist_max == 0)."""
+    __slots__ = ("pairs", "over", "max_distance", "rms_distance", "worst_particle", "induced_dipole", "hist", "hist_edges",
+                 "sum_d2", "threshold", "hist_max", "raw")
+
+    def __init__(self, st, threshold, hist_max):
+        put = lambda k, v: object.__setattr__(self, k, v)    # noqa: E731
+        put("raw", bytes(st))                                # the struct as the library filled it in
+        put("pairs", int(st.pairs)); put("over", int(st.over)); put("worst_particle", int(st.worst_particle))
+        put("max_distance", float(st.max_distance)); put("sum_d2", float(st.sum_d2))
+        put("rms_distance", float(np.sqrt(st.sum_d2 / st.pairs)) if st.pairs else 0.0)
+        put("threshold", threshold); put("hist_max", hist_max)
+        arrays = {"induced_dipole": np.array(st.dipole[:], np.float64), "hist": np.array(st.hist[:], np.int64),
+                  "hist_edges": np.linspace(0.0, hist_max, _lib.DRUDE_HIST_BINS + 1) if hist_max > 0 else None}
+        for k, v in arrays.items():
+            if v is not None:
+                v.setflags(write=False)
+            put(k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("DrudeStatistics is read-only")
+
+    def __repr__(self):
+        return (f"DrudeStatistics(pairs={self.pairs}, over={self.over}, max_distance={self.max_distance:.6g}, "
+                f"rms_distance={self.rms_distance:.6g}, worst_particle={self.worst_particle}, induced_dipole={self.induced_dipole.tolist()})")
+
+
 class HipContext(_HandleQueries):
     """Device state + handle: what OpenMM's Context / HIP platform data are to the reference kernel.
 
@@ -594,6 +624,10 @@ class HipContext(_HandleQueries):
         if self._has_clusters:
             _check(self.lib.tgnh_harness_shake_velocities(self.h, self.integrator.getConstraintTolerance(), self._stream()))
 
+    def setCharges(self, q):
+        """posq.w of every slot (OpenMM keeps the charge there; setPositions leaves it alone).  No step kernel reads it."""
+        self.posq[:, 3] = self.torch.from_numpy(np.ascontiguousarray(q, np.float64)).to(self.dev, self.rdt)
+
     def _state_changed(self):                                # DrudeTGNHIntegrator.cpp:166-170
         self.ke_sum_valid = False
         _check(self.lib.tgnh_state_changed(self.h))
@@ -793,6 +827,17 @@ class HipContext(_HandleQueries):
         out = C.c_double()
         _check(self.lib.tgnh_get_kinetic_energy(self.h, int(self.ke_sum_valid), self._stream(), C.byref(out)))
         return out.value
+
+    def drude_statistics(self, threshold=None, hist_max=0.0):
+        """tgnh_get_drude_statistics: the Drude-parent distances and the induced dipole of the positions as they are, summed on
+        the device (no copy of the positions, no flush).  threshold=None: the integrator's getMaxDrudeDistance().  Synchronises
+        the stream.  In a sharded run every context answers for its own slots (see include/drude_tgnh.h for what adds up)."""
+        if threshold is None:
+            threshold = self.integrator.getMaxDrudeDistance()
+        st = _lib.TgnhDrudeStats()
+        st.struct_size = C.sizeof(st)
+        _check(self.lib.tgnh_get_drude_statistics(self.h, float(threshold), float(hist_max), self._stream(), C.byref(st)))
+        return DrudeStatistics(st, float(threshold), float(hist_max))
 
     def time(self):
         t, k = C.c_double(), C.c_int64()
