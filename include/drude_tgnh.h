@@ -304,7 +304,7 @@ tgnh_status tgnh_state_changed(tgnh_handle h);
  * (the fourth normal is discarded).  Everything is computed in fp64 and stored in velm's type.  No state is kept between calls
  * and nothing depends on tiling, step path, grid, device or sharding: a particle gets the same velocity wherever and however
  * it is generated.  dualNH and TGNH handles draw alike (temperature groups play no part).
- * NOT done, as in OpenMM: no removal of the total momentum, no rescale to the exact target, no constraint projection (under
+ * NOT done, as in OpenMM: no removal of the total momentum (tgnh_remove_cm_motion afterwards does that), no rescale to the exact target, no constraint projection (under
  * constraints run the velocity-constraint call-out afterwards).
  * The call is a setVelocities: before anything is written it does what tgnh_state_changed does -- refused with that call's
  * status between the steps of a TGNH_FLAG_DEFER_SCALE sequence (velm untouched); afterwards bit 9 of tgnh_get_pending_state is
@@ -313,6 +313,65 @@ tgnh_status tgnh_state_changed(tgnh_handle h);
  * buffers not bound, a host-only handle. */
 tgnh_status tgnh_set_velocities_to_temperature(tgnh_handle h, double temperature, double drude_temperature,
                                                uint64_t seed, int64_t first_particle, void* stream);
+
+/* Centre-of-mass motion: the total mass and momentum of the bound velocities, and their removal (OpenMM's CMMotionRemover).
+ * tgnh_desc.has_cm_motion_remover only takes the three degrees of freedom off the thermostats; these calls do the removing -- for
+ * a host without OpenMM, for a particle-sharded run (no component outside the library sees every rank's momentum), and after
+ * tgnh_set_velocities_to_temperature, which leaves a net momentum of order sqrt(N) thermal momenta in the box.
+ * Per slot of the bound velm, everything in fp64, each product and each sum rounded on its own (no fused multiply-add):
+ *   massive slot (w != 0)    m = 1.0 / (double)w;   the slot adds m to M and m (double)vx, m (double)vy, m (double)vz to P
+ *   massless slot (w == 0)   adds nothing, is not counted in `massive`, and is never written
+ *   v_cm = P / M (three IEEE divisions);   removal / shift:  v' = (type of velm)((double)v - d), d = v_cm or dv, rounded once;
+ *   w is stored back bit for bit.  M == 0 (no massive slot): nothing is written.
+ * Reproducible as the header's rules above have it: no floating-point atomic; the grid of the summing pass is a function of
+ * num_particles alone (ceil(N / 256) work-groups, at most 1024, a grid-stride loop beyond) and every order of additions is fixed by
+ * it -- a thread adds its slots in ascending index order, a wavefront its lanes, a work-group its wavefronts and one work-group the
+ * rows, each in a fixed order -- so the same velm gives the same bits from any handle over the same slots: tiled or TGNH_FLAG_GATHER,
+ * dualNH or TGNH, whatever the flags, asked once or twice.  Every thread of the shift divides the same P by the same M.
+ *
+ * tgnh_get_momentum: a query.  Like tgnh_get_kinetic_energy it first applies what a step has left owed to velm (tgnh_flush); it
+ * changes nothing else of the trajectory and leaves the sweep direction as it found it.  It synchronises `stream` and follows
+ * tgnh_get_status_flags' rule for sticky failures.  SHARDED RUNS: the answer is for THIS handle's slots; mass, momentum and massive
+ * are additive over ranks.  TGNH_ERR_ARG: out is NULL or out->struct_size is not sizeof(tgnh_momentum) (set it before the call;
+ * nothing else of *out is read, and on an error nothing of it is written).  TGNH_ERR_STATE: buffers not bound, a host-only handle.
+ *
+ * tgnh_remove_cm_motion: v' = v - v_cm for every massive slot.  A setVelocities: before anything is written it does what
+ * tgnh_state_changed does -- refused with that call's status where that call is refused (between the steps of a
+ * TGNH_FLAG_DEFER_SCALE sequence; velm untouched) -- and afterwards bit 9 of tgnh_get_pending_state is clear and a cached
+ * kinetic-energy sum is stale (ke_sum_valid = 0).  It enqueues, on `stream` and without waiting for the device: the summing pass,
+ * the sum of its rows, then -- SHARDED RUNS -- the four doubles {M, Px, Py, Pz} through the all-reduce of tgnh_set_allreduce or the
+ * library's own RCCL (count 4, in place, the same call that carries the kinetic-energy sums; collective: every rank calls this
+ * between the same two steps), and the shift.  Every rank then divides the same sums: the same v_cm bits everywhere.  Capturable
+ * into a hipGraph like every launch of a step (the first call on a handle allocates a few KiB of scratch: make it, or
+ * tgnh_set_cm_motion_removal, outside the capture).  With a MAILBOX exchange attached: TGNH_ERR_UNSUPPORTED -- the mailboxes carry
+ * the kinetic-energy sums only; such a caller takes tgnh_get_momentum on every rank, adds the sums by its own means and calls
+ * tgnh_shift_velocities with the same dv on every rank.  TGNH_ERR_STATE: buffers not bound, a host-only handle.
+ *
+ * tgnh_shift_velocities: v' = v - dv for every massive slot, one launch.  Refuses and invalidates as tgnh_remove_cm_motion does (a
+ * mailbox exchange does not refuse it).  TGNH_ERR_ARG: dv is NULL or a component is not finite.  dv is read before the call returns.
+ *
+ * tgnh_set_cm_motion_removal(every): a CMMotionRemover inside the step loops.  every = 0 (the default): off.  every > 0:
+ * tgnh_step_begin and tgnh_step_begin_kick look at the step count (tgnh_get_time) BEFORE the step; if it is a multiple of `every`
+ * they enqueue tgnh_remove_cm_motion's launches before their own first launch and drop the kinetic energies carried under
+ * TGNH_FLAG_TRUST_STATE_CHANGED.  So tgnh_run_harness, tgnh_run_harness_constrained, tgnh_run_steps and any loop over the step
+ * entry points remove the drift every `every` steps.  (This is believed to be the step at which OpenMM's CMMotionRemover acts --
+ * in updateContextState, ahead of the integrator's step, when the step count is a multiple of its frequency; OpenMM was not at
+ * hand to check against.)  Inside OpenMM leave it off: the System's own CMMotionRemover keeps acting there.  SHARDED RUNS: every
+ * rank sets the same value.  A hipGraph of steps bakes in the removals of the steps it recorded: record a multiple of `every`
+ * steps, from a step count that is one.  TGNH_ERR_ARG: every < 0.  TGNH_ERR_UNSUPPORTED: every > 0 on a handle that steps with
+ * TGNH_FLAG_DEFER_SCALE (its velocities lag between steps) or has a mailbox exchange attached; and tgnh_exchange_attach /
+ * _attach_pointers return it while removal is on. */
+typedef struct tgnh_momentum {
+    uint32_t struct_size;     /* in: sizeof(tgnh_momentum); anything else: TGNH_ERR_ARG */
+    int32_t  reserved;        /* out: 0 */
+    int64_t  massive;         /* slots with w != 0 */
+    double   mass;            /* M */
+    double   momentum[3];     /* P */
+} tgnh_momentum;
+tgnh_status tgnh_get_momentum(tgnh_handle h, void* stream, tgnh_momentum* out);
+tgnh_status tgnh_shift_velocities(tgnh_handle h, const double dv[3], void* stream);
+tgnh_status tgnh_remove_cm_motion(tgnh_handle h, void* stream);
+tgnh_status tgnh_set_cm_motion_removal(tgnh_handle h, int every);
 
 /* Retargets both baths of a live handle (heating, annealing, equilibration at one temperature and production at another):
  * kB T and kB T_D -- the chain's launch arguments and the hard wall's thermal speed --, every N kT and every thermostat mass,
@@ -462,7 +521,8 @@ tgnh_status tgnh_run_harness_constrained(tgnh_handle h, const void* x0, double k
 /* The call-outs of the reference's own testWater (platforms/reference/tests/TestReferenceDrudeTGNHIntegrator.cpp:111-166),
  * harness only: its force field -- NonbondedForce with reaction field, cutoff `cutoff` in a cubic box of edge `box`, +
  * DrudeForce + the M site's force spread over O, H1, H2, for slots laid out O, D, H1, H2, M per molecule -- written into
- * `force_out` in OpenMM's fixed-point layout, and OpenMM's CMMotionRemover on the bound velocities. */
+ * `force_out` in OpenMM's fixed-point layout, and OpenMM's CMMotionRemover on the bound velocities (one work-group, sized for
+ * that test's 216 molecules and not for product use: tgnh_remove_cm_motion is the library's). */
 tgnh_status tgnh_harness_water_force(tgnh_handle h, double box, double cutoff, void* force_out, void* stream);
 tgnh_status tgnh_harness_remove_cm_motion(tgnh_handle h, void* stream);
 

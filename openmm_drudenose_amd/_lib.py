@@ -46,6 +46,14 @@ class TgnhDrudeStats(C.Structure):
     ]
 
 
+class TgnhMomentum(C.Structure):
+    """tgnh_momentum (tgnh_get_momentum)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("reserved", C.c_int32), ("massive", C.c_int64), ("mass", C.c_double),
+        ("momentum", C.c_double * 3),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p)
 
 # name -> (restype, argtypes); every symbol include/drude_tgnh.h declares
@@ -85,6 +93,11 @@ SIGNATURES = {
     "tgnh_state_changed": (C.c_int, [C.c_void_p]),
     # (seed: uint64_t in the header, handed over as the same 64 bits)
     "tgnh_set_velocities_to_temperature": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int64, C.c_int64, C.c_void_p]),
+    # (out: a TgnhMomentum by reference)
+    "tgnh_get_momentum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tgnh_shift_velocities": (C.c_int, [C.c_void_p, c_f64p, C.c_void_p]),
+    "tgnh_remove_cm_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tgnh_set_cm_motion_removal": (C.c_int, [C.c_void_p, C.c_int]),
     "tgnh_set_temperatures": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "tgnh_note_replayed_steps": (C.c_int, [C.c_void_p, C.c_int]),
     "tgnh_set_time": (C.c_int, [C.c_void_p, C.c_double, C.c_int64]),

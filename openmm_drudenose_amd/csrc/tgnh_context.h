@@ -90,6 +90,12 @@ struct tgnh_context {
         int rows_allocated = 0;
         tgnh::DrudeStatsRow h_row{};      // where the result lands on the host
     } dstats;
+    struct CmMotion {                 // tgnh_get_momentum / tgnh_shift_velocities / tgnh_remove_cm_motion: allocated at the first call that launches
+        tgnh::DeviceBuf<tgnh::CmRow> d_rows;           // (or at tgnh_set_cm_motion_removal: never inside somebody's stream capture)
+        int rows_allocated = 0;           // [rows_allocated]: a row per work-group of the pass, then the result
+        tgnh::CmRow h_row{};              // where the result lands on the host
+        int every = 0;                    // tgnh_set_cm_motion_removal: remove before every step whose number is a multiple of this (0: never)
+    } cmm;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block
         std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction

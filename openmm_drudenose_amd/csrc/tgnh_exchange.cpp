@@ -46,6 +46,14 @@ extern "C" tgnh_status tgnh_exchange_create(tgnh_handle h, int world, int rank, 
     return TGNH_OK;
 }
 
+// the mailboxes carry the kinetic-energy sums only: a handle that removes its centre-of-mass motion inside the step loop
+// (tgnh_set_cm_motion_removal) has no exchange for the momentum sums once they replace the hook
+static tgnh_status cm_removal_off(tgnh_handle h, const char* what) {
+    if (h->cmm.every > 0)
+        return fail(TGNH_ERR_UNSUPPORTED, std::string(what) + ": centre-of-mass removal is on (tgnh_set_cm_motion_removal(h, 0) first)");
+    return TGNH_OK;
+}
+
 static tgnh_status exchange_finish_attach(tgnh_handle h, const std::vector<unsigned long long*>& peers) {
     HIP_OK(hipMemcpy(h->xchg.d_peers, peers.data(), sizeof(unsigned long long*) * peers.size(), hipMemcpyHostToDevice));
     h->xchg.args = XchgArgs{};
@@ -61,7 +69,8 @@ extern "C" tgnh_status tgnh_exchange_attach(tgnh_handle h, const void* ipc_handl
     CHECK_H(h);
     if (!h->xchg.mailbox) return fail(TGNH_ERR_STATE, "tgnh_exchange_create first");
     if (!ipc_handles) return fail(TGNH_ERR_ARG, "null handles");
-    tgnh_status rc = deferred_guard(h, "tgnh_exchange_attach"); if (rc) return rc;
+    tgnh_status rc = cm_removal_off(h, "tgnh_exchange_attach"); if (rc) return rc;
+    rc = deferred_guard(h, "tgnh_exchange_attach"); if (rc) return rc;
     h->owed.ke_carry = false;
     HIP_OK(hipSetDevice(h->device));
     std::vector<unsigned long long*> peers(h->xchg.world, nullptr);
@@ -81,7 +90,8 @@ extern "C" tgnh_status tgnh_exchange_attach_pointers(tgnh_handle h, void* const*
     CHECK_H(h);
     if (!h->xchg.mailbox) return fail(TGNH_ERR_STATE, "tgnh_exchange_create first");
     if (!mailboxes) return fail(TGNH_ERR_ARG, "null mailboxes");
-    tgnh_status rc = deferred_guard(h, "tgnh_exchange_attach_pointers"); if (rc) return rc;
+    tgnh_status rc = cm_removal_off(h, "tgnh_exchange_attach_pointers"); if (rc) return rc;
+    rc = deferred_guard(h, "tgnh_exchange_attach_pointers"); if (rc) return rc;
     h->owed.ke_carry = false;
     HIP_OK(hipSetDevice(h->device));
     std::vector<unsigned long long*> peers(h->xchg.world, nullptr);

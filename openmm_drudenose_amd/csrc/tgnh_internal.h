@@ -354,6 +354,18 @@ struct DrudeStatsRow {
 inline int drude_stats_grid(int n) { const long long g = ((long long)n + BLOCK - 1) / BLOCK; return (int)(g < DRUDE_STATS_GRID_CAP ? g : DRUDE_STATS_GRID_CAP); }
 hipError_t launch_drude_stats(int precision, const void* posq, const void* posq_corr, const int* partner, int n, double threshold,
                               double hist_max, DrudeStatsRow* rows /*[grid + 1]: the work-groups' rows, then the result*/, int grid, hipStream_t s);
+// Centre-of-mass motion (tgnh_cm_motion.hip): a read-only pass by global index over velm, one row per work-group, then one work-group
+// that adds the rows into rows[grid]; and the pass that subtracts P / M -- read from `sums` = {M, Px, Py, Pz} on the device, where an
+// all-reduce may have added the other ranks' in between -- or the explicit dv[3] (host; sums == nullptr) from every massive slot.
+// The grid is a function of n alone, by drude_stats_grid's rule.
+constexpr int CM_GRID_CAP = 1024;
+struct CmRow {
+    double mass, p[3];                       // (the four doubles an all-reduce sums in place: contiguous, first)
+    long long massive;                       // slots with w != 0
+};
+inline int cm_grid(int n) { const long long g = ((long long)n + BLOCK - 1) / BLOCK; return (int)(g < CM_GRID_CAP ? g : CM_GRID_CAP); }
+hipError_t launch_cm_momentum(int precision, const void* velm, int n, CmRow* rows /*[grid + 1]: the work-groups' rows, then the result*/, int grid, hipStream_t s);
+hipError_t launch_cm_shift(int precision, void* velm, int n, const double* sums, const double* dv, int grid, hipStream_t s);
 
 }  // namespace tgnh
 

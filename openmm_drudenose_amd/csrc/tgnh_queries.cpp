@@ -224,6 +224,37 @@ extern "C" tgnh_status tgnh_get_drude_statistics(tgnh_handle h, double threshold
     return TGNH_OK;
 }
 
+// Total mass and momentum of this handle's slots (include/drude_tgnh.h has the contract; tgnh_cm_motion.hip the kernels).  A query
+// of the velocities, so what a step has left owed to velm is applied first, as tgnh_get_kinetic_energy does; the sweep direction is
+// left as it was found.
+extern "C" tgnh_status tgnh_get_momentum(tgnh_handle h, void* stream, tgnh_momentum* out) {
+    CHECK_H(h);
+    if (!out) return fail(TGNH_ERR_ARG, "null out");
+    if (out->struct_size != sizeof(tgnh_momentum)) return fail(TGNH_ERR_ARG, "tgnh_momentum size mismatch (ABI)");
+    tgnh_status rc = entry(h, true); if (rc) return rc;          // (buffers bound, not a host-only handle, no failure seen before)
+    hipStream_t s = (hipStream_t)stream;
+    const int dir = h->run.sweep_reverse;
+    rc = flush_impl(h, s);
+    h->run.sweep_reverse = dir;
+    if (rc) return rc;
+    CmRow& r = h->cmm.h_row;                                     // (the handle's: a copy still in flight when an error returns lands in live memory)
+    r = CmRow{};
+    CmRow* sums = nullptr;
+    {
+        Timed t(h, s, KID_OTHER);
+        rc = cm_momentum_launches(h, s, &sums); if (rc) return rc;
+    }
+    HIP_OK(hipMemcpyAsync(&r, sums, sizeof(r), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(h->status.h_seen, h->status.d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    note_status(h, *h->status.h_seen);
+    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);
+    out->reserved = 0;
+    out->massive = r.massive; out->mass = r.mass;
+    std::copy(r.p, r.p + 3, out->momentum);
+    return TGNH_OK;
+}
+
 // ---------------------------------------------------------------------------
 // timing / roofline bookkeeping
 // ---------------------------------------------------------------------------

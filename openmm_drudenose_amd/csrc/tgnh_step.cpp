@@ -1,4 +1,4 @@
-// tgnh_step.cpp -- step orchestration (A11): device-reported failures, the launch decisions by name, launch sizing, run_tile / run_gather / run_chain / run_resident, tgnh_step_*, flush, clock
+// tgnh_step.cpp -- step orchestration (A11): device-reported failures, the launch decisions by name, launch sizing, run_tile / run_gather / run_chain / run_resident, centre-of-mass removal, tgnh_step_*, flush, clock
 #include "tgnh_host.h"
 
 // ---------------------------------------------------------------------------
@@ -509,9 +509,87 @@ static tgnh_status advance_clock(tgnh_handle h, hipStream_t s) {
     return poll_status_async(h, s);
 }
 
+// ---------------------------------------------------------------------------
+// centre-of-mass motion (include/drude_tgnh.h has the contract; tgnh_cm_motion.hip the kernels)
+// ---------------------------------------------------------------------------
+tgnh_status cm_scratch(tgnh_handle h) {
+    const int grid = cm_grid(h->d.num_particles);
+    if (!h->cmm.d_rows) {
+        HIP_OK(h->cmm.d_rows.alloc((size_t)grid + 1));           // (every row is written by the pass before anybody reads it)
+        h->cmm.rows_allocated = grid + 1;
+    }
+    if (grid < 1 || grid > CM_GRID_CAP || grid + 1 > h->cmm.rows_allocated)
+        return fail(TGNH_ERR_STATE, "internal: the momentum pass's grid exceeds its rows");
+    return TGNH_OK;
+}
+
+tgnh_status cm_momentum_launches(tgnh_handle h, hipStream_t s, CmRow** result) {
+    tgnh_status rc = cm_scratch(h); if (rc) return rc;
+    const int grid = cm_grid(h->d.num_particles);
+    HIP_OK(launch_cm_momentum(h->d.precision, h->bound.velm, h->d.num_particles, h->cmm.d_rows, grid, s));
+    *result = h->cmm.d_rows + grid;
+    return TGNH_OK;
+}
+
+// momentum pass, row sum, the ranks' four sums added in place where an all-reduce is set (a caller's hook or the library's own
+// RCCL, which is installed as that hook), shift.  Nothing here waits for the device.  The caller has seen to tgnh_state_changed.
+static tgnh_status cm_removal_launches(tgnh_handle h, hipStream_t s) {
+    if (h->xchg.on) return fail(TGNH_ERR_UNSUPPORTED, "centre-of-mass removal with a mailbox exchange attached: the mailboxes carry the kinetic-energy sums only "
+                                                      "(tgnh_get_momentum on every rank, add the sums, tgnh_shift_velocities with the same dv everywhere)");
+    CmRow* sums = nullptr;
+    Timed t(h, s, KID_OTHER);
+    tgnh_status rc = cm_momentum_launches(h, s, &sums); if (rc) return rc;
+    if (h->xchg.allreduce && h->xchg.allreduce(&sums->mass, 4, (void*)s, h->xchg.allreduce_user) != 0)
+        return fail(TGNH_ERR_HIP, "all-reduce hook failed");
+    HIP_OK(launch_cm_shift(h->d.precision, h->bound.velm, h->d.num_particles, &sums->mass, nullptr, cm_grid(h->d.num_particles), s));
+    return TGNH_OK;
+}
+
+// tgnh_set_cm_motion_removal: before the step whose number is a multiple of `every`, and before that step's own first launch.
+// Such a handle never lags (the setter refuses DEFER_SCALE), so tgnh_state_changed's effect is all there is to do.
+static tgnh_status cm_removal_due(tgnh_handle h, hipStream_t s) {
+    if (h->cmm.every <= 0 || h->run.step_count % h->cmm.every != 0) return TGNH_OK;
+    h->owed.ke_carry = false;
+    return cm_removal_launches(h, s);
+}
+
+extern "C" tgnh_status tgnh_remove_cm_motion(tgnh_handle h, void* stream) {
+    tgnh_status rc = entry(h, true); if (rc) return rc;           // (buffers bound, not a host-only handle, no failure seen before)
+    rc = tgnh_state_changed(h); if (rc) return rc;              // (first: refused between the steps of a deferred sequence, and then nothing is written)
+    return cm_removal_launches(h, (hipStream_t)stream);
+}
+
+extern "C" tgnh_status tgnh_shift_velocities(tgnh_handle h, const double dv[3], void* stream) {
+    CHECK_H(h);
+    if (!dv) return fail(TGNH_ERR_ARG, "tgnh_shift_velocities: null dv");
+    if (!std::isfinite(dv[0]) || !std::isfinite(dv[1]) || !std::isfinite(dv[2])) return fail(TGNH_ERR_ARG, "tgnh_shift_velocities: dv is not finite");
+    tgnh_status rc = entry(h, true); if (rc) return rc;
+    rc = tgnh_state_changed(h); if (rc) return rc;
+    Timed t(h, (hipStream_t)stream, KID_OTHER);
+    HIP_OK(launch_cm_shift(h->d.precision, h->bound.velm, h->d.num_particles, nullptr, dv, cm_grid(h->d.num_particles), (hipStream_t)stream));
+    return TGNH_OK;
+}
+
+extern "C" tgnh_status tgnh_set_cm_motion_removal(tgnh_handle h, int every) {
+    CHECK_H(h);
+    if (every < 0) return fail(TGNH_ERR_ARG, "tgnh_set_cm_motion_removal: negative interval");
+    if (every > 0) {
+        if (h->d.flags & TGNH_FLAG_DEFER_SCALE)
+            return fail(TGNH_ERR_UNSUPPORTED, "tgnh_set_cm_motion_removal: velocities lag between the steps of a TGNH_FLAG_DEFER_SCALE handle");
+        if (h->xchg.on) return fail(TGNH_ERR_UNSUPPORTED, "tgnh_set_cm_motion_removal: a mailbox exchange is attached (it carries the kinetic-energy sums only)");
+        if (!h->host_only) {                                    // the scratch now: the first removal may be enqueued inside a stream capture
+            HIP_OK(hipSetDevice(h->device));
+            tgnh_status rc = cm_scratch(h); if (rc) return rc;
+        }
+    }
+    h->cmm.every = every;
+    return TGNH_OK;
+}
+
 extern "C" tgnh_status tgnh_step_begin(tgnh_handle h, void* stream) {
     tgnh_status rc = entry(h, true); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
+    rc = cm_removal_due(h, s); if (rc) return rc;
     start_of_step(h);
     if (h->owed.end_pending) {
         if (resident_now(h)) return run_resident(h, s, 0);           // the last step's end half and this begin half: one launch
@@ -593,6 +671,7 @@ static tgnh_status split_entry(tgnh_handle h, hipStream_t s, bool fresh_ke) {
 extern "C" tgnh_status tgnh_step_begin_kick(tgnh_handle h, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     tgnh_status rc = split_entry(h, s, false); if (rc) return rc;
+    rc = cm_removal_due(h, s); if (rc) return rc;
     start_of_step(h);
     if (!(h->d.flags & TGNH_FLAG_DEFER_SCALE) && resident_now(h) && !h->owed.ke_carry) return run_resident(h, s, 3);
     rc = first_half(h, s); if (rc) return rc;

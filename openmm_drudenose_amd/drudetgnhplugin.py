@@ -302,15 +302,39 @@ class DrudeStatistics:
                 f"rms_distance={self.rms_distance:.6g}, worst_particle={self.worst_particle}, induced_dipole={self.induced_dipole.tolist()})")
 
 
+class Momentum:
+    """What HipContext.momentum returns (read-only): mass (amu) and momentum (amu nm/ps, 3 values) of the context's massive slots,
+    massive (their number) and velocity = momentum / mass, the centre-of-mass velocity (zeros when there is no mass)."""
+    __slots__ = ("mass", "momentum", "massive", "velocity", "raw")
+
+    def __init__(self, st):
+        put = lambda k, v: object.__setattr__(self, k, v)    # noqa: E731
+        put("raw", bytes(st))                                # the struct as the library filled it in
+        put("mass", float(st.mass)); put("massive", int(st.massive))
+        p = np.array(st.momentum[:], np.float64)
+        v = p / st.mass if st.mass != 0 else np.zeros(3)
+        for k, a in (("momentum", p), ("velocity", v)):
+            a.setflags(write=False)
+            put(k, a)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Momentum is read-only")
+
+    def __repr__(self):
+        return f"Momentum(mass={self.mass:.6g}, momentum={self.momentum.tolist()}, massive={self.massive}, velocity={self.velocity.tolist()})"
+
+
 class HipContext(_HandleQueries):
     """Device state + handle: what OpenMM's Context / HIP platform data are to the reference kernel.
 
     force_fn(ctx) is the force call-out (calcForcesAndEnergy); the default is the
     harness force (Drude spring + tether) computed by the library's own kernel.
+    cm_motion_removal: None = no centre-of-mass removal inside the step loops, whatever system.has_cm_motion_remover says (that
+    flag only takes three degrees of freedom off the thermostats); an integer = tgnh_set_cm_motion_removal(every).
     """
 
     def __init__(self, system, integrator, mode="TGNH", precision="mixed", device=0, flags=0, kB=KB,
-                 k_drude=None, k_tether=None, allreduce=None, global_dof_sum=None, lattice_sites=True):
+                 k_drude=None, k_tether=None, allreduce=None, global_dof_sum=None, lattice_sites=True, cm_motion_removal=None):
         import torch
         self.torch = torch
         self.lib = _lib.load()
@@ -336,7 +360,11 @@ class HipContext(_HandleQueries):
         self._bath_epoch = 0
         self.first_particle = 0                              # a shard: the index of its first slot in the whole system (setVelocitiesToTemperature)
         self._hook = None
-        if global_dof_sum is not None:                       # particle sharding: dof terms are additive over ranks
+        self.cm_motion_removal = 0
+        if cm_motion_removal is not None:
+            with torch.cuda.device(self.dev):
+                self.set_cm_motion_removal(cm_motion_removal)
+        if global_dof_sum is not None:                      # particle sharding: dof terms are additive over ranks
             self.set_global_dof_terms(global_dof_sum(self.local_dof_terms()))
         if allreduce is not None:
             self.set_allreduce(allreduce)
@@ -605,12 +633,43 @@ class HipContext(_HandleQueries):
         self._state_changed()                                # (first: refused between the steps of a deferred sequence, and then nothing is written)
         self.velm[:, :3] = self.torch.from_numpy(np.ascontiguousarray(vel, np.float64)).to(self.dev, self.mdt)
 
-    def setVelocitiesToTemperature(self, temperature, randomSeed=None, drudeTemperature=None):
+    # ---- centre-of-mass motion (include/drude_tgnh.h: tgnh_get_momentum, tgnh_remove_cm_motion, ...) ----
+    def momentum(self):
+        """tgnh_get_momentum: total mass and momentum of this context's slots, summed on the device (what a step left owed to the
+        velocities is applied first).  Synchronises the stream.  In a sharded run every context answers for its own slots; the
+        fields add up over ranks."""
+        st = _lib.TgnhMomentum()
+        st.struct_size = C.sizeof(st)
+        _check(self.lib.tgnh_get_momentum(self.h, self._stream(), C.byref(st)))
+        return Momentum(st)
+
+    def removeCMMotion(self):
+        """tgnh_remove_cm_motion: v -= P / M on every massive slot, on the device and without a host synchronisation; with an
+        all-reduce set (set_allreduce, rccl_init) P and M are the whole system's, and the call is collective."""
+        _check(self.lib.tgnh_remove_cm_motion(self.h, self._stream()))
+        self.ke_sum_valid = False
+
+    def shift_velocities(self, dv):
+        """tgnh_shift_velocities: v -= dv on every massive slot."""
+        dv = np.ascontiguousarray(dv, np.float64)
+        if dv.shape != (3,):
+            raise TgnhError(_lib.ERR_ARG, "shift_velocities: dv must have three components")
+        _check(self.lib.tgnh_shift_velocities(self.h, dv.ctypes.data_as(_lib.c_f64p), self._stream()))
+        self.ke_sum_valid = False
+
+    def set_cm_motion_removal(self, every):
+        """tgnh_set_cm_motion_removal: remove the centre-of-mass motion before every step whose number is a multiple of `every`
+        (0: off), inside step() and whatever else runs the step entry points."""
+        _check(self.lib.tgnh_set_cm_motion_removal(self.h, int(every)))
+        self.cm_motion_removal = int(every)
+
+    def setVelocitiesToTemperature(self, temperature, randomSeed=None, drudeTemperature=None, removeCMMotion=False):
         """OpenMM's Context.setVelocitiesToTemperature, Drude-aware and drawn on the device (tgnh_set_velocities_to_temperature):
         pair centres of mass and ordinary particles at `temperature`, the relative Drude motion at `drudeTemperature` (default:
         the integrator's).  randomSeed=None takes one from os.urandom; the same seed gives the same velocities on any handle,
         path or sharding (self.first_particle places a shard in the whole system).  With constraint clusters set, the harness'
-        velocity-constraint stage runs afterwards, as OpenMM projects after its draw."""
+        velocity-constraint stage runs afterwards, as OpenMM projects after its draw.  removeCMMotion=True takes the net momentum
+        the draw leaves (of order sqrt(N) thermal momenta) off again, last of all (removeCMMotion())."""
         if drudeTemperature is None:
             drudeTemperature = self.integrator.getDrudeTemperature()
         if randomSeed is None:
@@ -623,6 +682,8 @@ class HipContext(_HandleQueries):
         self.ke_sum_valid = False
         if self._has_clusters:
             _check(self.lib.tgnh_harness_shake_velocities(self.h, self.integrator.getConstraintTolerance(), self._stream()))
+        if removeCMMotion:
+            self.removeCMMotion()
 
     def setCharges(self, q):
         """posq.w of every slot (OpenMM keeps the charge there; setPositions leaves it alone).  No step kernel reads it."""
@@ -722,6 +783,12 @@ class HipContext(_HandleQueries):
         torch = self.torch
         if self.force_fn is not None:
             raise TgnhError(_lib.ERR_STATE, "capture_steps supports the harness force call-out only")
+        # A recording bakes in the centre-of-mass removals of the steps it recorded (set_cm_motion_removal): it replays the loop's
+        # own launches only if every replay starts at a multiple of the interval, and so ends at one
+        every = self.cm_motion_removal
+        if every > 0 and (self.time()[1] % every or int(steps) % every):
+            raise TgnhError(_lib.ERR_STATE, f"capture_steps: with centre-of-mass removal every {every} steps, the step count at the "
+                            f"capture ({self.time()[1]}) and the steps captured ({int(steps)}) must both be multiples of it")
         # A graph replays launches, not the decisions that chose them: it may only be replayed from the state it was recorded
         # in.  The first steps of a handle differ from the later ones (nothing pending yet, a staged thermostat block to
         # commit), and so does a step after a query or a split step that settled part of what a step leaves owed.  So the

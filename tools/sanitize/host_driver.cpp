@@ -1,5 +1,6 @@
 // Stand-alone driver of the host-only sanitizer build (run_host_driver_asan.sh): the host side of tgnh_set_temperatures and
-// tgnh_set_velocities_to_temperature through a host-only handle (device -1), no Python in the process.  What needs a device --
+// tgnh_set_velocities_to_temperature, and the argument checks of the centre-of-mass calls, through a host-only handle (device -1),
+// no Python in the process.  What needs a device --
 // the upload of the retargeted block, the partner table's first use and the launch -- is not reached here.
 #include <cmath>
 #include <cstdio>
@@ -48,6 +49,19 @@ static int run(int mode, int chains, int drude_chains) {
     EXPECT(tgnh_set_velocities_to_temperature(a, 300, 1, 1, -1, nullptr) == TGNH_ERR_ARG);
     EXPECT(tgnh_set_velocities_to_temperature(nullptr, 300, 1, 1, 0, nullptr) == TGNH_ERR_ARG);
     EXPECT(tgnh_set_velocities_to_temperature(a, 300, 1, ~0ull, 1ll << 40, nullptr) == TGNH_ERR_STATE);      // host-only: nothing launches
+    // centre-of-mass motion: the argument checks and the host-only refusals (nothing launches, no scratch is allocated)
+    tgnh_momentum mom{};
+    const double dv[3] = {0.1, -0.2, 0.3}, odd[3] = {0.0, NAN, 0.0};
+    EXPECT(tgnh_get_momentum(a, nullptr, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_get_momentum(a, nullptr, &mom) == TGNH_ERR_ARG);                                               // struct_size 0
+    mom.struct_size = sizeof(mom);
+    EXPECT(tgnh_get_momentum(nullptr, nullptr, &mom) == TGNH_ERR_ARG);
+    EXPECT(tgnh_get_momentum(a, nullptr, &mom) == TGNH_ERR_STATE && mom.massive == 0 && mom.mass == 0);
+    EXPECT(tgnh_shift_velocities(a, nullptr, nullptr) == TGNH_ERR_ARG && tgnh_shift_velocities(a, odd, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_shift_velocities(a, dv, nullptr) == TGNH_ERR_STATE && tgnh_remove_cm_motion(a, nullptr) == TGNH_ERR_STATE);
+    EXPECT(tgnh_set_cm_motion_removal(a, -1) == TGNH_ERR_ARG && tgnh_set_cm_motion_removal(nullptr, 1) == TGNH_ERR_ARG);
+    EXPECT(tgnh_set_cm_motion_removal(a, 5) == TGNH_OK && tgnh_step_begin(a, nullptr) == TGNH_ERR_STATE);
+    EXPECT(tgnh_set_cm_motion_removal(a, 0) == TGNH_OK);
     EXPECT(tgnh_destroy(a) == TGNH_OK && tgnh_destroy(b) == TGNH_OK);
     return 0;
 }

@@ -20,6 +20,8 @@ hipError_t launch_plain_ke(int, const void*, const long long*, int, int, double,
 size_t tile_lds_bytes(int, int, bool, bool) { return 0; }
 hipError_t launch_velinit(int, void*, const int*, int, double, double, unsigned long long, long long, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_drude_stats(int, const void*, const void*, const int*, int, double, double, DrudeStatsRow*, int, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_cm_momentum(int, const void*, int, CmRow*, int, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_cm_shift(int, void*, int, const double*, const double*, int, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_gather_com(int, const GatherArgs&, hipStream_t) { return hipErrorNoDevice; }
 int gather_ke_grid(const GatherArgs&) { return 1; }
 hipError_t launch_gather_ke(int, const GatherArgs&, int, hipStream_t) { return hipErrorNoDevice; }
