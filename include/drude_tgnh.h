@@ -304,7 +304,7 @@ tgnh_status tgnh_state_changed(tgnh_handle h);
  * (the fourth normal is discarded).  Everything is computed in fp64 and stored in velm's type.  No state is kept between calls
  * and nothing depends on tiling, step path, grid, device or sharding: a particle gets the same velocity wherever and however
  * it is generated.  dualNH and TGNH handles draw alike (temperature groups play no part).
- * NOT done, as in OpenMM: no removal of the total momentum (tgnh_remove_cm_motion afterwards does that), no rescale to the exact target, no constraint projection (under
+ * NOT done, as in OpenMM: no removal of the total momentum (tgnh_remove_cm_motion afterwards does that), no rescale to the exact target (tgnh_rescale_to_temperature afterwards does that), no constraint projection (under
  * constraints run the velocity-constraint call-out afterwards).
  * The call is a setVelocities: before anything is written it does what tgnh_state_changed does -- refused with that call's
  * status between the steps of a TGNH_FLAG_DEFER_SCALE sequence (velm untouched); afterwards bit 9 of tgnh_get_pending_state is
@@ -372,6 +372,78 @@ tgnh_status tgnh_get_momentum(tgnh_handle h, void* stream, tgnh_momentum* out);
 tgnh_status tgnh_shift_velocities(tgnh_handle h, const double dv[3], void* stream);
 tgnh_status tgnh_remove_cm_motion(tgnh_handle h, void* stream);
 tgnh_status tgnh_set_cm_motion_removal(tgnh_handle h, int every);
+
+/* Velocity rescaling: one factor per thermostat applied to the bound velocities the way the integrator's own rescale applies the
+ * chain's (ReferenceDrudeTGNHKernels.cpp:516-541; CUDA kernel integrateDrudeTGNHChain), and the factors that put every thermostat's
+ * kinetic energy onto its N kT at once -- an exact-temperature start after tgnh_set_velocities_to_temperature, velocity-rescaling
+ * equilibration (a Nose-Hoover chain started far from its target rings for a long time), a replica-exchange swap
+ * (factor sqrt(T_new / T_old) per bath), a quench.  With factors s[NT] in tgnh_get_last_scale_factors' layout -- TGNH
+ * [groups.., COM, Drude], DUALNH [real, unused, Drude]; the unused entry is not looked at:
+ *   TGNH    ordinary slot of group g   v' = s[g] (v - v_com) + s[COM] v_com        v_com: its molecule's centre-of-mass velocity
+ *           pair (group of the Drude)  its centre of mass as an ordinary slot, its relative motion v_parent - v_Drude by s[Drude]
+ *           (COM group off: v_com = 0 and s[COM] plays no part)
+ *   DUALNH  ordinary slot v' = s[real] v;  pair: centre of mass by s[real], relative motion by s[Drude]
+ * This is not a second statement of that arithmetic: the launch IS the step's rescale launch (tiled, wave-tile or gather form,
+ * whichever the handle steps with), reading its factors from scratch of these calls instead of the thermostat block.  Massless
+ * slots and every w stay bit for bit.  The thermostat block is not written: tgnh_get_last_scale_factors keeps answering for the
+ * chain; eta, etaDot and the baths (tgnh_get_dof) stay.
+ *
+ * tgnh_scale_velocities: the caller's factors.  A setVelocities: before anything is written it does what tgnh_state_changed does
+ * -- refused with that call's status where that call is refused (between the steps of a TGNH_FLAG_DEFER_SCALE sequence; velm
+ * untouched) -- and afterwards bit 9 of tgnh_get_pending_state is clear and a cached kinetic-energy sum is stale
+ * (ke_sum_valid = 0).  The sweep direction (bit 8) is left as it was found: a run that never calls this keeps its bits, one that
+ * does is reproducible.  One streaming launch on `stream` (molecules longer than a tile: their centre-of-mass table is computed
+ * before it and again after it), nothing waits for the device.  `factors` is read before the call returns -- the values travel
+ * with a launch, by value: calls enqueued back to back each apply their own, and the caller's array is free at once.  Capturable
+ * into a hipGraph (the first call on a handle allocates 16 NT bytes of scratch: make it, or tgnh_set_velocity_rescaling, outside
+ * the capture).  SHARDED RUNS: every rank passes the same factors.  TGNH_ERR_ARG (checked first, so a host-only handle answers
+ * them): factors is NULL, count is not NT (tgnh_get_num_thermostats), a factor is negative or not finite (0 is legal: exact
+ * zeros).  TGNH_ERR_STATE: buffers not bound, a host-only handle.
+ *
+ * tgnh_rescale_to_temperature: on `stream`, with no host synchronisation in between: the kinetic-energy pass of the velocities
+ * as they are and the sum of its rows (tgnh_compute_kinetic_energies' launches, in the step's own order of additions: a chain
+ * still owed or a staged thermostat block is settled first), the handle's all-reduce where one is set (tgnh_set_allreduce or
+ * the library's RCCL: the same NT-value call the step makes -- SHARDED RUNS: the call is collective, every rank makes it
+ * between the same two steps with the same temperatures), one small kernel that turns sums into factors, and the rescale with them.
+ * Per thermostat k, in fp64, every operation rounded on its own:
+ *   target_k = the N kT tgnh_get_dof would report if the baths stood at (temperature, drude_temperature): formed on the host by
+ *              the functions tgnh_create and tgnh_set_temperatures use, from the handle's (global) degrees of freedom; the
+ *              handle's baths are not touched
+ *   inert thermostat (no degrees of freedom: N kT = 0 at any temperature -- the COM group switched off, DUALNH's unused
+ *              entry, a group without degrees of freedom, the Drude bath of a system without pairs)     s_k = 1
+ *   KE_k is NaN                           s_k = 1, and status bit 4 is set (as by a chain handed a NaN sum)
+ *   KE_k > 0                              s_k = sqrt(target_k / KE_k): one division, one square root (0 when the temperature is 0)
+ *   KE_k == 0                             s_k = 1
+ * KE_k, the sums before scaling (no 1/2), are what tgnh_get_last_kinetic_energies returns afterwards.  Refuses and invalidates as
+ * tgnh_scale_velocities does.  The factors of two handles over the same velocities agree as their kinetic-energy sums do (1e-12
+ * relative between different orders of additions); the same handle asked twice from the same velocities gives the same bits.
+ * A LIMIT: where a molecule spans two temperature groups, unequal factors inside it move its centre of mass, and one call does
+ * not land on the targets -- a box of 27 SWM4 waters with every hydrogen in a second group misses by 12 %.  The call does not
+ * iterate.  (TGNH_FLAG_TRUST_STATE_CHANGED is ignored for such a topology too.)  The same holds where the reference's
+ * centre-of-mass walk does not find a molecule's centre of mass: residues stored in several runs with the COM group on (the
+ * walk takes `count` consecutive particles from a residue's last run; library and oracle follow it).
+ * TGNH_ERR_ARG: a temperature that is negative or not finite.  TGNH_ERR_UNSUPPORTED: a MAILBOX exchange is attached (it carries
+ * the step's own sums); such a caller asks tgnh_compute_kinetic_energies on every rank, forms the factors and calls
+ * tgnh_scale_velocities alike everywhere.  TGNH_ERR_STATE: buffers not bound, a host-only handle.
+ *
+ * tgnh_get_rescale_factors: the NT factors the last of the two calls above applied (from tgnh_set_velocity_rescaling's too).  A
+ * query: synchronises `stream`, follows tgnh_get_status_flags' rule for sticky failures.  TGNH_ERR_STATE: before the first such
+ * call, buffers not bound, a host-only handle.
+ *
+ * tgnh_set_velocity_rescaling(every, temperature, drude_temperature): the same operation inside the step loops, placed as
+ * tgnh_set_cm_motion_removal places the remover.  every = 0 (the default): off.  every > 0: tgnh_step_begin and
+ * tgnh_step_begin_kick look at the step count BEFORE the step; if it is a multiple of `every` they enqueue
+ * tgnh_rescale_to_temperature's launches before their own first launch -- after a centre-of-mass removal due at the same step --
+ * and drop the kinetic energies carried under TGNH_FLAG_TRUST_STATE_CHANGED.  (The step's first thermostat half then runs its own
+ * kinetic-energy pass over the scaled velocities; the scaled sums are not handed on.)  SHARDED RUNS: every rank sets the same
+ * values.  A hipGraph of steps bakes in the rescalings of the steps it recorded: record a multiple of `every` steps, from a step
+ * count that is one.  TGNH_ERR_ARG: every < 0, a temperature that is negative or not finite.  TGNH_ERR_UNSUPPORTED: every > 0 on a
+ * handle that steps with TGNH_FLAG_DEFER_SCALE (its velocities lag between steps) or has a mailbox exchange attached; and
+ * tgnh_exchange_attach / _attach_pointers return it while rescaling is on. */
+tgnh_status tgnh_scale_velocities(tgnh_handle h, const double* factors, int count, void* stream);
+tgnh_status tgnh_rescale_to_temperature(tgnh_handle h, double temperature, double drude_temperature, void* stream);
+tgnh_status tgnh_get_rescale_factors(tgnh_handle h, void* stream, double* factors);      /* NT doubles; synchronises */
+tgnh_status tgnh_set_velocity_rescaling(tgnh_handle h, int every, double temperature, double drude_temperature);
 
 /* Retargets both baths of a live handle (heating, annealing, equilibration at one temperature and production at another):
  * kB T and kB T_D -- the chain's launch arguments and the hard wall's thermal speed --, every N kT and every thermostat mass,

@@ -98,6 +98,10 @@ SIGNATURES = {
     "tgnh_shift_velocities": (C.c_int, [C.c_void_p, c_f64p, C.c_void_p]),
     "tgnh_remove_cm_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tgnh_set_cm_motion_removal": (C.c_int, [C.c_void_p, C.c_int]),
+    "tgnh_scale_velocities": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_void_p]),
+    "tgnh_rescale_to_temperature": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
+    "tgnh_get_rescale_factors": (C.c_int, [C.c_void_p, C.c_void_p, c_f64p]),
+    "tgnh_set_velocity_rescaling": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double]),
     "tgnh_set_temperatures": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "tgnh_note_replayed_steps": (C.c_int, [C.c_void_p, C.c_int]),
     "tgnh_set_time": (C.c_int, [C.c_void_p, C.c_double, C.c_int64]),

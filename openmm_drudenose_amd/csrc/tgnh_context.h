@@ -96,6 +96,13 @@ struct tgnh_context {
         tgnh::CmRow h_row{};              // where the result lands on the host
         int every = 0;                    // tgnh_set_cm_motion_removal: remove before every step whose number is a multiple of this (0: never)
     } cmm;
+    struct Rescale {                  // tgnh_scale_velocities / tgnh_rescale_to_temperature: allocated at the first call that launches
+        tgnh::DeviceBuf<double> d_buf;    // (or at tgnh_set_velocity_rescaling: never inside somebody's stream capture) [2 NT]: the factors
+                                          // the rescale launch reads -- never the thermostat block's scale entries --, then the targets N kT
+        bool applied = false;             // a call has written the factors (tgnh_get_rescale_factors answers)
+        int every = 0;                    // tgnh_set_velocity_rescaling: rescale before every step whose number is a multiple of this (0: never)
+        double temperature = 0, drude_temperature = 0;   // ... to these
+    } resc;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block
         std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction

@@ -47,10 +47,13 @@ extern "C" tgnh_status tgnh_exchange_create(tgnh_handle h, int world, int rank, 
 }
 
 // the mailboxes carry the kinetic-energy sums only: a handle that removes its centre-of-mass motion inside the step loop
-// (tgnh_set_cm_motion_removal) has no exchange for the momentum sums once they replace the hook
+// (tgnh_set_cm_motion_removal) has no exchange for the momentum sums once they replace the hook; nor has one that rescales its
+// velocities there (tgnh_set_velocity_rescaling) for the sums of a kinetic-energy pass outside the step's own
 static tgnh_status cm_removal_off(tgnh_handle h, const char* what) {
     if (h->cmm.every > 0)
         return fail(TGNH_ERR_UNSUPPORTED, std::string(what) + ": centre-of-mass removal is on (tgnh_set_cm_motion_removal(h, 0) first)");
+    if (h->resc.every > 0)
+        return fail(TGNH_ERR_UNSUPPORTED, std::string(what) + ": velocity rescaling is on (tgnh_set_velocity_rescaling(h, 0, ...) first)");
     return TGNH_OK;
 }
 

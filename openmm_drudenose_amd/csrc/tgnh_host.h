@@ -1,7 +1,7 @@
 // tgnh_host.h -- what the host units behind the C ABI (include/drude_tgnh.h) share: tgnh_topology.cpp, tgnh_lifecycle.cpp,
 // tgnh_exchange.cpp, tgnh_step.cpp, tgnh_queries.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
 // live in tgnh_kernels.hip (tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h), tgnh_gather.hip, tgnh_velinit.hip,
-// tgnh_drude_stats.hip, tgnh_cm_motion.hip and tgnh_harness.hip.
+// tgnh_drude_stats.hip, tgnh_cm_motion.hip, tgnh_rescale.hip and tgnh_harness.hip.
 //
 // Reference semantics followed (scychon/openmm_drudeNose):
 //   Ref = platforms/reference/src/ReferenceDrudeTGNHKernels.cpp
@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "tgnh_context.h"
+#include "tgnh_rescale.h"
 
 using namespace tgnh;
 
@@ -37,6 +38,7 @@ tgnh_status build_topology(tgnh_context* c, const tgnh_desc* d);
 void local_dof_terms(tgnh_context* c);
 tgnh_status check_temperatures(double temperature, double drude_temperature);
 void set_bath_temperatures(tgnh_context* c, double temperature, double drude_temperature);
+std::vector<double> thermostat_nkt(const tgnh_context* c, double realkbT, double drudekbT);   // N kT per thermostat at these kT (stores nothing)
 void thermostat_targets(tgnh_context* c, std::vector<double>& st);
 tgnh_status finalize_thermostat(tgnh_context* c);
 std::vector<int> partner_table(const tgnh_context* c);
@@ -56,6 +58,7 @@ tgnh_status materialize_chain(tgnh_handle h, hipStream_t s);
 tgnh_status settle_kick(tgnh_handle h, hipStream_t s);
 tgnh_status settle_end(tgnh_handle h, hipStream_t s);
 tgnh_status flush_impl(tgnh_handle h, hipStream_t s);
+tgnh_status ke_query_launches(tgnh_handle h, hipStream_t s);    // tgnh_queries.cpp: what tgnh_compute_kinetic_energies enqueues behind its entry checks
 tgnh_status cm_scratch(tgnh_handle h);                                          // the rows of the momentum pass, allocated once
 tgnh_status cm_momentum_launches(tgnh_handle h, hipStream_t s, CmRow** result);   // pass + row sum of the bound velm -> *result (device)
 

@@ -155,8 +155,13 @@ extern "C" tgnh_status tgnh_get_topology(tgnh_handle h, int which, int32_t* out)
 
 extern "C" tgnh_status tgnh_compute_kinetic_energies(tgnh_handle h, void* stream) {
     tgnh_status rc = entry(h, true); if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    rc = settle_kick(h, s); if (rc) return rc;
+    return ke_query_launches(h, (hipStream_t)stream);
+}
+
+// ... and what it enqueues (tgnh_rescale_to_temperature begins with the same launches): the kinetic-energy pass of the velocities as
+// they are, its row sum, the all-reduce where one is set; the sums lie in ke_red and in the block's KE entries afterwards
+tgnh_status ke_query_launches(tgnh_handle h, hipStream_t s) {
+    tgnh_status rc = settle_kick(h, s); if (rc) return rc;
     rc = materialize_chain(h, s); if (rc) return rc;      // ke_red is about to be overwritten
     const int dir = h->run.sweep_reverse;                      // a query leaves the sweep direction as it found it: the step's next
     rc = run_tile(h, OP_KE, KID_KE, s);                    // KE launch then sums in the same order, to the same bits

@@ -1,4 +1,4 @@
-// tgnh_step.cpp -- step orchestration (A11): device-reported failures, the launch decisions by name, launch sizing, run_tile / run_gather / run_chain / run_resident, centre-of-mass removal, tgnh_step_*, flush, clock
+// tgnh_step.cpp -- step orchestration (A11): device-reported failures, the launch decisions by name, launch sizing, run_tile / run_gather / run_chain / run_resident, centre-of-mass removal, velocity rescaling, tgnh_step_*, flush, clock
 #include "tgnh_host.h"
 
 // ---------------------------------------------------------------------------
@@ -586,10 +586,125 @@ extern "C" tgnh_status tgnh_set_cm_motion_removal(tgnh_handle h, int every) {
     return TGNH_OK;
 }
 
+// ---------------------------------------------------------------------------
+// velocity rescaling (include/drude_tgnh.h has the contract; tgnh_rescale.hip the two small kernels; the rescale is run_tile's)
+// ---------------------------------------------------------------------------
+static tgnh_status rescale_scratch(tgnh_handle h) {
+    if (!h->resc.d_buf) HIP_OK(h->resc.d_buf.alloc(2 * (size_t)h->thermo.L.NT, true));
+    return TGNH_OK;
+}
+static double* rescale_factors(tgnh_handle h) { return h->resc.d_buf; }
+static double* rescale_targets(tgnh_handle h) { return h->resc.d_buf + h->thermo.L.NT; }
+
+// A6 with the factors in the scratch: the step's own rescale launch, told where its factors lie (so no chain is adopted and the
+// thermostat block is neither read nor written).  Molecules longer than a tile: the launch reads their centre-of-mass velocities
+// from a table -- of the velocities as they are (table_fresh: the kinetic-energy pass just before has left it) -- and the table is
+// made again of what the launch stored, as flush_impl does.  The gather path computes its own table inside run_gather unless a
+// kinetic-energy pass has left it since entry().  The sweep direction is left as it was found.
+static tgnh_status rescale_apply(tgnh_handle h, hipStream_t s, bool table_fresh) {
+    const int dir = h->run.sweep_reverse;
+    tgnh_status rc = big_com_on(h) && !table_fresh ? run_big_com(h, false, s) : TGNH_OK;
+    if (!rc) rc = run_tile(h, OP_SCALE, KID_SCALE, s, rescale_factors(h));
+    if (!rc && big_com_on(h)) rc = run_big_com(h, false, s);
+    h->run.sweep_reverse = dir;
+    if (!rc) h->resc.applied = true;
+    return rc;
+}
+
+static tgnh_status rescale_mailbox_refusal() {
+    return fail(TGNH_ERR_UNSUPPORTED, "velocity rescaling to a temperature with a mailbox exchange attached: the mailboxes carry the step's own kinetic-energy sums only "
+                                      "(tgnh_compute_kinetic_energies on every rank, form the factors, tgnh_scale_velocities with the same factors everywhere)");
+}
+
+// the kinetic-energy pass, its row sum [+ all-reduce], the factors, A6.  Nothing here waits for the device.  The caller has seen
+// to tgnh_state_changed (so nothing is owed to velm, and no chain waits for a rescale launch: materialize_chain commits a staged
+// block at the most) and to the scratch.
+static tgnh_status rescale_to_temperature_launches(tgnh_handle h, double temperature, double drude_temperature, hipStream_t s) {
+    if (h->xchg.on) return rescale_mailbox_refusal();
+    const ChainLayout& L = h->thermo.L;
+    std::vector<double> target = thermostat_nkt(h, h->d.kB * temperature, h->d.kB * drude_temperature);
+    for (int k = 0; k < L.NT; k++) if (h->thermo.dof[k] == 0.0) target[k] = RESCALE_INERT;     // (N kT = 0 at any temperature)
+    HIP_OK(launch_rescale_put(rescale_targets(h), target.data(), L.NT, s));
+    const int dir = h->run.sweep_reverse;
+    tgnh_status rc = ke_query_launches(h, s);
+    h->run.sweep_reverse = dir;
+    if (rc) return rc;
+    {
+        Timed t(h, s, KID_OTHER);
+        HIP_OK(launch_rescale_factors(h->thermo.d_state + L.off_ke_red, rescale_targets(h), L.NT, rescale_factors(h), h->status.d_word, s));
+    }
+    return rescale_apply(h, s, true);
+}
+
+// tgnh_set_velocity_rescaling: placed as cm_removal_due is, and after it
+static tgnh_status rescale_due(tgnh_handle h, hipStream_t s) {
+    if (h->resc.every <= 0 || h->run.step_count % h->resc.every != 0) return TGNH_OK;
+    h->owed.ke_carry = false;
+    return rescale_to_temperature_launches(h, h->resc.temperature, h->resc.drude_temperature, s);
+}
+
+extern "C" tgnh_status tgnh_scale_velocities(tgnh_handle h, const double* factors, int count, void* stream) {
+    CHECK_H(h);
+    const int NT = h->thermo.L.NT;
+    if (!factors) return fail(TGNH_ERR_ARG, "tgnh_scale_velocities: null factors");
+    if (count != NT) return fail(TGNH_ERR_ARG, "tgnh_scale_velocities: count is not the number of thermostats (tgnh_get_num_thermostats)");
+    std::vector<double> f(factors, factors + NT);
+    if (h->d.mode == TGNH_MODE_DUALNH) f[1] = 1.0;              // (dualNH's unused entry: whatever it holds)
+    for (double v : f) if (!(v >= 0) || !std::isfinite(v)) return fail(TGNH_ERR_ARG, "tgnh_scale_velocities: a factor is negative or not finite");
+    tgnh_status rc = entry(h, true); if (rc) return rc;           // (buffers bound, not a host-only handle, no failure seen before)
+    rc = tgnh_state_changed(h); if (rc) return rc;              // (first: refused between the steps of a deferred sequence, and then nothing is written)
+    hipStream_t s = (hipStream_t)stream;
+    rc = rescale_scratch(h); if (rc) return rc;
+    HIP_OK(launch_rescale_put(rescale_factors(h), f.data(), NT, s));    // (by value, with the launch: the caller's array is free again)
+    return rescale_apply(h, s, false);
+}
+
+extern "C" tgnh_status tgnh_rescale_to_temperature(tgnh_handle h, double temperature, double drude_temperature, void* stream) {
+    CHECK_H(h);
+    tgnh_status rc = check_temperatures(temperature, drude_temperature); if (rc) return rc;
+    rc = entry(h, true); if (rc) return rc;
+    if (h->xchg.on) return rescale_mailbox_refusal();           // (before anything of the handle changes)
+    rc = tgnh_state_changed(h); if (rc) return rc;
+    rc = rescale_scratch(h); if (rc) return rc;
+    return rescale_to_temperature_launches(h, temperature, drude_temperature, (hipStream_t)stream);
+}
+
+extern "C" tgnh_status tgnh_get_rescale_factors(tgnh_handle h, void* stream, double* factors) {
+    CHECK_H(h);
+    if (!factors) return fail(TGNH_ERR_ARG, "null out");
+    tgnh_status rc = entry(h, true); if (rc) return rc;
+    if (!h->resc.applied) return fail(TGNH_ERR_STATE, "tgnh_get_rescale_factors: neither tgnh_scale_velocities nor tgnh_rescale_to_temperature has run on this handle");
+    hipStream_t s = (hipStream_t)stream;
+    HIP_OK(hipMemcpyAsync(factors, rescale_factors(h), sizeof(double) * h->thermo.L.NT, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(h->status.h_seen, h->status.d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    note_status(h, *h->status.h_seen);
+    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);
+    return TGNH_OK;
+}
+
+extern "C" tgnh_status tgnh_set_velocity_rescaling(tgnh_handle h, int every, double temperature, double drude_temperature) {
+    CHECK_H(h);
+    if (every < 0) return fail(TGNH_ERR_ARG, "tgnh_set_velocity_rescaling: negative interval");
+    tgnh_status rc = check_temperatures(temperature, drude_temperature); if (rc) return rc;
+    if (every > 0) {
+        if (h->d.flags & TGNH_FLAG_DEFER_SCALE)
+            return fail(TGNH_ERR_UNSUPPORTED, "tgnh_set_velocity_rescaling: velocities lag between the steps of a TGNH_FLAG_DEFER_SCALE handle");
+        if (h->xchg.on) return fail(TGNH_ERR_UNSUPPORTED, "tgnh_set_velocity_rescaling: a mailbox exchange is attached (it carries the step's own kinetic-energy sums only)");
+        if (!h->host_only) {                                    // the scratch now: the first rescale may be enqueued inside a stream capture
+            HIP_OK(hipSetDevice(h->device));
+            rc = rescale_scratch(h); if (rc) return rc;
+        }
+    }
+    h->resc.every = every; h->resc.temperature = temperature; h->resc.drude_temperature = drude_temperature;
+    return TGNH_OK;
+}
+
 extern "C" tgnh_status tgnh_step_begin(tgnh_handle h, void* stream) {
     tgnh_status rc = entry(h, true); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     rc = cm_removal_due(h, s); if (rc) return rc;
+    rc = rescale_due(h, s); if (rc) return rc;
     start_of_step(h);
     if (h->owed.end_pending) {
         if (resident_now(h)) return run_resident(h, s, 0);           // the last step's end half and this begin half: one launch
@@ -672,6 +787,7 @@ extern "C" tgnh_status tgnh_step_begin_kick(tgnh_handle h, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     tgnh_status rc = split_entry(h, s, false); if (rc) return rc;
     rc = cm_removal_due(h, s); if (rc) return rc;
+    rc = rescale_due(h, s); if (rc) return rc;
     start_of_step(h);
     if (!(h->d.flags & TGNH_FLAG_DEFER_SCALE) && resident_now(h) && !h->owed.ke_carry) return run_resident(h, s, 3);
     rc = first_half(h, s); if (rc) return rc;

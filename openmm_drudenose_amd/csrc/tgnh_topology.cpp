@@ -427,17 +427,30 @@ void set_bath_temperatures(tgnh_context* c, double temperature, double drude_tem
     c->thermo.drudekbT = c->d.kB * drude_temperature;
 }
 
+// Every thermostat's N kT from thermo.dof and a pair of kT: what computes, apart from what stores.  thermostat_targets keeps the
+// result for the handle's own baths; tgnh_rescale_to_temperature asks for other temperatures' and leaves the baths alone.
+std::vector<double> thermostat_nkt(const tgnh_context* c, double realkbT, double drudekbT) {
+    const ChainLayout& L = c->thermo.L;
+    std::vector<double> nkbt(L.NT, 0.0);
+    if (c->d.mode == TGNH_MODE_DUALNH) {
+        nkbt[0] = c->thermo.dof[0] * realkbT; nkbt[2] = c->thermo.dof[2] * drudekbT;      // Ref :168-169
+    } else {
+        for (int i = 0; i < L.G + 1; i++) nkbt[i] = c->thermo.dof[i] * realkbT;           // Cu :218-225
+        nkbt[L.G + 1] = c->thermo.dof[L.G + 1] * drudekbT;                                // Cu :227-235
+    }
+    return nkbt;
+}
+
 // What the bath temperatures decide of the thermostat block -- every N kT (thermo.nkbt too) and every thermostat mass, and the
 // etaDotDot a chain STARTS with -- written into st (the block's layout, zero elsewhere) from thermo.dof and kT, kT_D.
 void thermostat_targets(tgnh_context* c, std::vector<double>& st) {
     const tgnh_desc& d = c->d;
     const ChainLayout& L = c->thermo.L;
     const int NT = L.NT, C = L.C;
-    c->thermo.nkbt.assign(NT, 0.0);
+    c->thermo.nkbt = thermostat_nkt(c, c->thermo.realkbT, c->thermo.drudekbT);
     const double tau2 = std::pow(d.coupling_time, 2), tauD2 = std::pow(d.drude_coupling_time, 2);
     if (d.mode == TGNH_MODE_DUALNH) {
-        const double realNkbT = c->thermo.dof[0] * c->thermo.realkbT, drudeNkbT = c->thermo.dof[2] * c->thermo.drudekbT;   // Ref :168-169
-        c->thermo.nkbt[0] = realNkbT; c->thermo.nkbt[2] = drudeNkbT;
+        const double realNkbT = c->thermo.nkbt[0], drudeNkbT = c->thermo.nkbt[2];
         double* etaMass = st.data() + L.off_etaMass;
         double* etaDot = st.data() + L.off_etaDot;
         double* etaDotDot = st.data() + L.off_etaDotDot;
@@ -461,14 +474,12 @@ void thermostat_targets(tgnh_context* c, std::vector<double>& st) {
         const int G = L.G;
         const double realUnit = c->thermo.realkbT * tau2, drudeUnit = c->thermo.drudekbT * tauD2;   // Cu :216-217
         for (int i = 0; i < G + 1; i++) {                                     // Cu :218-225
-            c->thermo.nkbt[i] = c->thermo.dof[i] * c->thermo.realkbT;
             double* em = st.data() + L.off_etaMass + i * C;
             double* edd = st.data() + L.off_etaDotDot + i * C;
             em[0] = c->thermo.dof[i] * realUnit;
             for (int ich = 1; ich < C; ich++) { em[ich] = realUnit; edd[ich] = (em[ich - 1] * 0.0 - c->thermo.realkbT) / em[ich]; }
         }
         const int itg = G + 1;                                                // Cu :227-235
-        c->thermo.nkbt[itg] = c->thermo.dof[itg] * c->thermo.drudekbT;
         double* em = st.data() + L.off_etaMass + itg * C;
         double* edd = st.data() + L.off_etaDotDot + itg * C;
         em[0] = c->thermo.dof[itg] * drudeUnit;

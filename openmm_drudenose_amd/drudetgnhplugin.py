@@ -361,6 +361,7 @@ class HipContext(_HandleQueries):
         self.first_particle = 0                              # a shard: the index of its first slot in the whole system (setVelocitiesToTemperature)
         self._hook = None
         self.cm_motion_removal = 0
+        self.velocity_rescaling = 0
         if cm_motion_removal is not None:
             with torch.cuda.device(self.dev):
                 self.set_cm_motion_removal(cm_motion_removal)
@@ -663,13 +664,49 @@ class HipContext(_HandleQueries):
         _check(self.lib.tgnh_set_cm_motion_removal(self.h, int(every)))
         self.cm_motion_removal = int(every)
 
-    def setVelocitiesToTemperature(self, temperature, randomSeed=None, drudeTemperature=None, removeCMMotion=False):
+    # ---- velocity rescaling (include/drude_tgnh.h: tgnh_scale_velocities, tgnh_rescale_to_temperature, ...) ----
+    def _bath_pair(self, temperature, drudeTemperature):
+        return (float(self.integrator.getTemperature() if temperature is None else temperature),
+                float(self.integrator.getDrudeTemperature() if drudeTemperature is None else drudeTemperature))
+
+    def scale_velocities(self, factors):
+        """tgnh_scale_velocities: the integrator's own rescale with one factor per thermostat, in last_scale_factors()' layout
+        (TGNH [groups.., COM, Drude], dualNH [real, unused, Drude]): velocities relative to their molecule's centre of mass by
+        their group's factor, the centres of mass by theirs, the relative Drude motion by the Drude factor.  No host
+        synchronisation; `factors` is read before the call returns."""
+        f = np.ascontiguousarray(factors, np.float64)
+        if f.ndim != 1:
+            raise TgnhError(_lib.ERR_ARG, "scale_velocities: factors must be a vector, one per thermostat")
+        _check(self.lib.tgnh_scale_velocities(self.h, f.ctypes.data_as(_lib.c_f64p), len(f), self._stream()))
+        self.ke_sum_valid = False
+
+    def rescale_to_temperature(self, temperature=None, drudeTemperature=None):
+        """tgnh_rescale_to_temperature: every thermostat's kinetic energy onto N kT at these temperatures (default: the
+        integrator's) -- kinetic-energy pass, all-reduce where one is set (the call is then collective), factors, rescale, all on
+        the device.  The baths stay as they are.  last_kinetic_energies() has the sums before scaling, rescale_factors() the
+        factors."""
+        _check(self.lib.tgnh_rescale_to_temperature(self.h, *self._bath_pair(temperature, drudeTemperature), self._stream()))
+        self.ke_sum_valid = False
+
+    def rescale_factors(self):
+        """tgnh_get_rescale_factors: what the last scale_velocities / rescale_to_temperature applied.  Synchronises the stream."""
+        return self._vec(self.lib.tgnh_get_rescale_factors, self.num_thermostats())
+
+    def set_velocity_rescaling(self, every, temperature=None, drudeTemperature=None):
+        """tgnh_set_velocity_rescaling: rescale_to_temperature before every step whose number is a multiple of `every` (0: off),
+        after a centre-of-mass removal due at the same step, inside step() and whatever else runs the step entry points."""
+        _check(self.lib.tgnh_set_velocity_rescaling(self.h, int(every), *self._bath_pair(temperature, drudeTemperature)))
+        self.velocity_rescaling = int(every)
+        self.ke_sum_valid = False
+
+    def setVelocitiesToTemperature(self, temperature, randomSeed=None, drudeTemperature=None, removeCMMotion=False, exact=False):
         """OpenMM's Context.setVelocitiesToTemperature, Drude-aware and drawn on the device (tgnh_set_velocities_to_temperature):
         pair centres of mass and ordinary particles at `temperature`, the relative Drude motion at `drudeTemperature` (default:
         the integrator's).  randomSeed=None takes one from os.urandom; the same seed gives the same velocities on any handle,
         path or sharding (self.first_particle places a shard in the whole system).  With constraint clusters set, the harness'
         velocity-constraint stage runs afterwards, as OpenMM projects after its draw.  removeCMMotion=True takes the net momentum
-        the draw leaves (of order sqrt(N) thermal momenta) off again, last of all (removeCMMotion())."""
+        the draw leaves (of order sqrt(N) thermal momenta) off again, after that stage (removeCMMotion()).  exact=True then puts
+        every thermostat's kinetic energy onto its N kT at these temperatures, last of all (rescale_to_temperature())."""
         if drudeTemperature is None:
             drudeTemperature = self.integrator.getDrudeTemperature()
         if randomSeed is None:
@@ -684,6 +721,8 @@ class HipContext(_HandleQueries):
             _check(self.lib.tgnh_harness_shake_velocities(self.h, self.integrator.getConstraintTolerance(), self._stream()))
         if removeCMMotion:
             self.removeCMMotion()
+        if exact:
+            self.rescale_to_temperature(temperature, drudeTemperature)
 
     def setCharges(self, q):
         """posq.w of every slot (OpenMM keeps the charge there; setPositions leaves it alone).  No step kernel reads it."""
@@ -785,10 +824,11 @@ class HipContext(_HandleQueries):
             raise TgnhError(_lib.ERR_STATE, "capture_steps supports the harness force call-out only")
         # A recording bakes in the centre-of-mass removals of the steps it recorded (set_cm_motion_removal): it replays the loop's
         # own launches only if every replay starts at a multiple of the interval, and so ends at one
-        every = self.cm_motion_removal
-        if every > 0 and (self.time()[1] % every or int(steps) % every):
-            raise TgnhError(_lib.ERR_STATE, f"capture_steps: with centre-of-mass removal every {every} steps, the step count at the "
-                            f"capture ({self.time()[1]}) and the steps captured ({int(steps)}) must both be multiples of it")
+        # (and the velocity rescalings, set_velocity_rescaling, alike)
+        for what, every in (("centre-of-mass removal", self.cm_motion_removal), ("velocity rescaling", self.velocity_rescaling)):
+            if every > 0 and (self.time()[1] % every or int(steps) % every):
+                raise TgnhError(_lib.ERR_STATE, f"capture_steps: with {what} every {every} steps, the step count at the "
+                                f"capture ({self.time()[1]}) and the steps captured ({int(steps)}) must both be multiples of it")
         # A graph replays launches, not the decisions that chose them: it may only be replayed from the state it was recorded
         # in.  The first steps of a handle differ from the later ones (nothing pending yet, a staged thermostat block to
         # commit), and so does a step after a query or a split step that settled part of what a step leaves owed.  So the

@@ -1,5 +1,5 @@
 // Stand-alone driver of the host-only sanitizer build (run_host_driver_asan.sh): the host side of tgnh_set_temperatures and
-// tgnh_set_velocities_to_temperature, and the argument checks of the centre-of-mass calls, through a host-only handle (device -1),
+// tgnh_set_velocities_to_temperature, and the argument checks of the centre-of-mass and velocity-rescaling calls, through a host-only handle (device -1),
 // no Python in the process.  What needs a device --
 // the upload of the retargeted block, the partner table's first use and the launch -- is not reached here.
 #include <cmath>
@@ -62,6 +62,24 @@ static int run(int mode, int chains, int drude_chains) {
     EXPECT(tgnh_set_cm_motion_removal(a, -1) == TGNH_ERR_ARG && tgnh_set_cm_motion_removal(nullptr, 1) == TGNH_ERR_ARG);
     EXPECT(tgnh_set_cm_motion_removal(a, 5) == TGNH_OK && tgnh_step_begin(a, nullptr) == TGNH_ERR_STATE);
     EXPECT(tgnh_set_cm_motion_removal(a, 0) == TGNH_OK);
+    // velocity rescaling: the argument checks, the targets formed on the host for other temperatures, the host-only refusals
+    std::vector<double> fac(nt, 1.25), got(nt, 7.0), nkt0(nt), nkt1(nt);
+    EXPECT(tgnh_get_dof(a, nullptr, nkt0.data()) == TGNH_OK);
+    EXPECT(tgnh_scale_velocities(a, nullptr, nt, nullptr) == TGNH_ERR_ARG && tgnh_scale_velocities(a, fac.data(), nt - 1, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_scale_velocities(nullptr, fac.data(), nt, nullptr) == TGNH_ERR_ARG);
+    fac[0] = -0.5;
+    EXPECT(tgnh_scale_velocities(a, fac.data(), nt, nullptr) == TGNH_ERR_ARG);
+    fac[0] = NAN;
+    EXPECT(tgnh_scale_velocities(a, fac.data(), nt, nullptr) == TGNH_ERR_ARG);
+    fac[0] = 0.0;
+    EXPECT(tgnh_scale_velocities(a, fac.data(), nt, nullptr) == TGNH_ERR_STATE);                               // host-only: nothing launches
+    EXPECT(tgnh_rescale_to_temperature(a, NAN, 1, nullptr) == TGNH_ERR_ARG && tgnh_rescale_to_temperature(a, 300, -1, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_rescale_to_temperature(a, 350, 2, nullptr) == TGNH_ERR_STATE && tgnh_rescale_to_temperature(a, 0, 0, nullptr) == TGNH_ERR_STATE);
+    EXPECT(tgnh_get_rescale_factors(a, nullptr, nullptr) == TGNH_ERR_ARG && tgnh_get_rescale_factors(a, nullptr, got.data()) == TGNH_ERR_STATE && got[0] == 7.0);
+    EXPECT(tgnh_set_velocity_rescaling(a, -1, 300, 1) == TGNH_ERR_ARG && tgnh_set_velocity_rescaling(a, 1, NAN, 1) == TGNH_ERR_ARG);
+    EXPECT(tgnh_set_velocity_rescaling(a, 4, 350, 2) == TGNH_OK && tgnh_step_begin(a, nullptr) == TGNH_ERR_STATE);
+    EXPECT(tgnh_set_velocity_rescaling(a, 0, 350, 2) == TGNH_OK);
+    EXPECT(tgnh_get_dof(a, nullptr, nkt1.data()) == TGNH_OK && nkt0 == nkt1);                                  // the baths are whose they were
     EXPECT(tgnh_destroy(a) == TGNH_OK && tgnh_destroy(b) == TGNH_OK);
     return 0;
 }

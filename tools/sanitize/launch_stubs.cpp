@@ -22,6 +22,8 @@ hipError_t launch_velinit(int, void*, const int*, int, double, double, unsigned 
 hipError_t launch_drude_stats(int, const void*, const void*, const int*, int, double, double, DrudeStatsRow*, int, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_cm_momentum(int, const void*, int, CmRow*, int, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_cm_shift(int, void*, int, const double*, const double*, int, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_rescale_put(double*, const double*, int, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_rescale_factors(const double*, const double*, int, double*, uint32_t*, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_gather_com(int, const GatherArgs&, hipStream_t) { return hipErrorNoDevice; }
 int gather_ke_grid(const GatherArgs&) { return 1; }
 hipError_t launch_gather_ke(int, const GatherArgs&, int, hipStream_t) { return hipErrorNoDevice; }
