@@ -373,6 +373,70 @@ tgnh_status tgnh_shift_velocities(tgnh_handle h, const double dv[3], void* strea
 tgnh_status tgnh_remove_cm_motion(tgnh_handle h, void* stream);
 tgnh_status tgnh_set_cm_motion_removal(tgnh_handle h, int every);
 
+/* Scaling the molecules' centres: the coordinate move of a Monte Carlo barostat (OpenMM's MonteCarloBarostat rescales the box and
+ * the molecule centres; the reference's example runs one, example/nacl_tg.py:13-14, 56-57) for a host without OpenMM and for a
+ * particle-sharded run, without the positions leaving the device.  A barostat must move each molecule RIGIDLY: scaled per particle,
+ * every Drude-parent distance and every constrained bond would be scaled too, and the hard wall would be hit by the barostat
+ * instead of by the physics.  So these calls know molecules.
+ *
+ * THE MOLECULE TABLE.  tgnh_set_molecules: molecule[i] is any int32 label; slots with equal labels form one molecule, whether or
+ * not they are consecutive.  NULL selects the default: the descriptor's resid where the handle was given one, in either mode --
+ * here a residue stored in several runs is ONE molecule, unlike the reference's centre-of-mass walk (see
+ * tgnh_rescale_to_temperature's limit).  Without resid (DUALNH created with resid = NULL) there is no default: TGNH_ERR_STATE,
+ * "call tgnh_set_molecules first", from every call that needs a table, until labels are set.  A handle that never calls
+ * tgnh_set_molecules has the default table, resolved at the first call that needs one.  tgnh_get_molecules returns the labels
+ * renumbered in order of first appearance, 0..M-1; tgnh_get_num_molecules returns M (a barostat's acceptance rule needs it).  All
+ * three work on a host-only handle.  TGNH_ERR_ARG: a Drude pair whose two members carry different labels -- the move would
+ * stretch the spring; the message names the pair.  The default table gets the same check, so a resid that splits a pair fails
+ * with that message.  A refused table leaves the one in force as it was.  Constraints are NOT checked: the handle does not keep
+ * them (tgnh_desc.constraint_i / _j are read by tgnh_create only); the caller sees to it that no constraint crosses a molecule.
+ * SHARDED RUNS: shards are whole molecules already; nothing is exchanged, and every rank passes the same scale.
+ *
+ * tgnh_scale_positions.  Everything in fp64, every operation rounded on its own (no fused multiply-add).  Per component, with
+ * x(i) the coordinate as tgnh_get_drude_statistics defines it (posq, plus posq_correction in mixed precision):
+ *   S  = the sum of x(i) over the molecule's n members, massless slots included (virtual sites move with their molecule)
+ *        n <= 64: in ascending slot order, left to right, starting from the first member's value
+ *        n  > 64: in an order that is a function of the member list alone (not of the grid, the device, the flags or the step
+ *                 path): lane l of one wavefront adds members l, l + 64, ... in ascending order onto 0.0, then the 64 lanes are added
+ *   c  = S / (double)n                     one IEEE division
+ *   d  = c * (scale - 1.0)                 (scale - 1.0) formed once, on the host
+ *   x' = x(i) + d
+ *   stored:  double  posq = x'
+ *            single  posq = (float)x'
+ *            mixed   posq = hi = (float)x',  posq_correction = (float)(x' - (double)hi)
+ * posq.w (the charge) and posq_correction.w are stored back bit for bit.  NO periodic box is known and nothing is wrapped:
+ * molecules scale about the origin, and the caller scales its own box vectors.  OpenMM scales about the box's centre and wraps
+ * molecules back into the box; the two differ only by whole box vectors.  The same positions give the same bits from any handle
+ * over the same slots and the same molecule table: tiled or TGNH_FLAG_GATHER, TGNH or DUALNH, whatever the flags, asked once or
+ * twice from the same positions.  scale = (1, 1, 1) leaves every value bit for bit in double and single precision (d = +-0); in
+ * mixed precision the hi / lo split is re-normalised: hi + lo is unchanged, the two parts need not be.
+ * It enqueues on `stream`; nothing waits for the device; capturable into a hipGraph.  The device copies of the molecule table (and
+ * the table path's 24 bytes per molecule of scratch) are made at tgnh_set_molecules on a device handle or at the first launching
+ * call -- never inside a capture: a first call on a capturing stream returns TGNH_ERR_STATE and says so.  One launch where every
+ * molecule is a run of consecutive slots no longer than a wavefront (each slot read once and written once), two launches by
+ * global index otherwise (members that are not consecutive, molecules longer than 64 slots).
+ * save != 0: the same launch also stores what it read into a snapshot owned by the handle -- a trial move is ONE launch.  The
+ * snapshot is one copy of posq, and of posq_correction in mixed precision, allocated at the first such call.
+ * Positions are not velocities: the call does NOT do what tgnh_state_changed does.  The kinetic energies carried under
+ * TGNH_FLAG_TRUST_STATE_CHANGED, the sweep direction, tgnh_get_pending_state and the thermostat stay as they are.
+ * REFUSED while a half kick is still owed to velm -- bit 0 or bit 2 of tgnh_get_pending_state -- with TGNH_ERR_STATE and the
+ * positions untouched: that kick belongs to the forces of the old positions, and the folded launch of the next tgnh_step_begin
+ * would take it from the forces of the new ones.  THE CALLER'S TWO DUTIES: call tgnh_flush first; and after every successful
+ * call recompute the forces into the bound force buffer before the next step (the buffer holds the forces of the old positions).
+ * The harness' tether sites (tgnh_harness_pack_sites) are not scaled.
+ * TGNH_ERR_ARG, checked first so that a host-only handle answers it: scale is NULL, or a component is not finite or <= 0.
+ * TGNH_ERR_STATE: buffers not bound, a host-only handle, no molecule table and no resid.  Follows tgnh_get_status_flags' rule for
+ * sticky failures, as the step entry points do.
+ *
+ * tgnh_restore_positions: copies the snapshot back over posq and posq_correction, on `stream`: bit for bit what the saving call
+ * read, w included.  The snapshot stays valid until the next saving call: it can be restored twice.  TGNH_ERR_STATE: no
+ * snapshot, or tgnh_bind_buffers has rebound posq or posq_correction since it was taken; buffers not bound, a host-only handle. */
+tgnh_status tgnh_set_molecules(tgnh_handle h, const int32_t* molecule /* [N] or NULL */);
+tgnh_status tgnh_get_num_molecules(tgnh_handle h, int* count);
+tgnh_status tgnh_get_molecules(tgnh_handle h, int32_t* molecule_out /* [N] */);
+tgnh_status tgnh_scale_positions(tgnh_handle h, const double scale[3], int save, void* stream);
+tgnh_status tgnh_restore_positions(tgnh_handle h, void* stream);
+
 /* Velocity rescaling: one factor per thermostat applied to the bound velocities the way the integrator's own rescale applies the
  * chain's (ReferenceDrudeTGNHKernels.cpp:516-541; CUDA kernel integrateDrudeTGNHChain), and the factors that put every thermostat's
  * kinetic energy onto its N kT at once -- an exact-temperature start after tgnh_set_velocities_to_temperature, velocity-rescaling

@@ -102,6 +102,11 @@ SIGNATURES = {
     "tgnh_rescale_to_temperature": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "tgnh_get_rescale_factors": (C.c_int, [C.c_void_p, C.c_void_p, c_f64p]),
     "tgnh_set_velocity_rescaling": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double]),
+    "tgnh_set_molecules": (C.c_int, [C.c_void_p, c_i32p]),
+    "tgnh_get_num_molecules": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "tgnh_get_molecules": (C.c_int, [C.c_void_p, c_i32p]),
+    "tgnh_scale_positions": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_void_p]),
+    "tgnh_restore_positions": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tgnh_set_temperatures": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "tgnh_note_replayed_steps": (C.c_int, [C.c_void_p, C.c_int]),
     "tgnh_set_time": (C.c_int, [C.c_void_p, C.c_double, C.c_int64]),

@@ -103,6 +103,28 @@ struct tgnh_context {
         int every = 0;                    // tgnh_set_velocity_rescaling: rescale before every step whose number is a multiple of this (0: never)
         double temperature = 0, drude_temperature = 0;   // ... to these
     } resc;
+    struct Molecules {                // what tgnh_scale_positions moves rigidly (tgnh_positions.cpp): the caller's labels, or the descriptor's resid
+        struct Table {                    // host side, built as a whole from one set of labels
+            std::vector<int> mol_of;          // [N] labels renumbered 0..count-1 in order of first appearance
+            int count = 0;
+            std::vector<int> mem_start, members;   // [count + 1], [N]: the slots by molecule, ascending within one
+            bool spans = false;               // every molecule a run of consecutive slots no longer than a wavefront: the span kernel serves it
+            std::vector<int> span_first;      // [spans + 1] spans of whole molecules, <= 64 slots each
+            std::vector<unsigned long long> span_heads;   // [spans] bit l: a molecule starts at lane l of the span
+        } t;
+        bool set = false;                 // t is in force (tgnh_set_molecules, or the default resolved at the first call that needed one)
+        bool on_device = false;           // the copies below are t's: made at tgnh_set_molecules on a device handle or at the first launching call
+        tgnh::DeviceBuf<int> d_span_first, d_mol_of, d_mem_start, d_members;      // spans: the first; otherwise the other three
+        tgnh::DeviceBuf<unsigned long long> d_span_heads;
+        tgnh::DeviceBuf<double> d_shift;  // [3 count] table path: d of every molecule, written by its first launch
+        void drop_device() { on_device = false; d_span_first.reset(); d_mol_of.reset(); d_mem_start.reset(); d_members.reset(); d_span_heads.reset(); d_shift.reset(); }
+    } mol;
+    struct PositionSnapshot {         // tgnh_scale_positions(save) -> tgnh_restore_positions: allocated at the first saving call
+        tgnh::DeviceBytes d_posq, d_corr; // one copy of posq, and of posq_correction in mixed precision
+        bool taken = false;               // a saving call has filled it
+        bool valid = false;               // ... and tgnh_bind_buffers has not rebound a position array since
+        const void *of_posq = nullptr, *of_corr = nullptr;     // the arrays it was read from
+    } snap;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block
         std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction

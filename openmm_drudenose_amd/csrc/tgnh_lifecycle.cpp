@@ -274,6 +274,7 @@ extern "C" tgnh_status tgnh_bind_buffers(tgnh_handle h, void* posq, void* posq_c
         }
     }
     h->owed.ke_carry = false;                                  // (other buffers: nothing computed from the old ones carries over)
+    if (posq != h->bound.posq || posq_correction != h->bound.posq_corr) h->snap.valid = false;      // (tgnh_restore_positions: its snapshot is of the old arrays)
     h->bound.posq = posq; h->bound.posq_corr = posq_correction; h->bound.velm = velm; h->bound.force = force; h->bound.pos_delta = pos_delta;
     return TGNH_OK;
 }

@@ -248,6 +248,32 @@ class _HandleQueries:
         return out
 
 
+    # ---- the molecule table (include/drude_tgnh.h: tgnh_set_molecules, ...): what scale_positions moves rigidly ----
+    def set_molecules(self, labels=None):
+        """tgnh_set_molecules: one int32 label per slot, equal labels one molecule (consecutive or not); None: the default, the
+        system's residues.  A Drude pair split between two molecules is refused."""
+        if labels is None:
+            _check(self.lib.tgnh_set_molecules(self.h, None))
+            return
+        lab = np.ascontiguousarray(labels, np.int32)
+        n = self.n
+        if lab.shape != (n,):
+            raise TgnhError(_lib.ERR_ARG, "set_molecules: one label per particle slot")
+        _check(self.lib.tgnh_set_molecules(self.h, lab.ctypes.data_as(_lib.c_i32p)))
+
+    def num_molecules(self):
+        """tgnh_get_num_molecules: M, the number of molecules of the table in force (a barostat's acceptance rule needs it)."""
+        n = C.c_int()
+        _check(self.lib.tgnh_get_num_molecules(self.h, C.byref(n)))
+        return n.value
+
+    def molecules(self):
+        """tgnh_get_molecules: the labels renumbered 0..M-1 in order of first appearance."""
+        out = np.zeros(self.n, np.int32)
+        _check(self.lib.tgnh_get_molecules(self.h, out.ctypes.data_as(_lib.c_i32p)))
+        return out
+
+
 class HostTopology(_HandleQueries):
     """Host-only handle (device -1): the library's topology / tile / dof logic without a GPU.  Used by the CPU
     tests; it cannot launch anything."""
@@ -257,6 +283,7 @@ class HostTopology(_HandleQueries):
         group, ngroups = integrator._resolve_groups(system.num_particles)
         self.group, self.num_groups = group, ngroups
         n = system.num_particles
+        self.n = n
         self.h = create_handle(self.lib, system, integrator, group, ngroups, _MODE[mode], _PREC[precision], -1, flags, kB,
                                (n + 31) // 32 * 32)
 
@@ -698,6 +725,22 @@ class HipContext(_HandleQueries):
         _check(self.lib.tgnh_set_velocity_rescaling(self.h, int(every), *self._bath_pair(temperature, drudeTemperature)))
         self.velocity_rescaling = int(every)
         self.ke_sum_valid = False
+
+    # ---- the barostat's trial move (include/drude_tgnh.h: tgnh_scale_positions, tgnh_restore_positions) ----
+    def scale_positions(self, scale, save=False):
+        """tgnh_scale_positions: every molecule of the table in force (set_molecules) moved rigidly by (scale - 1) x its centroid,
+        about the origin; a scalar means isotropic.  save=True keeps what was read in a snapshot of the handle's
+        (restore_positions), in the same launch.  No host synchronisation; velocities, thermostat and everything a step left
+        pending stay as they are.  Refused while a half kick is owed to the velocities (flush() first).  The caller scales its own
+        box and recomputes the forces before the next step."""
+        sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (3,)) if np.ndim(scale) == 0 else scale, np.float64)
+        if sc.shape != (3,):
+            raise TgnhError(_lib.ERR_ARG, "scale_positions: scale is a scalar or has three components")
+        _check(self.lib.tgnh_scale_positions(self.h, sc.ctypes.data_as(_lib.c_f64p), int(bool(save)), self._stream()))
+
+    def restore_positions(self):
+        """tgnh_restore_positions: the positions (and charges) as the last scale_positions(save=True) read them, bit for bit."""
+        _check(self.lib.tgnh_restore_positions(self.h, self._stream()))
 
     def setVelocitiesToTemperature(self, temperature, randomSeed=None, drudeTemperature=None, removeCMMotion=False, exact=False):
         """OpenMM's Context.setVelocitiesToTemperature, Drude-aware and drawn on the device (tgnh_set_velocities_to_temperature):

@@ -1,5 +1,5 @@
 // Stand-alone driver of the host-only sanitizer build (run_host_driver_asan.sh): the host side of tgnh_set_temperatures and
-// tgnh_set_velocities_to_temperature, and the argument checks of the centre-of-mass and velocity-rescaling calls, through a host-only handle (device -1),
+// tgnh_set_velocities_to_temperature, the argument checks of the centre-of-mass and velocity-rescaling calls, and the molecule table of tgnh_scale_positions, through a host-only handle (device -1),
 // no Python in the process.  What needs a device --
 // the upload of the retargeted block, the partner table's first use and the launch -- is not reached here.
 #include <cmath>
@@ -80,6 +80,20 @@ static int run(int mode, int chains, int drude_chains) {
     EXPECT(tgnh_set_velocity_rescaling(a, 4, 350, 2) == TGNH_OK && tgnh_step_begin(a, nullptr) == TGNH_ERR_STATE);
     EXPECT(tgnh_set_velocity_rescaling(a, 0, 350, 2) == TGNH_OK);
     EXPECT(tgnh_get_dof(a, nullptr, nkt1.data()) == TGNH_OK && nkt0 == nkt1);                                  // the baths are whose they were
+    // the molecule table: the default from resid, labels in two runs and longer than a wavefront, a split pair, the host-only refusals
+    int nmol = 0;
+    std::vector<int32_t> lab(N), out(N, -1);
+    EXPECT(tgnh_get_num_molecules(a, &nmol) == TGNH_OK && nmol == mols);
+    for (int i = 0; i < N; i++) lab[i] = i < 70 ? -5 : (i / 5 == mols - 1 ? -5 : 1000000 + i / 5);              // 75 slots in two runs, the rest per water
+    EXPECT(tgnh_set_molecules(a, lab.data()) == TGNH_OK && tgnh_get_num_molecules(a, &nmol) == TGNH_OK && nmol == mols - 14);
+    EXPECT(tgnh_get_molecules(a, out.data()) == TGNH_OK && out[0] == 0 && out[N - 1] == 0 && out[70] == 1 && out[N - 6] == mols - 15);
+    lab[1] = 7;                                                                                                // Drude of pair 0 alone
+    EXPECT(tgnh_set_molecules(a, lab.data()) == TGNH_ERR_ARG && tgnh_get_num_molecules(a, &nmol) == TGNH_OK && nmol == mols - 14);
+    EXPECT(tgnh_set_molecules(a, nullptr) == TGNH_OK && tgnh_get_num_molecules(a, &nmol) == TGNH_OK && nmol == mols);
+    const double sc[3] = {1.01, 0.99, 1.0}, bad[3] = {1.0, 0.0, 1.0};
+    EXPECT(tgnh_scale_positions(a, nullptr, 0, nullptr) == TGNH_ERR_ARG && tgnh_scale_positions(a, bad, 0, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_scale_positions(a, odd, 1, nullptr) == TGNH_ERR_ARG && tgnh_scale_positions(a, sc, 1, nullptr) == TGNH_ERR_STATE);
+    EXPECT(tgnh_restore_positions(a, nullptr) == TGNH_ERR_STATE && tgnh_restore_positions(nullptr, nullptr) == TGNH_ERR_ARG);
     EXPECT(tgnh_destroy(a) == TGNH_OK && tgnh_destroy(b) == TGNH_OK);
     return 0;
 }

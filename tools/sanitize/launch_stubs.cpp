@@ -2,6 +2,7 @@
 // fail, so that the host units (csrc/tgnh_*.cpp: topology, tiles, dof, orchestration) can be compiled with g++ -fsanitize and
 // exercised through host-only handles (device -1) on a machine without a GPU.  Nothing here ships.
 #include "../../openmm_drudenose_amd/csrc/tgnh_internal.h"
+#include "../../openmm_drudenose_amd/csrc/tgnh_scale_positions.h"
 
 namespace tgnh {
 hipError_t launch_tile(int, int, int, const TileArgs&, int, size_t, hipStream_t) { return hipErrorNoDevice; }
@@ -24,6 +25,8 @@ hipError_t launch_cm_momentum(int, const void*, int, CmRow*, int, hipStream_t) {
 hipError_t launch_cm_shift(int, void*, int, const double*, const double*, int, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_rescale_put(double*, const double*, int, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_rescale_factors(const double*, const double*, int, double*, uint32_t*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_scale_positions_spans(int, const ScalePosArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_scale_positions_table(int, const ScalePosArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_gather_com(int, const GatherArgs&, hipStream_t) { return hipErrorNoDevice; }
 int gather_ke_grid(const GatherArgs&) { return 1; }
 hipError_t launch_gather_ke(int, const GatherArgs&, int, hipStream_t) { return hipErrorNoDevice; }
