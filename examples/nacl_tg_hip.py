@@ -7,7 +7,11 @@ call-out is the harness spring force.  Needs a GPU.
 Note on what it prints: the harness force makes every site an independent harmonic oscillator, the textbook case in
 which a Nose-Hoover thermostat is not ergodic -- instantaneous temperatures swing widely and only their long-time
 means approach the targets (three chain links help; the CPU oracle shows the same numbers).  With a real force
-field the thermostats hold their targets: tests/test_reference_water*.py (216 interacting waters, within 1.4 %)."""
+field the thermostats hold their targets: tests/test_reference_water*.py (216 interacting waters, within 1.4 %).
+
+--dcd PATH writes a frame every 1000 steps (the reference's DCDReporter(dcdfile, 1000)) through reporters.DCDReporter, Drude
+particles included, in a cubic cell around the generated sites; the frames are wrapped into it on the way to the file and the
+positions themselves are left alone (the harness' tether force is not periodic).  Without the argument nothing changes."""
 import sys, os
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from drudetgnhplugin import DrudeTGNHIntegrator, HipContext           # the reference: from drudetgnhplugin import *
@@ -19,6 +23,12 @@ integ.setMaxDrudeDistance(0.02)                                                 
 system, group, ngroups = synth.nacl()
 context = HipContext(system, integ, mode="TGNH", precision="mixed")                          # 'CudaPrecision': 'mixed', nacl_tg.py:60
 context.setVelocitiesToTemperature(temperature)                                             # nacl_tg.py:80 (Drude motion at the integrator's 1 K)
+reporter = None
+if "--dcd" in sys.argv:                                                                      # nacl_tg.py: DCDReporter(dcdfile, 1000)
+    from openmm_drudenose_amd.reporters import DCDReporter
+    edge = float(system.positions.max() - system.positions.min()) + 0.31
+    context.setPeriodicBoxVectors((edge, 0, 0), (0, edge, 0), (0, 0, edge))
+    reporter = DCDReporter(sys.argv[sys.argv.index("--dcd") + 1], 1000)
 print("Simulating...")
 dof, nkt = context.dof()
 mean, n = 0.0, 0
@@ -26,7 +36,11 @@ for block in range(1, 21):
     for _ in range(10):
         integ.step(100)                                                                      # nacl_tg.py:94-95
         mean, n = mean + context.compute_kinetic_energies() / dof / synth.KB, n + 1
+    if reporter is not None:
+        reporter.report(context)
     t, steps = context.time()
     print(f"step {steps:6d}  time {t:7.3f} ps  KE {integ.computeKineticEnergy():10.3f} kJ/mol  "
           f"<T>(group, COM, Drude) so far = {', '.join(f'{x:7.2f}' for x in mean / n)} K")
+if reporter is not None:
+    reporter.close()
 print("Done!")

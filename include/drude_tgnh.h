@@ -437,6 +437,75 @@ tgnh_status tgnh_get_molecules(tgnh_handle h, int32_t* molecule_out /* [N] */);
 tgnh_status tgnh_scale_positions(tgnh_handle h, const double scale[3], int save, void* stream);
 tgnh_status tgnh_restore_positions(tgnh_handle h, void* stream);
 
+/* The periodic box, whole molecules wrapped into it on the device, and compact fp32 frames: what the reference's example takes
+ * from OpenMM as getState(getPositions=True, enforcePeriodicBox=True) and DCDReporter (example/nacl_tg.py), for a host without
+ * OpenMM and for a particle-sharded run, without the fp64 positions leaving the device.  A run whose barostat scales its molecules
+ * (tgnh_scale_positions) and never wraps lets them diffuse out of the cell: coordinates grow, and in single and mixed precision
+ * that costs position bits.
+ *
+ * THE BOX.  tgnh_set_periodic_box takes the three box vectors in OpenMM's reduced form, as Context::setPeriodicBoxVectors demands
+ * it (recalled from OpenMM's documentation; OpenMM was not at hand to check against):
+ *   a = (ax, 0, 0),  b = (bx, by, 0),  c = (cx, cy, cz);   ax, by, cz > 0;   ax >= 2 |bx|,  ax >= 2 |cx|,  by >= 2 |cy|;
+ *   every component finite.
+ * Anything else: TGNH_ERR_ARG, and the box in force stays as it was.  The box is kept on the host -- the call works on a host-only
+ * handle -- and tgnh_get_periodic_box returns the stored doubles bit for bit (TGNH_ERR_STATE before the first set).  It travels
+ * with each launch by value, as tgnh_scale_velocities' factors do: a recorded hipGraph bakes in the box it was recorded with.
+ * tgnh_scale_positions does not touch the box: the caller sets the new one after an accepted move.  SHARDED RUNS: every rank sets
+ * the same box; nothing is exchanged.
+ *
+ * tgnh_wrap_molecules.  Per molecule of the table in force (THE MOLECULE TABLE above: the same default, the same TGNH_ERR_STATE
+ * without one), everything in fp64, every operation rounded on its own (no fused multiply-add).  S, n and c = S / (double)n are
+ * exactly tgnh_scale_positions': the same coordinates x(i), the same order of additions for n <= 64 and for n > 64.  Then
+ *   kz = floor(c_z / cz);            d = (kz cx, kz cy, kz cz)
+ *   ky = floor((c_y - d_y) / by);    d_x = d_x + ky bx;   d_y = d_y + ky by
+ *   kx = floor((c_x - d_x) / ax);    d_x = d_x + kx ax
+ * -- OpenMM's enforcePeriodicBox arithmetic as recalled: molecule centres into the cell [0, L), z first.  A molecule with
+ * kx == ky == kz == 0, or with a centroid that is not finite, is NOT WRITTEN AT ALL: its posq and posq_correction stay bit for bit
+ * (in mixed precision the hi / lo split is not re-normalised; the positions of a run that has blown up stay as evidence).  Every
+ * other molecule: x' = x(i) - d, stored exactly as tgnh_scale_positions stores; posq.w and posq_correction.w are stored back bit
+ * for bit.  Cell indices are integers and d is formed from them and the box alone: the same positions, table and box give the same
+ * bits from any handle -- tiled or TGNH_FLAG_GATHER, TGNH or DUALNH, asked once or twice from the same positions.
+ * It enqueues on `stream`, waits for nothing and is capturable; the device tables are made outside a capture by
+ * tgnh_scale_positions' rule (a first call on a capturing stream: TGNH_ERR_STATE).  Positions are not velocities: the call does NOT
+ * do what tgnh_state_changed does; tgnh_get_pending_state, the carried kinetic energies, the sweep direction and the thermostat
+ * stay as they are.  It is NOT refused while a half kick is owed to velm: the forces of a periodic system do not change when a
+ * whole molecule moves by box vectors, so the owed kick is the same kick.  The harness' tether force is NOT periodic and its sites
+ * are not moved: a caller of tgnh_run_harness* does not wrap.  The snapshot of tgnh_scale_positions(save) is left alone: a
+ * tgnh_restore_positions after a wrap gives the positions from before it.
+ * TGNH_ERR_STATE: no box set (checked first, so a host-only handle answers it); then: buffers not bound, a host-only handle, no
+ * molecule table and no resid.  Follows tgnh_get_status_flags' rule for sticky failures, as the step entry points do.
+ *
+ * tgnh_write_frame: ONE READ-ONLY pass over the bound positions that leaves fp32 coordinates in `out`, a device pointer of the
+ * caller's.  It never writes posq, posq_correction or anything else of the trajectory; it needs no tgnh_flush (only velm ever
+ * lags), does not synchronise and is capturable.  Per slot i and output index j, in fp64 and rounded once to float:
+ *   value = (float)((x(i) - d) * unit)
+ * with d the slot's molecule's shift as above under TGNH_FRAME_WRAP, and d = +0.0 without the flag or for a molecule that
+ * tgnh_wrap_molecules would not move.  Planar layout (the default; what a DCD record is): component k at out[k * stride + j];
+ * TGNH_FRAME_INTERLEAVED: component k at out[3 j + k].  Floats of `out` that are no coordinate -- the gap between count and stride,
+ * anything beyond -- are not written.  j = i; with TGNH_FRAME_SKIP_DRUDE the Drude slots (pair_drude) are left out and j = i minus
+ * the number of Drude slots below i.  tgnh_get_frame_count returns the number of output indices, N or N minus the Drude slots, on a
+ * host-only handle too.  Without TGNH_FRAME_WRAP the call needs neither a box nor a molecule table: a DUALNH handle created without
+ * resid can write frames.  Out of scope: writing straight into pinned host memory; the caller copies the frame.
+ * TGNH_ERR_ARG, checked first so that a host-only handle answers it: desc or out is NULL, desc->struct_size is not
+ * sizeof(tgnh_frame_desc), an unknown flag, unit not finite or <= 0, stride < count (planar) or stride != 0 (interleaved), capacity
+ * smaller than 2 stride + count (planar) or 3 count (interleaved); and where the runtime knows the allocation behind `out`, fewer
+ * than `capacity` floats behind the pointer (not looked at on a capturing stream).  TGNH_ERR_STATE: TGNH_FRAME_WRAP without a box or
+ * without a molecule table, buffers not bound, a host-only handle; on a capturing stream, a table the call needs that is not on the
+ * device yet (call once with the same flags outside the capture).  SHARDED RUNS: every rank writes its own slots. */
+tgnh_status tgnh_set_periodic_box(tgnh_handle h, const double a[3], const double b[3], const double c[3]);
+tgnh_status tgnh_get_periodic_box(tgnh_handle h, double a[3], double b[3], double c[3]);
+tgnh_status tgnh_wrap_molecules(tgnh_handle h, void* stream);
+enum { TGNH_FRAME_WRAP = 1, TGNH_FRAME_SKIP_DRUDE = 2, TGNH_FRAME_INTERLEAVED = 4 };
+typedef struct tgnh_frame_desc {
+    uint32_t struct_size;   /* sizeof(tgnh_frame_desc); anything else: TGNH_ERR_ARG */
+    int32_t  flags;         /* TGNH_FRAME_*; any other bit: TGNH_ERR_ARG */
+    double   unit;          /* every coordinate is multiplied by it (10.0: nm -> Angstrom, DCD's unit) */
+    int64_t  stride;        /* planar layout: floats between the x, y and z planes, >= count; interleaved: must be 0 */
+    int64_t  capacity;      /* floats behind `out` */
+} tgnh_frame_desc;
+tgnh_status tgnh_get_frame_count(tgnh_handle h, int32_t flags, int64_t* count);
+tgnh_status tgnh_write_frame(tgnh_handle h, const tgnh_frame_desc* desc, float* out /* device */, void* stream);
+
 /* Velocity rescaling: one factor per thermostat applied to the bound velocities the way the integrator's own rescale applies the
  * chain's (ReferenceDrudeTGNHKernels.cpp:516-541; CUDA kernel integrateDrudeTGNHChain), and the factors that put every thermostat's
  * kinetic energy onto its N kT at once -- an exact-temperature start after tgnh_set_velocities_to_temperature, velocity-rescaling

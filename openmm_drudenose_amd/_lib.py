@@ -54,6 +54,16 @@ class TgnhMomentum(C.Structure):
     ]
 
 
+FRAME_WRAP, FRAME_SKIP_DRUDE, FRAME_INTERLEAVED = 1, 2, 4
+
+
+class TgnhFrameDesc(C.Structure):
+    """tgnh_frame_desc (tgnh_write_frame)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("flags", C.c_int32), ("unit", C.c_double), ("stride", C.c_int64), ("capacity", C.c_int64),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p)
 
 # name -> (restype, argtypes); every symbol include/drude_tgnh.h declares
@@ -107,6 +117,12 @@ SIGNATURES = {
     "tgnh_get_molecules": (C.c_int, [C.c_void_p, c_i32p]),
     "tgnh_scale_positions": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_void_p]),
     "tgnh_restore_positions": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tgnh_set_periodic_box": (C.c_int, [C.c_void_p, c_f64p, c_f64p, c_f64p]),
+    "tgnh_get_periodic_box": (C.c_int, [C.c_void_p, c_f64p, c_f64p, c_f64p]),
+    "tgnh_wrap_molecules": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tgnh_get_frame_count": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
+    # (desc: a TgnhFrameDesc by reference; out: a device pointer)
+    "tgnh_write_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tgnh_set_temperatures": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "tgnh_note_replayed_steps": (C.c_int, [C.c_void_p, C.c_int]),
     "tgnh_set_time": (C.c_int, [C.c_void_p, C.c_double, C.c_int64]),

@@ -3,7 +3,8 @@
 Inside OpenMM leave it alone: the System's own MonteCarloBarostat acts there (the reference's example adds one,
 example/nacl_tg.py:13-14, 56-57).  Here the trial move is the library's tgnh_scale_positions -- every molecule moved rigidly,
 on the device, snapshot in the same launch -- and a rejected move is tgnh_restore_positions.  The library knows no potential
-energy and no periodic box: the caller hands in both.
+energy, and the move does not touch the library's periodic box: the caller hands in both, and after an accepted move sets the new
+box itself (context.setPeriodicBoxVectors) where it wraps molecules or writes wrapped frames.
 """
 import math
 

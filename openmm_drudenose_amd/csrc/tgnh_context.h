@@ -111,14 +111,27 @@ struct tgnh_context {
             bool spans = false;               // every molecule a run of consecutive slots no longer than a wavefront: the span kernel serves it
             std::vector<int> span_first;      // [spans + 1] spans of whole molecules, <= 64 slots each
             std::vector<unsigned long long> span_heads;   // [spans] bit l: a molecule starts at lane l of the span
+            std::vector<int> span_out;        // [spans] tgnh_write_frame without Drude slots: the output index of the span's first kept slot
+            std::vector<unsigned long long> span_drude;   // [spans] ... and bit l: lane l of the span is a Drude slot
         } t;
         bool set = false;                 // t is in force (tgnh_set_molecules, or the default resolved at the first call that needed one)
         bool on_device = false;           // the copies below are t's: made at tgnh_set_molecules on a device handle or at the first launching call
         tgnh::DeviceBuf<int> d_span_first, d_mol_of, d_mem_start, d_members;      // spans: the first; otherwise the other three
         tgnh::DeviceBuf<unsigned long long> d_span_heads;
+        tgnh::DeviceBuf<int> d_span_out;  // spans: the two words more of a frame without Drude slots
+        tgnh::DeviceBuf<unsigned long long> d_span_drude;
         tgnh::DeviceBuf<double> d_shift;  // [3 count] table path: d of every molecule, written by its first launch
-        void drop_device() { on_device = false; d_span_first.reset(); d_mol_of.reset(); d_mem_start.reset(); d_members.reset(); d_span_heads.reset(); d_shift.reset(); }
+        void drop_device() { on_device = false; d_span_first.reset(); d_mol_of.reset(); d_mem_start.reset(); d_members.reset(); d_span_heads.reset(); d_shift.reset(); d_span_out.reset(); d_span_drude.reset(); }
     } mol;
+    struct PeriodicBox {              // tgnh_set_periodic_box (tgnh_frames.cpp): host side only, handed to every launch by value
+        bool set = false;
+        double a[3] = {0, 0, 0}, b[3] = {0, 0, 0}, c[3] = {0, 0, 0};     // the caller's doubles, bit for bit
+    } box;
+    struct Frames {                   // tgnh_write_frame without Drude slots, by slot index (the table form, the plain frame): no molecule table in it
+        std::vector<int> out_index;       // [N] output index of a slot, -1 for a Drude slot; built at the first call that asks (frame_index)
+        int kept = -1;                    // N minus the Drude slots (-1: not counted yet)
+        tgnh::DeviceBuf<int> d_out_index; // made once, never inside a capture
+    } frames;
     struct PositionSnapshot {         // tgnh_scale_positions(save) -> tgnh_restore_positions: allocated at the first saving call
         tgnh::DeviceBytes d_posq, d_corr; // one copy of posq, and of posq_correction in mixed precision
         bool taken = false;               // a saving call has filled it

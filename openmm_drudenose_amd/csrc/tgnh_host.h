@@ -1,7 +1,7 @@
 // tgnh_host.h -- what the host units behind the C ABI (include/drude_tgnh.h) share: tgnh_topology.cpp, tgnh_lifecycle.cpp,
-// tgnh_exchange.cpp, tgnh_step.cpp, tgnh_queries.cpp, tgnh_positions.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
+// tgnh_exchange.cpp, tgnh_step.cpp, tgnh_queries.cpp, tgnh_positions.cpp, tgnh_frames.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
 // live in tgnh_kernels.hip (tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h), tgnh_gather.hip, tgnh_velinit.hip,
-// tgnh_drude_stats.hip, tgnh_cm_motion.hip, tgnh_rescale.hip, tgnh_scale_positions.hip and tgnh_harness.hip.
+// tgnh_drude_stats.hip, tgnh_cm_motion.hip, tgnh_rescale.hip, tgnh_scale_positions.hip, tgnh_wrap.hip and tgnh_harness.hip.
 //
 // Reference semantics followed (scychon/openmm_drudeNose):
 //   Ref = platforms/reference/src/ReferenceDrudeTGNHKernels.cpp
@@ -63,6 +63,8 @@ tgnh_status ke_query_launches(tgnh_handle h, hipStream_t s);    // tgnh_queries.
 tgnh_status cm_scratch(tgnh_handle h);                                          // the rows of the momentum pass, allocated once
 tgnh_status cm_momentum_launches(tgnh_handle h, hipStream_t s, CmRow** result);   // pass + row sum of the bound velm -> *result (device)
 // tgnh_positions.cpp
+tgnh_status molecules_ensure(tgnh_context* c, const char* what);              // the table in force: the caller's, or the default resolved now (TGNH_ERR_STATE: no resid)
+tgnh_status molecules_launch_bounds(const tgnh_context* c);                   // what the launches over the table are bound by, against what the tables hold
 tgnh_status molecules_device(tgnh_context* c, hipStream_t s);                 // the molecule table's device copies, made once per table (never inside a capture)
 
 // a launch between two events when timing is on (tgnh_timing_enable)

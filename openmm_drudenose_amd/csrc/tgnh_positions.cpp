@@ -1,4 +1,5 @@
 // tgnh_positions.cpp -- the molecule table (labels, pair check, spans and member lists, eligibility for the span kernel), tgnh_scale_positions and its snapshot, tgnh_restore_positions
+// (tgnh_frames.cpp has the table's other user: the periodic box, tgnh_wrap_molecules, tgnh_write_frame)
 #include <unordered_map>
 
 #include "tgnh_host.h"
@@ -65,6 +66,19 @@ static tgnh_status molecules_build(tgnh_context* c, const int32_t* label, const 
             m.span_heads.back() |= 1ull << (b - m.span_first.back());
         }
         m.span_first.push_back(N);
+        // a frame without Drude slots: where a span's kept slots start in the output, and which of its lanes are left out
+        std::vector<char> drude((size_t)N, 0);
+        for (int d : c->topo.pair_drude) drude[d] = 1;
+        int kept = 0;
+        for (size_t k = 0; k + 1 < m.span_first.size(); k++) {
+            unsigned long long mask = 0ull;
+            m.span_out.push_back(kept);
+            for (int i = m.span_first[k]; i < m.span_first[k + 1]; i++) {
+                if (drude[i]) mask |= 1ull << (i - m.span_first[k]);
+                else kept++;
+            }
+            m.span_drude.push_back(mask);
+        }
     }
     c->mol.drop_device();                // (the old table's device copies; the next launching call uploads these: the caller has made the device current)
     c->mol.t = std::move(m);
@@ -73,7 +87,7 @@ static tgnh_status molecules_build(tgnh_context* c, const int32_t* label, const 
 }
 
 // the table in force: the caller's, or the default (the descriptor's resid) resolved at the first call that needs one
-static tgnh_status molecules_ensure(tgnh_context* c, const char* what) {
+tgnh_status molecules_ensure(tgnh_context* c, const char* what) {
     if (c->mol.set) return TGNH_OK;
     if ((int)c->topo.resid.size() != c->d.num_particles)
         return fail(TGNH_ERR_STATE, std::string(what) + ": the handle was created without resid, so there is no default molecule table: call tgnh_set_molecules first");
@@ -102,6 +116,8 @@ tgnh_status molecules_device(tgnh_context* c, hipStream_t s) {
                 return fail(TGNH_ERR_STATE, "internal: a span longer than a wavefront");
         HIP_OK(m.d_span_first.upload(t.span_first));
         HIP_OK(m.d_span_heads.upload(t.span_heads));
+        HIP_OK(m.d_span_out.upload(t.span_out));
+        HIP_OK(m.d_span_drude.upload(t.span_drude));
     } else {
         HIP_OK(m.d_mol_of.upload(t.mol_of));
         HIP_OK(m.d_mem_start.upload(t.mem_start));
@@ -147,7 +163,7 @@ static size_t posq_bytes(const tgnh_context* c) { return (size_t)c->d.num_partic
 static size_t corr_bytes(const tgnh_context* c) { return c->d.precision == TGNH_PREC_MIXED ? (size_t)c->d.num_particles * 16 : 0; }
 
 // what the launches are bound by, against what the tables hold: a launch that would run off a buffer is not made
-static tgnh_status scale_launch_bounds(const tgnh_context* c) {
+tgnh_status molecules_launch_bounds(const tgnh_context* c) {
     const tgnh_context::Molecules& m = c->mol;
     const tgnh_context::Molecules::Table& t = m.t;
     const int N = c->d.num_particles;
@@ -155,7 +171,8 @@ static tgnh_status scale_launch_bounds(const tgnh_context* c) {
         return fail(TGNH_ERR_STATE, "internal: the molecule table does not match the handle");
     if (t.spans) {
         const size_t ns = t.span_heads.size();
-        if (ns < 1 || t.span_first.size() != ns + 1 || t.span_first.front() != 0 || t.span_first.back() != N || !m.d_span_first || !m.d_span_heads)
+        if (ns < 1 || t.span_first.size() != ns + 1 || t.span_first.front() != 0 || t.span_first.back() != N || !m.d_span_first || !m.d_span_heads ||
+            t.span_out.size() != ns || t.span_drude.size() != ns || !m.d_span_out || !m.d_span_drude)
             return fail(TGNH_ERR_STATE, "internal: the span table does not cover the slots");
     } else if ((int)t.members.size() != N || (int)t.mem_start.size() != t.count + 1 || t.mem_start.back() != N || !m.d_mol_of || !m.d_mem_start ||
                !m.d_members || !m.d_shift)
@@ -182,7 +199,7 @@ extern "C" tgnh_status tgnh_scale_positions(tgnh_handle h, const double scale[3]
         HIP_OK(snap.d_posq.alloc(posq_bytes(h)));
         if (corr_bytes(h)) HIP_OK(snap.d_corr.alloc(corr_bytes(h)));
     }
-    rc = scale_launch_bounds(h); if (rc) return rc;
+    rc = molecules_launch_bounds(h); if (rc) return rc;
     const tgnh_context::Molecules& m = h->mol;
     ScalePosArgs a{};
     a.posq = h->bound.posq; a.corr = h->bound.posq_corr; a.n = h->d.num_particles;

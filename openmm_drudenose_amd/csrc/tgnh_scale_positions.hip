@@ -21,57 +21,14 @@
 // tiles, pairs, flags or the step path, and no order of additions depends on a grid.
 //
 // A unit of its own so that the step kernels' units compile to what they compiled to before.
-#include "tgnh_device_math.h"
-#include "tgnh_scale_positions.h"
+#include "tgnh_molecule_device.h"
 
 namespace tgnh {
 
 // every product, quotient and sum below is rounded on its own, as the header writes them (no fused multiply-add: a test restates them in numpy)
 #pragma clang fp contract(off)
 
-static_assert(BLOCK % 64 == 0 && SP_SPAN_SLOTS == 64, "whole wavefronts; a span is a wavefront's");
-
-// a slot as it lies in memory, and its coordinates as the header defines them
-template <int PREC> struct Site {
-    typename Prec<PREC>::real4 p;
-    float4 c;                                // mixed precision only
-    double x, y, z;
-};
-
-template <int PREC>
-__device__ __forceinline__ void site_load(const ScalePosArgs& a, const int i, Site<PREC>& s) {
-    s.p = static_cast<const typename Prec<PREC>::real4*>(a.posq)[i];
-    s.x = (double)s.p.x; s.y = (double)s.p.y; s.z = (double)s.p.z;
-    if (PREC == TGNH_PREC_MIXED) {
-        s.c = static_cast<const float4*>(a.corr)[i];
-        s.x = s.x + (double)s.c.x; s.y = s.y + (double)s.c.y; s.z = s.z + (double)s.c.z;
-    }
-}
-
-// x' = x + d in the position type; the snapshot first, from the registers the slot was read into
-template <int PREC>
-__device__ __forceinline__ void site_store(const ScalePosArgs& a, const int i, const Site<PREC>& s, const double dx, const double dy, const double dz) {
-    typedef typename Prec<PREC>::real4 R4;
-    typedef typename Prec<PREC>::real R;
-    if (a.snap_posq) {
-        static_cast<R4*>(a.snap_posq)[i] = s.p;
-        if (PREC == TGNH_PREC_MIXED) static_cast<float4*>(a.snap_corr)[i] = s.c;
-    }
-    const double nx = s.x + dx, ny = s.y + dy, nz = s.z + dz;
-    const R hx = (R)nx, hy = (R)ny, hz = (R)nz;
-    static_cast<R4*>(a.posq)[i] = mk4(hx, hy, hz, s.p.w);
-    if (PREC == TGNH_PREC_MIXED)
-        static_cast<float4*>(a.corr)[i] = make_float4((float)(nx - (double)hx), (float)(ny - (double)hy), (float)(nz - (double)hz), s.c.w);
-}
-
-// what a wavefront has written to its LDS image is read by other lanes of the same wavefront
-__device__ __forceinline__ void wave_image_ready() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-struct SpImage { double v[SP_WAVES][3][64]; };       // 6 KiB a work-group: x, y, z of a wavefront's 64 lanes, each wavefront its own
+// (Site, site_load, site_store, the LDS image and the two centroid walks: tgnh_molecule_device.h, shared with tgnh_wrap.hip)
 
 // the fast path: a wavefront per span
 template <int PREC>
@@ -85,21 +42,18 @@ __global__ __launch_bounds__(BLOCK) void sp_span_kernel(const ScalePosArgs a) {
     const bool on = lane < len;
     Site<PREC> s;
     s.x = s.y = s.z = 0.0;
-    if (on) site_load<PREC>(a, first + lane, s);
+    if (on) site_load<PREC>(a.posq, a.corr, first + lane, s);
     double (&im)[3][64] = img.v[w];
     im[0][lane] = s.x; im[1][lane] = s.y; im[2][lane] = s.z;
     wave_image_ready();
     if (!on) return;
-    // this lane's molecule: from the last head at or below the lane to the next head above it (or the span's end)
-    const unsigned long long below = heads & ((2ull << lane) - 1ull);            // (lane 63: 2 << 63 wraps to 0, the mask to all ones)
-    const int m0 = 63 - __clzll((long long)below);
-    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-    const int m1 = above ? min(lane + __ffsll((long long)above), len) : len;
-    double sx = im[0][m0], sy = im[1][m0], sz = im[2][m0];
-    for (int k = m0 + 1; k < m1; k++) { sx = sx + im[0][k]; sy = sy + im[1][k]; sz = sz + im[2][k]; }
+    int m0, m1;
+    span_molecule(heads, lane, len, m0, m1);
+    double sx, sy, sz;
+    image_sum(im, m0, m1, sx, sy, sz);
     const double nn = (double)(m1 - m0);
     const double dx = (sx / nn) * a.sm1[0], dy = (sy / nn) * a.sm1[1], dz = (sz / nn) * a.sm1[2];
-    site_store<PREC>(a, first + lane, s, dx, dy, dz);
+    site_store<PREC>(a.posq, a.corr, a.snap_posq, a.snap_corr, first + lane, s, dx, dy, dz);
 }
 
 // the table path, first launch: a wavefront per molecule -> shift[3 molecule]
@@ -111,23 +65,7 @@ __global__ __launch_bounds__(BLOCK) void sp_shift_kernel(const ScalePosArgs a) {
     if (mol >= a.num_molecules) return;                          // (a whole wavefront; no work-group barrier below)
     const int b = a.mem_start[mol], n = a.mem_start[mol + 1] - b;                 // (the host checked: n >= 1, the last molecule ends at a.n)
     double sx, sy, sz;
-    Site<PREC> s;
-    if (n <= 64) {
-        s.x = s.y = s.z = 0.0;
-        if (lane < n) site_load<PREC>(a, a.members[b + lane], s);
-        double (&im)[3][64] = img.v[w];
-        im[0][lane] = s.x; im[1][lane] = s.y; im[2][lane] = s.z;
-        wave_image_ready();
-        sx = im[0][0]; sy = im[1][0]; sz = im[2][0];
-        for (int k = 1; k < n; k++) { sx = sx + im[0][k]; sy = sy + im[1][k]; sz = sz + im[2][k]; }     // (every lane: the same additions)
-    } else {
-        double tx = 0.0, ty = 0.0, tz = 0.0;
-        for (int k = lane; k < n; k += 64) {
-            site_load<PREC>(a, a.members[b + k], s);
-            tx = tx + s.x; ty = ty + s.y; tz = tz + s.z;
-        }
-        sx = wave_sum(tx); sy = wave_sum(ty); sz = wave_sum(tz);      // (all 64 lanes are here: n is the wavefront's)
-    }
+    members_sum<PREC>(a.posq, a.corr, a.members, b, n, lane, img.v[w], sx, sy, sz);
     if (lane == 0) {
         const double nn = (double)n;
         double* d = a.shift + 3 * mol;
@@ -142,8 +80,8 @@ __global__ __launch_bounds__(BLOCK) void sp_apply_kernel(const ScalePosArgs a) {
         const int i = (int)it;
         const double* d = a.shift + 3 * (long long)a.mol_of[i];      // (inside [0, num_molecules): the table is the host's renumbering)
         Site<PREC> s;
-        site_load<PREC>(a, i, s);
-        site_store<PREC>(a, i, s, d[0], d[1], d[2]);
+        site_load<PREC>(a.posq, a.corr, i, s);
+        site_store<PREC>(a.posq, a.corr, a.snap_posq, a.snap_corr, i, s, d[0], d[1], d[2]);
     }
 }
 

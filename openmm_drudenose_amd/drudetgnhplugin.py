@@ -273,6 +273,31 @@ class _HandleQueries:
         _check(self.lib.tgnh_get_molecules(self.h, out.ctypes.data_as(_lib.c_i32p)))
         return out
 
+    # ---- the periodic box and the size of a frame (include/drude_tgnh.h: tgnh_set_periodic_box, tgnh_get_frame_count) ----
+    def setPeriodicBoxVectors(self, a, b, c):
+        """tgnh_set_periodic_box: the three box vectors (nm) in OpenMM's reduced form -- a = (ax, 0, 0), b = (bx, by, 0),
+        c = (cx, cy, cz), ax, by, cz > 0, ax >= 2 |bx|, ax >= 2 |cx|, by >= 2 |cy| --; anything else is refused and the box in force
+        stays.  Kept on the host: wrap_molecules() and frame(wrap=True) take it along by value."""
+        v = [np.ascontiguousarray(x, np.float64) for x in (a, b, c)]
+        if any(x.shape != (3,) for x in v):
+            raise TgnhError(_lib.ERR_ARG, "setPeriodicBoxVectors: three vectors of three components")
+        _check(self.lib.tgnh_set_periodic_box(self.h, *[x.ctypes.data_as(_lib.c_f64p) for x in v]))
+
+    def getPeriodicBoxVectors(self):
+        """tgnh_get_periodic_box: the box vectors as they were set, a [3, 3] array of rows a, b, c (nm); None before the first set."""
+        out = np.zeros((3, 3))
+        rc = self.lib.tgnh_get_periodic_box(self.h, *[out[k].ctypes.data_as(_lib.c_f64p) for k in range(3)])
+        if rc == _lib.ERR_STATE:
+            return None
+        _check(rc)
+        return out
+
+    def frame_count(self, skip_drude=False):
+        """tgnh_get_frame_count: the atoms of a frame -- every slot, or every slot that is no Drude particle."""
+        n = C.c_int64()
+        _check(self.lib.tgnh_get_frame_count(self.h, _lib.FRAME_SKIP_DRUDE if skip_drude else 0, C.byref(n)))
+        return n.value
+
 
 class HostTopology(_HandleQueries):
     """Host-only handle (device -1): the library's topology / tile / dof logic without a GPU.  Used by the CPU
@@ -741,6 +766,34 @@ class HipContext(_HandleQueries):
     def restore_positions(self):
         """tgnh_restore_positions: the positions (and charges) as the last scale_positions(save=True) read them, bit for bit."""
         _check(self.lib.tgnh_restore_positions(self.h, self._stream()))
+
+    # ---- whole molecules back into the cell, and frames for a trajectory file (tgnh_wrap_molecules, tgnh_write_frame) ----
+    def wrap_molecules(self):
+        """tgnh_wrap_molecules: every molecule of the table in force whose centroid lies outside the cell [0, L) of the box
+        (setPeriodicBoxVectors) moved by whole box vectors, on the device; a molecule inside is not written at all.  No host
+        synchronisation, no flush needed; velocities, thermostat and everything a step left pending stay as they are.  Not for a
+        run on the harness force: its tether is not periodic."""
+        _check(self.lib.tgnh_wrap_molecules(self.h, self._stream()))
+
+    def frame(self, wrap=False, skip_drude=False, unit=1.0, planes=False, out=None):
+        """tgnh_write_frame: the positions as a float32 tensor on the device, [count, 3] -- or [3, count] with planes=True, what a
+        DCD record is --, every coordinate times `unit` (10.0: Angstrom), formed in fp64 and rounded once.  wrap=True: as
+        wrap_molecules() would leave them, without touching the positions.  skip_drude=True leaves the Drude particles out
+        (count = frame_count(True)).  One read-only launch on the current stream; nothing is copied to the host.  out: a
+        contiguous float32 tensor of that shape on the context's device to write into."""
+        torch = self.torch
+        count = self.frame_count(skip_drude)
+        shape = (3, count) if planes else (count, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.dev)
+        elif out.dtype != torch.float32 or out.device != self.dev or tuple(out.shape) != shape or not out.is_contiguous():
+            raise TgnhError(_lib.ERR_ARG, f"frame: out must be a contiguous float32 tensor of shape {shape} on {self.dev}")
+        d = _lib.TgnhFrameDesc()
+        d.struct_size = C.sizeof(d)
+        d.flags = (_lib.FRAME_WRAP if wrap else 0) | (_lib.FRAME_SKIP_DRUDE if skip_drude else 0) | (0 if planes else _lib.FRAME_INTERLEAVED)
+        d.unit, d.stride, d.capacity = float(unit), count if planes else 0, 3 * count
+        _check(self.lib.tgnh_write_frame(self.h, C.byref(d), out.data_ptr(), self._stream()))
+        return out
 
     def setVelocitiesToTemperature(self, temperature, randomSeed=None, drudeTemperature=None, removeCMMotion=False, exact=False):
         """OpenMM's Context.setVelocitiesToTemperature, Drude-aware and drawn on the device (tgnh_set_velocities_to_temperature):

@@ -1,5 +1,6 @@
 // Stand-alone driver of the host-only sanitizer build (run_host_driver_asan.sh): the host side of tgnh_set_temperatures and
-// tgnh_set_velocities_to_temperature, the argument checks of the centre-of-mass and velocity-rescaling calls, and the molecule table of tgnh_scale_positions, through a host-only handle (device -1),
+// tgnh_set_velocities_to_temperature, the argument checks of the centre-of-mass and velocity-rescaling calls, the molecule table of tgnh_scale_positions, and the periodic
+// box, tgnh_get_frame_count and the argument order of tgnh_wrap_molecules / tgnh_write_frame, through a host-only handle (device -1),
 // no Python in the process.  What needs a device --
 // the upload of the retargeted block, the partner table's first use and the launch -- is not reached here.
 #include <cmath>
@@ -94,6 +95,42 @@ static int run(int mode, int chains, int drude_chains) {
     EXPECT(tgnh_scale_positions(a, nullptr, 0, nullptr) == TGNH_ERR_ARG && tgnh_scale_positions(a, bad, 0, nullptr) == TGNH_ERR_ARG);
     EXPECT(tgnh_scale_positions(a, odd, 1, nullptr) == TGNH_ERR_ARG && tgnh_scale_positions(a, sc, 1, nullptr) == TGNH_ERR_STATE);
     EXPECT(tgnh_restore_positions(a, nullptr) == TGNH_ERR_STATE && tgnh_restore_positions(nullptr, nullptr) == TGNH_ERR_ARG);
+    // the periodic box: reduced form or nothing, kept bit for bit; the frame's size; the argument checks before the host-only refusals
+    const double ba[3] = {0.83, 0, 0}, bb[3] = {0.17, 0.71, 0}, bc[3] = {-0.29, 0.23, 0.97}, wide[3] = {0.42, 0.71, 0}, tilt[3] = {0.83, 0, 1e-9};
+    double ga[3], gb[3], gc[3];
+    EXPECT(tgnh_get_periodic_box(a, ga, gb, gc) == TGNH_ERR_STATE && tgnh_wrap_molecules(a, nullptr) == TGNH_ERR_STATE);
+    EXPECT(tgnh_set_periodic_box(a, ba, wide, bc) == TGNH_ERR_ARG && tgnh_set_periodic_box(a, tilt, bb, bc) == TGNH_ERR_ARG);
+    EXPECT(tgnh_set_periodic_box(a, ba, odd, bc) == TGNH_ERR_ARG && tgnh_set_periodic_box(a, nullptr, bb, bc) == TGNH_ERR_ARG);
+    EXPECT(tgnh_get_periodic_box(a, ga, gb, gc) == TGNH_ERR_STATE);
+    EXPECT(tgnh_set_periodic_box(a, ba, bb, bc) == TGNH_OK && tgnh_set_periodic_box(a, bb, ba, bc) == TGNH_ERR_ARG);
+    EXPECT(tgnh_get_periodic_box(a, ga, gb, gc) == TGNH_OK && tgnh_get_periodic_box(a, nullptr, gb, gc) == TGNH_ERR_ARG);
+    for (int k = 0; k < 3; k++) EXPECT(ga[k] == ba[k] && gb[k] == bb[k] && gc[k] == bc[k]);
+    int64_t cnt = -1;
+    EXPECT(tgnh_get_frame_count(a, 0, &cnt) == TGNH_OK && cnt == N);
+    EXPECT(tgnh_get_frame_count(a, TGNH_FRAME_SKIP_DRUDE | TGNH_FRAME_WRAP, &cnt) == TGNH_OK && cnt == N - mols);
+    EXPECT(tgnh_get_frame_count(a, 8, &cnt) == TGNH_ERR_ARG && tgnh_get_frame_count(a, 0, nullptr) == TGNH_ERR_ARG && cnt == N - mols);
+    float* dev = reinterpret_cast<float*>(4096);                                                               // (never dereferenced: nothing launches)
+    tgnh_frame_desc fd{};
+    EXPECT(tgnh_write_frame(a, nullptr, dev, nullptr) == TGNH_ERR_ARG && tgnh_write_frame(a, &fd, dev, nullptr) == TGNH_ERR_ARG);   // struct_size 0
+    fd.struct_size = sizeof(fd); fd.flags = TGNH_FRAME_WRAP | TGNH_FRAME_SKIP_DRUDE; fd.unit = 10.0; fd.stride = N - mols + 7; fd.capacity = 2 * fd.stride + N - mols;
+    EXPECT(tgnh_write_frame(a, &fd, nullptr, nullptr) == TGNH_ERR_ARG && tgnh_write_frame(nullptr, &fd, dev, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_write_frame(a, &fd, dev, nullptr) == TGNH_ERR_STATE);                                          // host-only: nothing launches
+    fd.capacity -= 1;
+    EXPECT(tgnh_write_frame(a, &fd, dev, nullptr) == TGNH_ERR_ARG);
+    fd.capacity += 1; fd.stride = N - mols - 1;
+    EXPECT(tgnh_write_frame(a, &fd, dev, nullptr) == TGNH_ERR_ARG);
+    fd.flags = TGNH_FRAME_INTERLEAVED; fd.stride = 1; fd.capacity = 3 * N;
+    EXPECT(tgnh_write_frame(a, &fd, dev, nullptr) == TGNH_ERR_ARG);
+    fd.stride = 0; fd.unit = 0.0;
+    EXPECT(tgnh_write_frame(a, &fd, dev, nullptr) == TGNH_ERR_ARG);
+    fd.unit = 1.0; fd.flags |= 16;
+    EXPECT(tgnh_write_frame(a, &fd, dev, nullptr) == TGNH_ERR_ARG);
+    fd.flags = TGNH_FRAME_INTERLEAVED;
+    EXPECT(tgnh_write_frame(a, &fd, dev, nullptr) == TGNH_ERR_STATE && tgnh_wrap_molecules(a, nullptr) == TGNH_ERR_STATE);
+    EXPECT(tgnh_write_frame(b, &fd, dev, nullptr) == TGNH_ERR_STATE && tgnh_wrap_molecules(nullptr, nullptr) == TGNH_ERR_ARG);
+    fd.flags = TGNH_FRAME_WRAP;
+    fd.capacity = 3 * N; fd.stride = N;
+    EXPECT(tgnh_write_frame(b, &fd, dev, nullptr) == TGNH_ERR_STATE);                                          // b has no box
     EXPECT(tgnh_destroy(a) == TGNH_OK && tgnh_destroy(b) == TGNH_OK);
     return 0;
 }

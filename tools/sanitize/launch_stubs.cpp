@@ -3,6 +3,7 @@
 // exercised through host-only handles (device -1) on a machine without a GPU.  Nothing here ships.
 #include "../../openmm_drudenose_amd/csrc/tgnh_internal.h"
 #include "../../openmm_drudenose_amd/csrc/tgnh_scale_positions.h"
+#include "../../openmm_drudenose_amd/csrc/tgnh_wrap.h"
 
 namespace tgnh {
 hipError_t launch_tile(int, int, int, const TileArgs&, int, size_t, hipStream_t) { return hipErrorNoDevice; }
@@ -27,6 +28,11 @@ hipError_t launch_rescale_put(double*, const double*, int, hipStream_t) { return
 hipError_t launch_rescale_factors(const double*, const double*, int, double*, uint32_t*, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_scale_positions_spans(int, const ScalePosArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_scale_positions_table(int, const ScalePosArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_wrap_spans(int, const WrapArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_wrap_table(int, const WrapArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_frame_spans(int, const WrapArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_frame_table(int, const WrapArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_frame_plain(int, const WrapArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_gather_com(int, const GatherArgs&, hipStream_t) { return hipErrorNoDevice; }
 int gather_ke_grid(const GatherArgs&) { return 1; }
 hipError_t launch_gather_ke(int, const GatherArgs&, int, hipStream_t) { return hipErrorNoDevice; }

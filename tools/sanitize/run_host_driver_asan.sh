@@ -1,6 +1,7 @@
 #!/bin/bash
 # Builds the host units (csrc/tgnh_*.cpp), the launch stubs and the stand-alone driver host_driver.cpp into ONE program with
-# AddressSanitizer + UBSan (g++, CPU only) and runs it: the host side of tgnh_set_temperatures / tgnh_set_velocities_to_temperature.
+# AddressSanitizer + UBSan (g++, CPU only) and runs it: the host side of tgnh_set_temperatures / tgnh_set_velocities_to_temperature,
+# the molecule table, the periodic box and the frame's argument checks.
 set -e
 cd "$(dirname "$0")/../.."
 OUT=$(mktemp -d)/tgnh_host_driver
