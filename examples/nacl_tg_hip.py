@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The reference's example (example/nacl_tg.py: 1 M NaCl(aq) in SWM4-NDP water, DrudeTGNHIntegrator(300 K, 0.1 ps,
-1 K, 0.1 ps, 1 fs, 20), hard wall 0.02 nm) on the MI355X HIP path.  OpenMM's force field, minimiser and reporters
-are not here: the topology (492 waters + 10 Na+ + 10 Cl-, 2500 sites, 512 Drude pairs) is generated and the force
+1 K, 0.1 ps, 1 fs, 20), hard wall 0.02 nm) on the MI355X HIP path.  OpenMM's force field and reporters are not here, and
+its minimiser's place is taken by the library's FIRE (HipContext.minimizeEnergy): the topology (492 waters + 10 Na+ +
+10 Cl-, 2500 sites, 512 Drude pairs) is generated and the force
 call-out is the harness spring force.  Needs a GPU.
 
 Note on what it prints: the harness force makes every site an independent harmonic oscillator, the textbook case in
@@ -22,6 +23,9 @@ integ = DrudeTGNHIntegrator(temperature, REALFREQ, 1.0, DRUDEFREQ, timestep, num
 integ.setMaxDrudeDistance(0.02)                                                              # nacl_tg.py:22
 system, group, ngroups = synth.nacl()
 context = HipContext(system, integ, mode="TGNH", precision="mixed")                          # 'CudaPrecision': 'mixed', nacl_tg.py:60
+print("Minimizing...")
+state = context.minimizeEnergy(maxIterations=20000)                                         # nacl_tg.py:71
+print(f"  {state.iterations} iterations, rms force {state.rms_force:.3f} kJ/mol/nm" + ("" if state.converged == 1 else " (not converged)"))
 context.setVelocitiesToTemperature(temperature)                                             # nacl_tg.py:80 (Drude motion at the integrator's 1 K)
 reporter = None
 if "--dcd" in sys.argv:                                                                      # nacl_tg.py: DCDReporter(dcdfile, 1000)

@@ -437,6 +437,93 @@ tgnh_status tgnh_get_molecules(tgnh_handle h, int32_t* molecule_out /* [N] */);
 tgnh_status tgnh_scale_positions(tgnh_handle h, const double scale[3], int save, void* stream);
 tgnh_status tgnh_restore_positions(tgnh_handle h, void* stream);
 
+/* Energy minimisation on the device: FIRE (Bitzek, Koskinen, Gaehler, Moseler, Gumbsch, Phys. Rev. Lett. 97, 170201, 2006) between
+ * the caller's force call-outs -- what the reference's example takes from OpenMM as simulation.minimizeEnergy (example/nacl_tg.py),
+ * for a host without OpenMM and for a particle-sharded run, without the positions leaving the device.  For a Drude system the call
+ * is not optional: a model builder puts every Drude particle on its parent, and a run must relax them before its first step.  The
+ * library knows no potential energy, so the method needs forces only; its accept / reset decision is three sums and lives on the
+ * device: a batch of {force call-out, tgnh_minimize_iterate} is enqueued with no host round trip.
+ *
+ * tgnh_minimize_begin(desc, work).  WHICH SLOTS MOVE: a slot moves if its mass in the descriptor is non-zero (virtual sites never
+ * move: the caller's virtual-site call-out places them), AND desc->moving is NULL or non-zero there, AND -- with
+ * TGNH_MIN_DRUDE_ONLY -- it is a Drude slot (pair_drude).  The mask, one byte per slot, is formed on the host and uploaded once.
+ * `work` is device memory of the caller's, 3 N doubles, the minimiser's velocity in planes work[k N + i], fp64 in every precision;
+ * begin zeroes it and initialises the state block on the device (dt = dt_start, alpha = alpha_start, all counters 0), then waits
+ * for `stream`.  A begin on a capturing stream returns TGNH_ERR_STATE and says so.  A begin while a minimisation is under way
+ * starts anew.  Units: masses are 1, so a displacement is dt^2 f with f in kJ/mol/nm: dt is not a time.
+ *
+ * tgnh_minimize_iterate: ONE ITERATION on whatever the bound force buffer holds.  Everything in fp64, every operation rounded on
+ * its own (no fused multiply-add).
+ *   1. SUMS over the moving slots, with f_k = (double)F_k[i] / 4294967296.0 (F the fixed-point force) and v_k = work[k N + i]:
+ *        P  = sum of (fx vx + fy vy) + fz vz        FF = sum of (fx fx + fy fy) + fz fz
+ *        VV = sum of (vx vx + vy vy) + vz vz        moving = sum of 1.0
+ *      added in exactly tgnh_get_momentum's order: the grid is a function of N alone (256 slots per work-group, at most 1024
+ *      work-groups, a grid-stride loop beyond); a thread adds its slots in ascending index order onto 0.0; a wavefront adds its 64
+ *      lanes in a fixed order; a work-group its wavefronts in wavefront order; one work-group adds the rows -- thread t the run of
+ *      consecutive rows [t c, (t + 1) c), c = ceil(rows / 256), then as a work-group does.  No floating-point atomic: the same
+ *      forces, `work` and mask give the same bits from any handle over the same slots.
+ *   2. EXCHANGE.  Where the handle has an all-reduce (tgnh_set_allreduce, or the library's RCCL) the four doubles
+ *      {P, FF, VV, moving} go through it in place, in one call of count 4.  SHARDED RUNS: the call is collective.
+ *   3. DECISION, by one thread on the device, on the state block.  Once converged != 0 the block stays as it is.  Otherwise
+ *        rms = sqrt(FF / (3.0 * moving));  the four sums and rms are stored
+ *        a sum is not finite:   converged = -1, nothing else changes
+ *        rms <= tolerance:      converged = 1, nothing else changes
+ *        iterations == 0:       a = 1, b = 0, dt and alpha as they are
+ *        P > 0:                 since_uphill++;  a = 1.0 - alpha;  b = (alpha * sqrt(VV)) / sqrt(FF);
+ *                               if since_uphill > n_min:  dt = min(dt * f_inc, dt_max);  alpha = alpha * f_alpha
+ *        else:                  uphill++;  since_uphill = 0;  a = b = 0;  dt = dt * f_dec;  alpha = alpha_start
+ *        then iterations++      (iterations counts updates: the decision that finds convergence does not count)
+ *      The mix uses alpha before its update; the update below uses dt after its update.
+ *   4. UPDATE, per moving slot and component k, unless converged != 0 (then this and every later update launch returns at once:
+ *      the positions stay those at which the converged forces were computed; a run that blew up stays as evidence):
+ *        v'  = (a * v) + (b * f);   v'' = v' + dt * f;   d = dt * v'';   r = sqrt((dx dx + dy dy) + dz dz)
+ *        r > max_step:  s = max_step / r (one division), every d = d * s
+ *        x'  = x + d, x as tgnh_scale_positions reads it and stored as tgnh_scale_positions stores it (mixed precision: hi / lo
+ *              re-normalised); posq.w and posq_correction.w go back bit for bit;  work = v'' (not scaled by s)
+ *      A slot that does not move is neither loaded nor written.
+ * Without an all-reduce the row sum and the decision share a launch (three launches an iteration); with one the decision is a
+ * launch of its own behind the hook (four).  The bits are the same.  Nothing waits for the device: capturable into a hipGraph.
+ *
+ * WHAT THE CALLS ARE NOT.  Like tgnh_scale_positions they are not a tgnh_state_changed: velm, the carried kinetic energies, the
+ * sweep direction, tgnh_get_pending_state, the thermostat and tgnh_scale_positions' snapshot stay as they are.  Begin and iterate
+ * are REFUSED with TGNH_ERR_STATE, positions untouched, while a half kick is owed to velm (bit 0 or 2 of tgnh_get_pending_state:
+ * tgnh_flush first).  The hard wall is not applied; tgnh_get_drude_statistics tells afterwards.  CONSTRAINTS are call-outs the
+ * minimiser does not make: a caller with constraints moves only slots no constraint touches (TGNH_MIN_DRUDE_ONLY, or a mask), or
+ * projects itself.  The caller recomputes the forces before the next step unless the minimisation ended converged = 1 (then the
+ * buffer holds the forces of the positions as they are).
+ *
+ * tgnh_get_minimize_state: the state block as the last decision left it (`moving`: this handle's own moving slots).  A query:
+ * synchronises `stream`.  tgnh_minimize_end frees mask, rows and state block (not `work`: the caller's); harmless without a begin.
+ * tgnh_run_harness_minimize: `iterations` x {the harness force into the bound force buffer, tgnh_minimize_iterate}, enqueued back
+ * to back, as tgnh_run_harness enqueues steps.
+ *
+ * TGNH_ERR_ARG, checked first so that a host-only handle answers it: desc or work is NULL, a parameter that is not finite,
+ * tolerance < 0, dt_start <= 0, dt_max < dt_start, max_step <= 0, f_inc < 1, f_dec or f_alpha outside (0, 1), alpha_start outside
+ * (0, 1], n_min < 0, unknown flag bits; a NULL `out`; iterations < 0.  TGNH_ERR_UNSUPPORTED: a MAILBOX exchange is attached (it
+ * carries the kinetic-energy sums only).  TGNH_ERR_STATE: buffers not bound, a host-only handle, iterate / get / run without a
+ * begin, no slot moves, a capturing stream at begin, an owed half kick.  Follows tgnh_get_status_flags' rule for sticky failures. */
+enum { TGNH_MIN_DRUDE_ONLY = 1 };
+typedef struct tgnh_minimize_desc {
+    double tolerance;          /* kJ/mol/nm: stop when the root mean square of the moving slots' force components is <= this (OpenMM's rule; its default 10) */
+    double dt_start, dt_max;   /* unit masses: a displacement is dt^2 f.  The Python layer's defaults: 1e-4, 1e-3 */
+    double max_step;           /* nm, per slot and iteration; default 0.01 */
+    double f_inc, f_dec, alpha_start, f_alpha;   /* 1.1, 0.5, 0.1, 0.99 */
+    int32_t n_min;             /* 5 */
+    int32_t flags;             /* TGNH_MIN_DRUDE_ONLY: only Drude slots move; any other bit: TGNH_ERR_ARG */
+    const uint8_t* moving;     /* host, [N] or NULL: a slot moves only where this is non-zero */
+} tgnh_minimize_desc;
+typedef struct tgnh_minimize_state {
+    int64_t iterations, uphill, since_uphill, moving;
+    int32_t converged;         /* 0 running, 1 rms <= tolerance, -1 a sum was not finite */
+    int32_t reserved;
+    double dt, alpha, power, ff, vv, rms_force;   /* of the last decision */
+} tgnh_minimize_state;
+tgnh_status tgnh_minimize_begin(tgnh_handle h, const tgnh_minimize_desc* desc, double* work /* device, 3 N doubles, the caller's */, void* stream);
+tgnh_status tgnh_minimize_iterate(tgnh_handle h, void* stream);
+tgnh_status tgnh_get_minimize_state(tgnh_handle h, void* stream, tgnh_minimize_state* out);   /* synchronises */
+tgnh_status tgnh_minimize_end(tgnh_handle h);
+tgnh_status tgnh_run_harness_minimize(tgnh_handle h, const void* x0, double k_drude, double k_tether, int iterations, void* stream);
+
 /* The periodic box, whole molecules wrapped into it on the device, and compact fp32 frames: what the reference's example takes
  * from OpenMM as getState(getPositions=True, enforcePeriodicBox=True) and DCDReporter (example/nacl_tg.py), for a host without
  * OpenMM and for a particle-sharded run, without the fp64 positions leaving the device.  A run whose barostat scales its molecules

@@ -64,6 +64,28 @@ class TgnhFrameDesc(C.Structure):
     ]
 
 
+MIN_DRUDE_ONLY = 1
+
+
+class TgnhMinimizeDesc(C.Structure):
+    """tgnh_minimize_desc (tgnh_minimize_begin)"""
+    _fields_ = [
+        ("tolerance", C.c_double), ("dt_start", C.c_double), ("dt_max", C.c_double), ("max_step", C.c_double),
+        ("f_inc", C.c_double), ("f_dec", C.c_double), ("alpha_start", C.c_double), ("f_alpha", C.c_double),
+        ("n_min", C.c_int32), ("flags", C.c_int32), ("moving", C.c_void_p),
+    ]
+
+
+class TgnhMinimizeState(C.Structure):
+    """tgnh_minimize_state (tgnh_get_minimize_state)"""
+    _fields_ = [
+        ("iterations", C.c_int64), ("uphill", C.c_int64), ("since_uphill", C.c_int64), ("moving", C.c_int64),
+        ("converged", C.c_int32), ("reserved", C.c_int32),
+        ("dt", C.c_double), ("alpha", C.c_double), ("power", C.c_double), ("ff", C.c_double), ("vv", C.c_double),
+        ("rms_force", C.c_double),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p)
 
 # name -> (restype, argtypes); every symbol include/drude_tgnh.h declares
@@ -117,6 +139,12 @@ SIGNATURES = {
     "tgnh_get_molecules": (C.c_int, [C.c_void_p, c_i32p]),
     "tgnh_scale_positions": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_void_p]),
     "tgnh_restore_positions": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # (desc: a TgnhMinimizeDesc by reference; work: a device pointer; out: a TgnhMinimizeState by reference)
+    "tgnh_minimize_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tgnh_minimize_iterate": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tgnh_get_minimize_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tgnh_minimize_end": (C.c_int, [C.c_void_p]),
+    "tgnh_run_harness_minimize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p]),
     "tgnh_set_periodic_box": (C.c_int, [C.c_void_p, c_f64p, c_f64p, c_f64p]),
     "tgnh_get_periodic_box": (C.c_int, [C.c_void_p, c_f64p, c_f64p, c_f64p]),
     "tgnh_wrap_molecules": (C.c_int, [C.c_void_p, C.c_void_p]),

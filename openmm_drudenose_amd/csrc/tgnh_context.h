@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "tgnh_internal.h"
+#include "tgnh_minimize.h"
 
 void tgnh_set_error(const std::string& msg);   // sets what tgnh_last_error() returns (tgnh_lifecycle.cpp)
 
@@ -138,6 +139,16 @@ struct tgnh_context {
         bool valid = false;               // ... and tgnh_bind_buffers has not rebound a position array since
         const void *of_posq = nullptr, *of_corr = nullptr;     // the arrays it was read from
     } snap;
+    struct Minimize {                 // tgnh_minimize_begin .. tgnh_minimize_end (tgnh_minimize.cpp): everything is allocated at begin, never inside a capture
+        bool active = false;              // between a begin that succeeded and the next end
+        double* work = nullptr;           // the caller's [3 N] doubles: the minimiser's velocity
+        int64_t moving = 0;               // this handle's moving slots
+        tgnh::DeviceBuf<unsigned char> d_mask;     // [N] non-zero: the slot moves
+        tgnh::DeviceBuf<double> d_rows;   // [cm_grid(N) + 1][4]: a row per work-group of the sums pass, then the four sums an all-reduce adds in place
+        tgnh::DeviceBuf<tgnh::MinState> d_state;
+        tgnh::MinState h_state{};         // what begin uploads, and where tgnh_get_minimize_state's copy lands
+        void drop() { active = false; work = nullptr; moving = 0; d_mask.reset(); d_rows.reset(); d_state.reset(); }
+    } minim;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block
         std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction

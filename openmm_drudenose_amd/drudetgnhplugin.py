@@ -376,6 +376,51 @@ class Momentum:
         return f"Momentum(mass={self.mass:.6g}, momentum={self.momentum.tolist()}, massive={self.massive}, velocity={self.velocity.tolist()})"
 
 
+class MinimizeState:
+    """What HipContext.minimizeEnergy and minimize_state return (read-only): tgnh_minimize_state as the last decision left it --
+    iterations (updates made), uphill (resets), since_uphill, moving (this context's moving slots), converged (0 running, 1 the
+    rms force is <= tolerance, -1 a sum was not finite), dt, alpha, power (f.v), ff, vv and rms_force (kJ/mol/nm)."""
+    __slots__ = ("iterations", "uphill", "since_uphill", "moving", "converged", "dt", "alpha", "power", "ff", "vv", "rms_force", "raw")
+
+    def __init__(self, st):
+        put = lambda k, v: object.__setattr__(self, k, v)    # noqa: E731
+        put("raw", bytes(st))                                # the struct as the library filled it in
+        for k in ("iterations", "uphill", "since_uphill", "moving", "converged"):
+            put(k, int(getattr(st, k)))
+        for k in ("dt", "alpha", "power", "ff", "vv", "rms_force"):
+            put(k, float(getattr(st, k)))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("MinimizeState is read-only")
+
+    def __repr__(self):
+        return (f"MinimizeState(iterations={self.iterations}, converged={self.converged}, rms_force={self.rms_force:.6g}, "
+                f"uphill={self.uphill}, dt={self.dt:.6g}, alpha={self.alpha:.6g}, moving={self.moving})")
+
+
+FIRE_DEFAULTS = dict(dt_start=1e-4, dt_max=1e-3, max_step=0.01, f_inc=1.1, f_dec=0.5, alpha_start=0.1, f_alpha=0.99, n_min=5)
+
+
+def minimize_desc(n, tolerance=10.0, drude_only=False, moving=None, **fire):
+    """-> (tgnh_minimize_desc, the mask array it points to or None: keep it alive for the call).  **fire: FIRE_DEFAULTS' names."""
+    unknown = set(fire) - set(FIRE_DEFAULTS)
+    if unknown:
+        raise TgnhError(_lib.ERR_ARG, f"minimize: unknown FIRE parameter(s) {sorted(unknown)}")
+    par = dict(FIRE_DEFAULTS, **fire)
+    d = _lib.TgnhMinimizeDesc()
+    d.tolerance = float(tolerance)
+    for k, v in par.items():
+        setattr(d, k, int(v) if k == "n_min" else float(v))
+    d.flags = _lib.MIN_DRUDE_ONLY if drude_only else 0
+    mask = None
+    if moving is not None:
+        mask = np.ascontiguousarray(np.asarray(moving) != 0, np.uint8)
+        if mask.shape != (n,):
+            raise TgnhError(_lib.ERR_ARG, "minimize: one mask entry per particle slot")
+        d.moving = mask.ctypes.data
+    return d, mask
+
+
 class HipContext(_HandleQueries):
     """Device state + handle: what OpenMM's Context / HIP platform data are to the reference kernel.
 
@@ -766,6 +811,73 @@ class HipContext(_HandleQueries):
     def restore_positions(self):
         """tgnh_restore_positions: the positions (and charges) as the last scale_positions(save=True) read them, bit for bit."""
         _check(self.lib.tgnh_restore_positions(self.h, self._stream()))
+
+    # ---- energy minimisation (include/drude_tgnh.h: tgnh_minimize_begin, tgnh_minimize_iterate, ...) ----
+    def minimize_begin(self, tolerance=10.0, drude_only=False, moving=None, **fire):
+        """tgnh_minimize_begin: which slots move, the FIRE parameters (FIRE_DEFAULTS), and the minimiser's velocity -- a float64
+        tensor [3, N] of this context's (self.minimize_work), zeroed by the call."""
+        d, mask = minimize_desc(self.n, tolerance, drude_only, moving, **fire)
+        self.minimize_work = self.torch.empty((3, self.n), dtype=self.torch.float64, device=self.dev)
+        _check(self.lib.tgnh_minimize_begin(self.h, C.byref(d), self.minimize_work.data_ptr(), self._stream()))
+
+    def minimize_iterate(self):
+        """tgnh_minimize_iterate: one FIRE iteration on whatever the force buffer holds; no host synchronisation."""
+        _check(self.lib.tgnh_minimize_iterate(self.h, self._stream()))
+
+    def minimize_state(self):
+        """tgnh_get_minimize_state.  Synchronises the stream."""
+        st = _lib.TgnhMinimizeState()
+        _check(self.lib.tgnh_get_minimize_state(self.h, self._stream(), C.byref(st)))
+        return MinimizeState(st)
+
+    def minimize_end(self):
+        _check(self.lib.tgnh_minimize_end(self.h))
+        self.minimize_work = None
+
+    def _minimize_batch(self, iterations):
+        """`iterations` x {virtual sites where the context has them, the force call-out, one iteration}, enqueued back to back"""
+        sites = self.system.site_atoms is not None and len(self.system.site_atoms) > 0
+        if self.force_fn is None and not sites:
+            _check(self.lib.tgnh_run_harness_minimize(self.h, self._x0_arg(), self.k_drude, self.k_tether, int(iterations), self._stream()))
+            return
+        for _ in range(iterations):
+            if sites:
+                _check(self.lib.tgnh_harness_virtual_sites(self.h, self._stream()))
+            self.compute_forces()
+            self.minimize_iterate()
+
+    def minimizeEnergy(self, tolerance=10.0, maxIterations=0, drude_only=False, moving=None, check_every=50, **fire):
+        """OpenMM's Context.minimizeEnergy plus the Drude option, by FIRE on the device between force call-outs: until the root
+        mean square of the moving slots' force components is <= tolerance (kJ/mol/nm), or for maxIterations iterations (0: until
+        converged).  drude_only=True moves only the Drude particles (the relaxation a Drude system needs before its first step);
+        moving: a mask, one entry per slot.  Massless slots never move.  The state is read back every check_every iterations;
+        nothing else waits for the device.  **fire: FIRE_DEFAULTS' names.  Constraints are not projected: a constrained context
+        is refused unless drude_only or a mask says which slots are free to move.  Velocities, thermostat and step count stay as
+        they are.  Returns a MinimizeState; unless it says converged == 1 the forces are recomputed at the final positions."""
+        if self.constrained and not drude_only and moving is None:
+            raise TgnhError(_lib.ERR_STATE, "minimizeEnergy: the context has constraints or virtual sites and the minimiser projects no "
+                                            "constraints: pass drude_only=True or a `moving` mask of slots that no constraint touches")
+        if check_every < 1 or maxIterations < 0:
+            raise TgnhError(_lib.ERR_ARG, "minimizeEnergy: check_every must be positive and maxIterations not negative")
+        self.flush()
+        self.minimize_begin(tolerance, drude_only, moving, **fire)
+        try:
+            done = 0
+            while True:
+                batch = int(check_every) if maxIterations == 0 else min(int(check_every), int(maxIterations) - done)
+                if batch > 0:
+                    self._minimize_batch(batch)
+                    done += batch
+                st = self.minimize_state()
+                if st.converged != 0 or batch <= 0 or (maxIterations and done >= maxIterations):
+                    break
+        finally:
+            self.minimize_end()
+        if st.converged != 1:                                # (the buffer holds the forces of the positions before the last update)
+            if self.system.site_atoms is not None and len(self.system.site_atoms) > 0:
+                _check(self.lib.tgnh_harness_virtual_sites(self.h, self._stream()))
+            self.compute_forces()
+        return st
 
     # ---- whole molecules back into the cell, and frames for a trajectory file (tgnh_wrap_molecules, tgnh_write_frame) ----
     def wrap_molecules(self):

@@ -1,6 +1,6 @@
 // Stand-alone driver of the host-only sanitizer build (run_host_driver_asan.sh): the host side of tgnh_set_temperatures and
 // tgnh_set_velocities_to_temperature, the argument checks of the centre-of-mass and velocity-rescaling calls, the molecule table of tgnh_scale_positions, and the periodic
-// box, tgnh_get_frame_count and the argument order of tgnh_wrap_molecules / tgnh_write_frame, through a host-only handle (device -1),
+// box, tgnh_get_frame_count and the argument order of tgnh_wrap_molecules / tgnh_write_frame, and the minimiser's argument checks and refusals, through a host-only handle (device -1),
 // no Python in the process.  What needs a device --
 // the upload of the retargeted block, the partner table's first use and the launch -- is not reached here.
 #include <cmath>
@@ -131,6 +131,34 @@ static int run(int mode, int chains, int drude_chains) {
     fd.flags = TGNH_FRAME_WRAP;
     fd.capacity = 3 * N; fd.stride = N;
     EXPECT(tgnh_write_frame(b, &fd, dev, nullptr) == TGNH_ERR_STATE);                                          // b has no box
+    // the minimiser: every argument check before the host-only refusal; the mask is never formed, nothing launches, end is harmless
+    tgnh_minimize_desc md{};
+    md.tolerance = 10.0; md.dt_start = 1e-4; md.dt_max = 1e-3; md.max_step = 0.01; md.f_inc = 1.1; md.f_dec = 0.5; md.alpha_start = 0.1; md.f_alpha = 0.99; md.n_min = 5;
+    std::vector<uint8_t> mv(N, 1);
+    double* wk = reinterpret_cast<double*>(4096);                                                              // (never dereferenced)
+    tgnh_minimize_state ms{};
+    EXPECT(tgnh_minimize_begin(a, nullptr, wk, nullptr) == TGNH_ERR_ARG && tgnh_minimize_begin(a, &md, nullptr, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_minimize_begin(nullptr, &md, wk, nullptr) == TGNH_ERR_ARG);
+    {
+        tgnh_minimize_desc x = md; x.tolerance = -1;    EXPECT(tgnh_minimize_begin(a, &x, wk, nullptr) == TGNH_ERR_ARG);
+        x = md; x.tolerance = NAN;                      EXPECT(tgnh_minimize_begin(a, &x, wk, nullptr) == TGNH_ERR_ARG);
+        x = md; x.dt_start = 0;                         EXPECT(tgnh_minimize_begin(a, &x, wk, nullptr) == TGNH_ERR_ARG);
+        x = md; x.dt_max = 5e-5;                        EXPECT(tgnh_minimize_begin(a, &x, wk, nullptr) == TGNH_ERR_ARG);
+        x = md; x.max_step = INFINITY;                  EXPECT(tgnh_minimize_begin(a, &x, wk, nullptr) == TGNH_ERR_ARG);
+        x = md; x.f_inc = 0.5;                          EXPECT(tgnh_minimize_begin(a, &x, wk, nullptr) == TGNH_ERR_ARG);
+        x = md; x.f_dec = 1.0;                          EXPECT(tgnh_minimize_begin(a, &x, wk, nullptr) == TGNH_ERR_ARG);
+        x = md; x.f_alpha = 0.0;                        EXPECT(tgnh_minimize_begin(a, &x, wk, nullptr) == TGNH_ERR_ARG);
+        x = md; x.alpha_start = 1.5;                    EXPECT(tgnh_minimize_begin(a, &x, wk, nullptr) == TGNH_ERR_ARG);
+        x = md; x.n_min = -1;                           EXPECT(tgnh_minimize_begin(a, &x, wk, nullptr) == TGNH_ERR_ARG);
+        x = md; x.flags = 2;                            EXPECT(tgnh_minimize_begin(a, &x, wk, nullptr) == TGNH_ERR_ARG);
+        x = md; x.flags = TGNH_MIN_DRUDE_ONLY; x.moving = mv.data();
+        EXPECT(tgnh_minimize_begin(a, &x, wk, nullptr) == TGNH_ERR_STATE);                                         // host-only: nothing launches
+    }
+    EXPECT(tgnh_minimize_begin(a, &md, wk, nullptr) == TGNH_ERR_STATE && tgnh_minimize_iterate(a, nullptr) == TGNH_ERR_STATE);
+    EXPECT(tgnh_minimize_iterate(nullptr, nullptr) == TGNH_ERR_ARG && tgnh_get_minimize_state(a, nullptr, nullptr) == TGNH_ERR_ARG);
+    EXPECT(tgnh_get_minimize_state(a, nullptr, &ms) == TGNH_ERR_STATE && ms.iterations == 0 && ms.converged == 0);
+    EXPECT(tgnh_run_harness_minimize(a, nullptr, 1.0, 1.0, -1, nullptr) == TGNH_ERR_ARG && tgnh_run_harness_minimize(a, nullptr, 1.0, 1.0, 2, nullptr) == TGNH_ERR_STATE);
+    EXPECT(tgnh_minimize_end(a) == TGNH_OK && tgnh_minimize_end(a) == TGNH_OK && tgnh_minimize_end(nullptr) == TGNH_ERR_ARG);
     EXPECT(tgnh_destroy(a) == TGNH_OK && tgnh_destroy(b) == TGNH_OK);
     return 0;
 }

@@ -4,6 +4,7 @@
 #include "../../openmm_drudenose_amd/csrc/tgnh_internal.h"
 #include "../../openmm_drudenose_amd/csrc/tgnh_scale_positions.h"
 #include "../../openmm_drudenose_amd/csrc/tgnh_wrap.h"
+#include "../../openmm_drudenose_amd/csrc/tgnh_minimize.h"
 
 namespace tgnh {
 hipError_t launch_tile(int, int, int, const TileArgs&, int, size_t, hipStream_t) { return hipErrorNoDevice; }
@@ -33,6 +34,9 @@ hipError_t launch_wrap_table(int, const WrapArgs&, hipStream_t) { return hipErro
 hipError_t launch_frame_spans(int, const WrapArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_frame_table(int, const WrapArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_frame_plain(int, const WrapArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_min_sums(const MinArgs&, int, int, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_min_decide(const MinArgs&, int, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_min_update(int, const MinArgs&, int, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_gather_com(int, const GatherArgs&, hipStream_t) { return hipErrorNoDevice; }
 int gather_ke_grid(const GatherArgs&) { return 1; }
 hipError_t launch_gather_ke(int, const GatherArgs&, int, hipStream_t) { return hipErrorNoDevice; }
