@@ -686,7 +686,7 @@ tgnh_status tgnh_get_kinetic_energy(tgnh_handle h, int ke_sum_valid, void* strea
 tgnh_status tgnh_get_num_thermostats(tgnh_handle h, int* count);               /* NT: TGNH G+2 = [groups.., COM, Drude]; DUALNH 3 = [real, unused, Drude] */
 tgnh_status tgnh_get_last_kinetic_energies(tgnh_handle h, void* stream, double* ke);   /* no 1/2; before the chain */
 tgnh_status tgnh_get_last_scale_factors(tgnh_handle h, void* stream, double* scale);
-/* bit0: a Drude beyond 2x the hard wall; bit1: the harness SHAKE did not converge; bit2: a mailbox exchange timed out;
+/* bit0: a Drude beyond 2x the hard wall; bit1: the harness SHAKE did not converge, or the direct solver's result is outside the tolerance; bit2: a mailbox exchange timed out;
  * bit3: the work-groups of a resident step did not all meet; bit4: a kinetic-energy pass that sums its own rows (tail sum) did not
  * receive every row -- the sums were left as NaN -- or a chain was handed a NaN sum (with an all-reduce attached the NaN of one
  * rank's failed pass reaches every rank, and every rank sets the bit itself).  *flags is always filled in.  bit2, bit3, bit4 -- and bit0 in DUALNH mode, where the Reference platform throws
@@ -806,9 +806,49 @@ tgnh_status tgnh_harness_shake_positions(tgnh_handle h, double tol, void* stream
 tgnh_status tgnh_harness_shake_velocities(tgnh_handle h, double tol, void* stream);   /* velocity stage on velm */
 tgnh_status tgnh_harness_set_virtual_sites(tgnh_handle h, int n, const int32_t* atoms, const double* weights);
 tgnh_status tgnh_harness_virtual_sites(tgnh_handle h, void* stream);
-/* nsteps x { begin_kick, SHAKE, begin_move, virtual sites, harness force, end_kick, [TGNH: velocity stage], end_thermo } */
+/* nsteps x { begin_kick, SHAKE, begin_move, virtual sites, harness force, end_kick, [TGNH: velocity stage], end_thermo };
+ * with a table of tgnh_set_constraint_clusters (below), tgnh_apply_constraints behind SHAKE and tgnh_apply_velocity_constraints
+ * behind the velocity stage -- with an empty one, the launches above and no other */
 tgnh_status tgnh_run_harness_constrained(tgnh_handle h, const void* x0, double k_drude, double k_tether,
                                          double tol, int nsteps, void* stream);
+
+/* THE LIBRARY'S OWN CONSTRAINT STAGE, for a host that has no OpenMM behind it (the OpenMM glue keeps calling OpenMM's
+ * applyConstraints / applyVelocityConstraints): every cluster solved directly on the device, one lane per cluster, with no iteration
+ * to convergence.  It stands beside the harness call-outs above and does not replace them.
+ *
+ * tgnh_set_constraint_clusters(n, atoms, dist): clusters in the harness' canonical form -- [n][4] slot indices (-1 = unused) and
+ * [n][6] distances for the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), 0 = unconstrained -- with ONE, TWO OR THREE constraints each:
+ * a rigid three-site water, X-H, X-H2, X-H3.  The inverse masses are taken from the descriptor's masses, never from velm.  The
+ * table replaces the one set before; n = 0 clears it.  The arrays are read before the call returns.  Every check runs before any
+ * device work, so a host-only handle gives the same answers and the same count.  TGNH_ERR_ARG: n < 0 or a NULL array, an index out
+ * of range, an atom listed twice in a cluster or in two clusters (two lanes would write one slot), a constraint whose pair names an
+ * unused atom, a negative or non-finite distance, a cluster without any constraint.  TGNH_ERR_UNSUPPORTED, with the cluster's
+ * number in tgnh_last_error(): more than three constraints in a cluster (leave it to an iterative solver -- the harness' takes
+ * it), a constrained atom without mass.  THE DEGREES OF FREEDOM STAY WITH THE DESCRIPTOR'S CONSTRAINT LIST (num_constraints,
+ * constraint_i / _j): this table changes nothing of tgnh_get_dof.  Not inside a stream capture (the table is uploaded synchronously).
+ * tgnh_get_num_constraint_clusters: the clusters in force.
+ *
+ * With r_k = x(i_k) - x(j_k) the bond vector of constraint k before the move, w the inverse masses and c_kl the sum over the atoms
+ * two constraints share of +-w (w_i + w_j for k = l), everything in fp64 in every precision:
+ * tgnh_apply_constraints(tol): on posDelta, where the reference calls applyConstraints (Cu :363).  Multipliers lambda move atom i_k
+ * by +lambda_k w_i r_k and atom j_k by -lambda_k w_j r_k.  EXACTLY FOUR Newton iterations from lambda = 0 on
+ * sigma_k = |s_k(lambda)|^2 - d_k^2 (s_k: the bond vector after the move, of x + posDelta), each one K x K solve with the Jacobian
+ * 2 (s_k . r_l) c_kl; x is posq (+ posq_correction in mixed precision).  The converged result is SHAKE's converged result.  Four
+ * iterations reach fp64 rounding from displacements of a 1-2 fs step at 300 K drawn without regard to the constraints.
+ * tgnh_apply_velocity_constraints(tol): on velm, where the reference calls applyVelocityConstraints (Cu :391).  Linear: ONE solve of
+ * sum_l (r_k . r_l) c_kl mu_l = r_k . (v_i - v_j), then v_i -= mu_k w_i r_k, v_j += mu_k w_j r_k.  Clears the kinetic energies
+ * carried under TGNH_FLAG_TRUST_STATE_CHANGED, as tgnh_harness_shake_velocities does.
+ * `tol` does not steer the solve; it is the gate on the result, the harness' own: |sigma_k| <= 2 tol d_k^2, and
+ * |r_k . (v_i - v_j)| / r_k^2 <= tol.  A cluster that misses it -- a NaN misses it -- sets status bit 1 (tgnh_get_status_flags), and
+ * its result is stored all the same.  Only x, y, z of the clusters' atoms are written: w of posDelta and velm, every other slot,
+ * posq and posq_correction stay bit for bit.  One launch each on `stream`, none with an empty table (TGNH_OK); neither call
+ * synchronises, both can be captured into a hipGraph.  TGNH_ERR_STATE: a host-only handle, buffers not bound, (positions) no posDelta
+ * bound.  tgnh_run_harness_constrained runs each of the two right after its harness counterpart -- the clusters of the two tables
+ * are the caller's to keep disjoint. */
+tgnh_status tgnh_set_constraint_clusters(tgnh_handle h, int n, const int32_t* atoms /* [n][4], -1 = unused */, const double* dist /* [n][6] */);
+tgnh_status tgnh_get_num_constraint_clusters(tgnh_handle h, int* count);
+tgnh_status tgnh_apply_constraints(tgnh_handle h, double tol, void* stream);            /* on posDelta: where Cu :363 calls out */
+tgnh_status tgnh_apply_velocity_constraints(tgnh_handle h, double tol, void* stream);   /* on velm: where Cu :391 calls out */
 
 /* The call-outs of the reference's own testWater (platforms/reference/tests/TestReferenceDrudeTGNHIntegrator.cpp:111-166),
  * harness only: its force field -- NonbondedForce with reaction field, cutoff `cutoff` in a cubic box of edge `box`, +

@@ -183,6 +183,10 @@ SIGNATURES = {
     "tgnh_harness_set_virtual_sites": (C.c_int, [C.c_void_p, C.c_int, c_i32p, c_f64p]),
     "tgnh_harness_virtual_sites": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tgnh_run_harness_constrained": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    "tgnh_set_constraint_clusters": (C.c_int, [C.c_void_p, C.c_int, c_i32p, c_f64p]),
+    "tgnh_get_num_constraint_clusters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "tgnh_apply_constraints": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "tgnh_apply_velocity_constraints": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "tgnh_harness_water_force": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "tgnh_harness_remove_cm_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tgnh_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),

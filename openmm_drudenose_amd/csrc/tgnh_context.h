@@ -149,6 +149,14 @@ struct tgnh_context {
         tgnh::MinState h_state{};         // what begin uploads, and where tgnh_get_minimize_state's copy lands
         void drop() { active = false; work = nullptr; moving = 0; d_mask.reset(); d_rows.reset(); d_state.reset(); }
     } minim;
+    struct Constraints {              // tgnh_set_constraint_clusters (tgnh_constraints.cpp): the direct solver's cluster table, rows sorted by smallest slot
+        int count = 0;                    // clusters in force (a host-only handle keeps the count and nothing else)
+        tgnh::DeviceBuf<int4> d_atoms;    // [count] uploaded at set time, never inside a capture
+        tgnh::DeviceBuf<double4> d_invmass;   // [count] from the descriptor's masses
+        tgnh::DeviceBuf<double> d_d2;     // [3][count]
+        tgnh::DeviceBuf<uint32_t> d_pairs;    // [count]
+        void drop() { count = 0; d_atoms.reset(); d_invmass.reset(); d_d2.reset(); d_pairs.reset(); }
+    } cons;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block
         std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction

@@ -160,6 +160,23 @@ class DrudeTGNHIntegrator:
         return np.asarray(self._particleTempGroup, np.int32), len(self._tempGroups)
 
 
+MAX_DIRECT_CONSTRAINTS = 3      # constraints per cluster that tgnh_set_constraint_clusters takes (csrc/tgnh_constraints.h)
+
+
+def split_clusters(atoms, dist):
+    """Constraint clusters in the canonical form ([K,4] slot indices, -1 = unused; [K,6] distances, 0 = none) -> (direct, rest), each
+    an (atoms, dist) pair: the clusters of at most three constraints, which the library's direct solver takes
+    (tgnh_set_constraint_clusters), and the others, which stay with the harness' iterative SHAKE.  Every cluster lands on exactly
+    one side, and each side keeps the order it came in.  Pure numpy: no handle, no device."""
+    atoms = np.ascontiguousarray(atoms, np.int32).reshape(-1, 4)
+    dist = np.ascontiguousarray(dist, np.float64).reshape(-1, 6)
+    if len(atoms) != len(dist):
+        raise TgnhError(_lib.ERR_ARG, "split_clusters: one row of distances per cluster")
+    direct = (dist != 0).sum(1) <= MAX_DIRECT_CONSTRAINTS
+    return ((np.ascontiguousarray(atoms[direct]), np.ascontiguousarray(dist[direct])),
+            (np.ascontiguousarray(atoms[~direct]), np.ascontiguousarray(dist[~direct])))
+
+
 def create_handle(lib, system, integrator, group, ngroups, mode, precision, device, flags, kB, padded):
     """tgnh_create from a DrudeSystem + integrator mirror.  device = -1 gives a host-only handle."""
     n = system.num_particles
@@ -272,6 +289,22 @@ class _HandleQueries:
         out = np.zeros(self.n, np.int32)
         _check(self.lib.tgnh_get_molecules(self.h, out.ctypes.data_as(_lib.c_i32p)))
         return out
+
+    # ---- the direct constraint solver's cluster table (include/drude_tgnh.h: tgnh_set_constraint_clusters) ----
+    def set_constraint_clusters(self, atoms, dist):
+        """tgnh_set_constraint_clusters: clusters of one to three constraints in the canonical form; an empty table clears it.  The
+        checks run on a host-only handle too."""
+        atoms = np.ascontiguousarray(atoms, np.int32).reshape(-1, 4)
+        dist = np.ascontiguousarray(dist, np.float64).reshape(-1, 6)
+        if len(atoms) != len(dist):
+            raise TgnhError(_lib.ERR_ARG, "set_constraint_clusters: one row of distances per cluster")
+        _check(self.lib.tgnh_set_constraint_clusters(self.h, len(atoms), atoms.ctypes.data_as(_lib.c_i32p), dist.ctypes.data_as(_lib.c_f64p)))
+
+    def num_constraint_clusters(self):
+        """tgnh_get_num_constraint_clusters: the clusters of the direct solver's table"""
+        n = C.c_int()
+        _check(self.lib.tgnh_get_num_constraint_clusters(self.h, C.byref(n)))
+        return n.value
 
     # ---- the periodic box and the size of a frame (include/drude_tgnh.h: tgnh_set_periodic_box, tgnh_get_frame_count) ----
     def setPeriodicBoxVectors(self, a, b, c):
@@ -428,10 +461,13 @@ class HipContext(_HandleQueries):
     harness force (Drude spring + tether) computed by the library's own kernel.
     cm_motion_removal: None = no centre-of-mass removal inside the step loops, whatever system.has_cm_motion_remover says (that
     flag only takes three degrees of freedom off the thermostats); an integer = tgnh_set_cm_motion_removal(every).
+    direct_constraints: True hands the system's clusters of at most three constraints to the library's direct solver
+    (split_clusters, tgnh_set_constraint_clusters) and only the rest to the harness' SHAKE; False (the default): all to the harness.
     """
 
     def __init__(self, system, integrator, mode="TGNH", precision="mixed", device=0, flags=0, kB=KB,
-                 k_drude=None, k_tether=None, allreduce=None, global_dof_sum=None, lattice_sites=True, cm_motion_removal=None):
+                 k_drude=None, k_tether=None, allreduce=None, global_dof_sum=None, lattice_sites=True, cm_motion_removal=None,
+                 direct_constraints=False):
         import torch
         self.torch = torch
         self.lib = _lib.load()
@@ -490,10 +526,16 @@ class HipContext(_HandleQueries):
         self.ke_sum_valid = False
         self.constrained = False
         self._has_clusters = system.cluster_atoms is not None and len(system.cluster_atoms) > 0
+        self._harness_clusters = 0
         if self._has_clusters:
-            _check(self.lib.tgnh_harness_set_clusters(self.h, len(system.cluster_atoms),
-                                                      system.cluster_atoms.ctypes.data_as(_lib.c_i32p),
-                                                      system.cluster_dist.ctypes.data_as(_lib.c_f64p)))
+            harness = (system.cluster_atoms, system.cluster_dist)
+            if direct_constraints:
+                direct, harness = split_clusters(*harness)
+                self.set_constraint_clusters(*direct)
+            self._harness_clusters = len(harness[0])
+            if self._harness_clusters:
+                _check(self.lib.tgnh_harness_set_clusters(self.h, len(harness[0]), harness[0].ctypes.data_as(_lib.c_i32p),
+                                                          harness[1].ctypes.data_as(_lib.c_f64p)))
             self.constrained = True
         if system.site_atoms is not None and len(system.site_atoms):
             _check(self.lib.tgnh_harness_set_virtual_sites(self.h, len(system.site_atoms),
@@ -912,7 +954,7 @@ class HipContext(_HandleQueries):
         pair centres of mass and ordinary particles at `temperature`, the relative Drude motion at `drudeTemperature` (default:
         the integrator's).  randomSeed=None takes one from os.urandom; the same seed gives the same velocities on any handle,
         path or sharding (self.first_particle places a shard in the whole system).  With constraint clusters set, the harness'
-        velocity-constraint stage runs afterwards, as OpenMM projects after its draw.  removeCMMotion=True takes the net momentum
+        velocity-constraint stage and the direct solver's run afterwards, as OpenMM projects after its draw.  removeCMMotion=True takes the net momentum
         the draw leaves (of order sqrt(N) thermal momenta) off again, after that stage (removeCMMotion()).  exact=True then puts
         every thermostat's kinetic energy onto its N kT at these temperatures, last of all (rescale_to_temperature())."""
         if drudeTemperature is None:
@@ -927,10 +969,28 @@ class HipContext(_HandleQueries):
         self.ke_sum_valid = False
         if self._has_clusters:
             _check(self.lib.tgnh_harness_shake_velocities(self.h, self.integrator.getConstraintTolerance(), self._stream()))
+            _check(self.lib.tgnh_apply_velocity_constraints(self.h, self.integrator.getConstraintTolerance(), self._stream()))
         if removeCMMotion:
             self.removeCMMotion()
         if exact:
             self.rescale_to_temperature(temperature, drudeTemperature)
+
+    @property
+    def constraint_clusters(self):
+        """(direct, harness): the clusters in the direct solver's table and in the harness' SHAKE table"""
+        return self.num_constraint_clusters(), self._harness_clusters
+
+    def apply_constraints(self, tol=None):
+        """tgnh_apply_constraints: the direct solver on posDelta, for the clusters of its table (tol=None: the integrator's
+        constraint tolerance; it gates the result, status bit 1, and does not steer the solve).  No synchronisation."""
+        tol = self.integrator.getConstraintTolerance() if tol is None else float(tol)
+        _check(self.lib.tgnh_apply_constraints(self.h, tol, self._stream()))
+
+    def apply_velocity_constraints(self, tol=None):
+        """tgnh_apply_velocity_constraints: the direct solver's velocity stage on velm (one linear solve per cluster)."""
+        tol = self.integrator.getConstraintTolerance() if tol is None else float(tol)
+        _check(self.lib.tgnh_apply_velocity_constraints(self.h, tol, self._stream()))
+        self.ke_sum_valid = False
 
     def setCharges(self, q):
         """posq.w of every slot (OpenMM keeps the charge there; setPositions leaves it alone).  No step kernel reads it."""
@@ -1003,12 +1063,14 @@ class HipContext(_HandleQueries):
             tol = self.integrator.getConstraintTolerance()
             _check(lib.tgnh_step_begin_kick(h, self._stream()))          # Cu :336-360
             _check(lib.tgnh_harness_shake_positions(h, tol, self._stream()))   # Cu :363
+            _check(lib.tgnh_apply_constraints(h, tol, self._stream()))         # ... the direct solver's clusters
             _check(lib.tgnh_step_begin_move(h, self._stream()))          # Cu :366-376
             _check(lib.tgnh_harness_virtual_sites(h, self._stream()))    # Cu :377
             self.compute_forces()                                        # Cu :380
             _check(lib.tgnh_step_end_kick(h, self._stream()))            # Cu :384-388
             if self.mode == MODE_TGNH:
                 _check(lib.tgnh_harness_shake_velocities(h, tol, self._stream()))   # Cu :391
+                _check(lib.tgnh_apply_velocity_constraints(h, tol, self._stream()))
             _check(lib.tgnh_step_end_thermo(h, self._stream()))          # Cu :394-406
             self.ke_sum_valid = True
 
@@ -1105,7 +1167,7 @@ class HipContext(_HandleQueries):
         return bits.value
 
     def status_flags(self):
-        """The device's status word (bit 0 Drude beyond 2x the hard wall, bit 1 harness SHAKE not converged, bit 2 mailbox
+        """The device's status word (bit 0 Drude beyond 2x the hard wall, bit 1 harness SHAKE not converged or the direct solver's result outside the tolerance, bit 2 mailbox
         exchange timed out), whether or not it spells a failure.  Synchronises the stream."""
         flags = C.c_uint32()
         self.lib.tgnh_get_status_flags(self.h, self._stream(), C.byref(flags))
