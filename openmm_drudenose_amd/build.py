@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdrudetgnh_hip.so")
-SOURCES = ["tgnh_topology.cpp", "tgnh_lifecycle.cpp", "tgnh_exchange.cpp", "tgnh_step.cpp", "tgnh_queries.cpp", "tgnh_harness_host.cpp", "tgnh_positions.cpp",
+SOURCES = ["tgnh_topology.cpp", "tgnh_lifecycle.cpp", "tgnh_exchange.cpp", "tgnh_step.cpp", "tgnh_velocities.cpp", "tgnh_queries.cpp", "tgnh_harness_host.cpp", "tgnh_positions.cpp",
            "tgnh_frames.cpp", "tgnh_minimize.cpp", "tgnh_constraints.cpp",
            "tgnh_kernels.hip", "tgnh_gather.hip", "tgnh_harness.hip", "tgnh_velinit.hip", "tgnh_drude_stats.hip", "tgnh_cm_motion.hip",
            "tgnh_rescale.hip", "tgnh_scale_positions.hip", "tgnh_wrap.hip", "tgnh_minimize.hip", "tgnh_constraints.hip"]

@@ -8,49 +8,35 @@
 // sharded run -- the caller's all-reduce adds the ranks' four sums in place.  Nothing here knows tiles, pairs or molecules; the two
 // instantiations are the two types velm has: float4 (single precision) and double4 (mixed, double).
 //
-// Same bits from any handle over the same slots: the grid is a function of the slot count alone (cm_grid), a thread adds its
-// slots in ascending index order, a wavefront adds its lanes with wave_sum (fixed order), a work-group its wavefronts in wavefront
-// order through LDS, and cm_momentum_sum_kernel -- one work-group -- the rows in an order that depends on their number only.
-// No floating-point atomic anywhere; the count of massive slots goes through an integer LDS atomic (a count does not depend on the
-// order).  The shift forms v_cm = P / M in every thread from the same two operands: the same bits everywhere, and on every rank
-// that was handed the same sums.
+// Same bits from any handle over the same slots: the sums are added in the fixed order of tgnh_rows_device.h, the rows by
+// cm_momentum_sum_kernel, one work-group.  The count of massive slots goes through an integer LDS atomic (a count does not depend
+// on the order).  The shift forms v_cm = P / M in every thread from the same two operands: the same bits everywhere, and on every
+// rank that was handed the same sums.
 //
 // A unit of its own so that the step kernels' units compile to what they compiled to before.
-#include "tgnh_device_math.h"
+#include "tgnh_rows_device.h"
 
 namespace tgnh {
 
 // every product and sum below is rounded on its own, as the header writes them (no fused multiply-add: a test restates them in numpy)
 #pragma clang fp contract(off)
 
-static_assert(BLOCK % 64 == 0 && BLOCK >= 4, "whole wavefronts; one thread per sum");
-
 template <typename V4> struct Component;
 template <> struct Component<float4> { typedef float type; };
 template <> struct Component<double4> { typedef double type; };
 
 struct CmLds {
-    double wsum[BLOCK / 64][4];
+    Sum4Lds sum;
     unsigned long long massive;
 };
 
-// a thread's four sums and its count -> the work-group's row.  Every thread of the work-group calls this, outside any divergent
-// branch (wave_sum reads all 64 lanes); l.massive was cleared, and a barrier passed, before the first thread gets here.
+// a thread's four sums and its count -> the work-group's row.  Called as sum4_put is, l.massive cleared and a barrier passed before.
 __device__ __forceinline__ void cm_block_row(CmLds& l, double s0, double s1, double s2, double s3, const unsigned long long count,
                                              CmRow* __restrict__ row) {
-    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
-    if ((threadIdx.x & 63) == 0) {
-        double* w = l.wsum[threadIdx.x >> 6];
-        w[0] = s0; w[1] = s1; w[2] = s2; w[3] = s3;
-    }
+    sum4_put(l.sum, s0, s1, s2, s3);
     if (count) atomicAdd(&l.massive, count);
     __syncthreads();
-    if (threadIdx.x < 4) {
-        double s = l.wsum[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < BLOCK / 64; w++) s += l.wsum[w][threadIdx.x];      // wavefront order
-        (threadIdx.x == 0 ? row->mass : row->p[threadIdx.x - 1]) = s;
-    }
+    if (threadIdx.x < 4) (threadIdx.x == 0 ? row->mass : row->p[threadIdx.x - 1]) = sum4_total(l.sum);
     if (threadIdx.x == 0) row->massive = (long long)l.massive;
 }
 
@@ -74,14 +60,13 @@ __global__ __launch_bounds__(BLOCK) void cm_momentum_kernel(const V4* __restrict
     cm_block_row(l, sm, px, py, pz, massive, rows + blockIdx.x);
 }
 
-// rows [0, nrows) -> *out.  One work-group: thread t adds the run of consecutive rows [t c, (t + 1) c), c = ceil(nrows / BLOCK), in
-// row order; the threads' sums then meet as a work-group's do in the pass.
+// rows [0, nrows) -> *out.  One work-group, a thread its chunk of the rows (row_chunk).
 __global__ __launch_bounds__(BLOCK) void cm_momentum_sum_kernel(const CmRow* __restrict__ rows, const int nrows, CmRow* __restrict__ out) {
     __shared__ CmLds l;
     if (threadIdx.x == 0) l.massive = 0ull;
     __syncthreads();
-    const int chunk = (nrows + BLOCK - 1) / BLOCK;
-    const int r0 = min((int)threadIdx.x * chunk, nrows), r1 = min(r0 + chunk, nrows);
+    int r0, r1;
+    row_chunk(nrows, r0, r1);
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     unsigned long long massive = 0;
     for (int r = r0; r < r1; r++) {
@@ -113,7 +98,7 @@ __global__ __launch_bounds__(BLOCK) void cm_shift_kernel(V4* __restrict__ velm, 
 }
 
 hipError_t launch_cm_momentum(int precision, const void* velm, int n, CmRow* rows, int grid, hipStream_t s) {
-    if (n < 1 || grid < 1 || grid > CM_GRID_CAP || !velm || !rows) return hipErrorInvalidValue;
+    if (n < 1 || grid < 1 || grid > INDEX_GRID_CAP || !velm || !rows) return hipErrorInvalidValue;
     switch (precision) {
         case TGNH_PREC_SINGLE: TGNH_LAUNCH(cm_momentum_kernel<float4>, grid, BLOCK, 0, s, static_cast<const float4*>(velm), n, rows); break;
         case TGNH_PREC_MIXED:
@@ -127,7 +112,7 @@ hipError_t launch_cm_momentum(int precision, const void* velm, int n, CmRow* row
 }
 
 hipError_t launch_cm_shift(int precision, void* velm, int n, const double* sums, const double* dv, int grid, hipStream_t s) {
-    if (n < 1 || grid < 1 || grid > CM_GRID_CAP || !velm || (!sums && !dv)) return hipErrorInvalidValue;
+    if (n < 1 || grid < 1 || grid > INDEX_GRID_CAP || !velm || (!sums && !dv)) return hipErrorInvalidValue;
     const double dx = sums ? 0.0 : dv[0], dy = sums ? 0.0 : dv[1], dz = sums ? 0.0 : dv[2];
     switch (precision) {
         case TGNH_PREC_SINGLE: TGNH_LAUNCH(cm_shift_kernel<float4>, grid, BLOCK, 0, s, static_cast<float4*>(velm), n, sums, dx, dy, dz); break;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "tgnh_internal.h"
+#include "tgnh_by_index.h"
 #include "tgnh_minimize.h"
 
 void tgnh_set_error(const std::string& msg);   // sets what tgnh_last_error() returns (tgnh_lifecycle.cpp)
@@ -42,6 +43,15 @@ public:
     operator T*() const { return p_; }
 };
 typedef DeviceBuf<unsigned char> DeviceBytes;   // what the kernels read as real4 / mixed4 of the handle's precision
+
+// The rows of a pass by global index (tgnh_by_index.h): allocated once, at the first call that launches or at the setter that announces launches to come
+template <typename Row> struct __attribute__((visibility("hidden"))) RowScratch {
+    DeviceBuf<Row> d_rows;            // [rows_allocated]: a row per work-group of the pass, then the result
+    int rows_allocated = 0;
+    Row h_row{};                      // where the result lands on the host
+    // the rows of a pass of `grid` work-groups (zero: cleared when they are allocated); too_small: what to say when grid exceeds them
+    tgnh_status ensure(int grid, bool zero, const char* too_small);      // (tgnh_host.h)
+};
 }  // namespace tgnh
 
 // Every DeviceBuf below is the handle's own.  Raw pointers are somebody else's memory: the caller's bound arrays (Bound), the
@@ -86,15 +96,8 @@ struct tgnh_context {
     struct ByIndex {                  // the passes by global index on a tiled handle (the velocity draw, the Drude statistics): the gather
         tgnh::DeviceBuf<int> d_partner;   // path's partner table, built by whichever of them is called first (device_partner_table)
     } by_index;
-    struct DrudeStats {               // tgnh_get_drude_statistics: allocated at its first call
-        tgnh::DeviceBuf<tgnh::DrudeStatsRow> d_rows;   // [rows_allocated]: a row per work-group of the pass, then the result
-        int rows_allocated = 0;
-        tgnh::DrudeStatsRow h_row{};      // where the result lands on the host
-    } dstats;
-    struct CmMotion {                 // tgnh_get_momentum / tgnh_shift_velocities / tgnh_remove_cm_motion: allocated at the first call that launches
-        tgnh::DeviceBuf<tgnh::CmRow> d_rows;           // (or at tgnh_set_cm_motion_removal: never inside somebody's stream capture)
-        int rows_allocated = 0;           // [rows_allocated]: a row per work-group of the pass, then the result
-        tgnh::CmRow h_row{};              // where the result lands on the host
+    tgnh::RowScratch<tgnh::DrudeStatsRow> dstats;      // tgnh_get_drude_statistics
+    struct CmMotion : tgnh::RowScratch<tgnh::CmRow> {  // tgnh_get_momentum / tgnh_remove_cm_motion, tgnh_set_cm_motion_removal (tgnh_velocities.cpp)
         int every = 0;                    // tgnh_set_cm_motion_removal: remove before every step whose number is a multiple of this (0: never)
     } cmm;
     struct Rescale {                  // tgnh_scale_velocities / tgnh_rescale_to_temperature: allocated at the first call that launches
@@ -144,7 +147,7 @@ struct tgnh_context {
         double* work = nullptr;           // the caller's [3 N] doubles: the minimiser's velocity
         int64_t moving = 0;               // this handle's moving slots
         tgnh::DeviceBuf<unsigned char> d_mask;     // [N] non-zero: the slot moves
-        tgnh::DeviceBuf<double> d_rows;   // [cm_grid(N) + 1][4]: a row per work-group of the sums pass, then the four sums an all-reduce adds in place
+        tgnh::DeviceBuf<double> d_rows;   // [index_grid(N) + 1][4]: a row per work-group of the sums pass, then the four sums an all-reduce adds in place
         tgnh::DeviceBuf<tgnh::MinState> d_state;
         tgnh::MinState h_state{};         // what begin uploads, and where tgnh_get_minimize_state's copy lands
         void drop() { active = false; work = nullptr; moving = 0; d_mask.reset(); d_rows.reset(); d_state.reset(); }

@@ -6,15 +6,13 @@
 // (partner | is-Drude << 31, -1: in no pair) and only a Drude lane goes on -- it loads its own posq (and the correction in mixed
 // precision) and its parent's.  Nothing is written but one row per work-group.
 //
-// Same bits from any handle over the same slots: the grid is a function of the slot count alone (drude_stats_grid), a thread adds
-// its pairs in index order, a wavefront adds its lanes with wave_sum (fixed order), a work-group its wavefronts in wavefront
-// order through LDS, and drude_stats_sum_kernel -- one work-group -- the rows in an order that depends on their number only.
-// No floating-point atomic anywhere.  What is counted (bins, pairs beyond the threshold, pairs) goes through integer LDS
+// Same bits from any handle over the same slots: the sums are added in the fixed order of tgnh_rows_device.h, the rows by
+// drude_stats_sum_kernel, one work-group.  What is counted (bins, pairs beyond the threshold, pairs) goes through integer LDS
 // atomics: a count does not depend on the order.  The maximum travels as the bit pattern of d2 -- for non-negative doubles it
 // orders as an unsigned 64-bit integer does -- with the slot index beside it; ties go to the lowest index.
 //
 // A unit of its own so that the step kernels' units compile to what they compiled to before.
-#include "tgnh_device_math.h"
+#include "tgnh_rows_device.h"
 
 namespace tgnh {
 
@@ -24,11 +22,11 @@ namespace tgnh {
 constexpr int HB = TGNH_DRUDE_HIST_BINS;
 constexpr int NCOUNT = HB + 3;                  // the row's counts: HB + 1 bins, over, pairs
 constexpr int NO_PAIR = 0x7fffffff;             // index beside a maximum nobody has bid for yet
-static_assert(NCOUNT <= BLOCK && BLOCK % 64 == 0, "one thread per count");
+static_assert(NCOUNT <= BLOCK, "one thread per count");
 
 // what a work-group of either kernel keeps in LDS: CNT = 32-bit counts in the pass (widened in the row), 64-bit where rows are added
 template <typename CNT> struct StatsLds {
-    double wsum[BLOCK / 64][4];
+    Sum4Lds sum;
     unsigned long long key;
     int idx;
     CNT count[NCOUNT];
@@ -41,25 +39,16 @@ template <typename CNT> __device__ __forceinline__ void stats_lds_clear(StatsLds
 }
 
 // a thread's sums, its maximum (idx == NO_PAIR: it has none) -> the work-group's row; the counts are in l.count already.
-// Every thread of the work-group calls this, outside any divergent branch (wave_sum reads all 64 lanes).
+// Called as sum4_put is.
 template <typename CNT>
 __device__ __forceinline__ void stats_block_row(StatsLds<CNT>& l, double s0, double s1, double s2, double s3,
                                                 const unsigned long long key, const int idx, DrudeStatsRow* __restrict__ row) {
-    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
-    if ((threadIdx.x & 63) == 0) {
-        double* w = l.wsum[threadIdx.x >> 6];
-        w[0] = s0; w[1] = s1; w[2] = s2; w[3] = s3;
-    }
+    sum4_put(l.sum, s0, s1, s2, s3);
     if (idx != NO_PAIR) atomicMax(&l.key, key);
     __syncthreads();
     if (idx != NO_PAIR && key == l.key) atomicMin(&l.idx, idx);        // ties: the lowest index
     __syncthreads();
-    if (threadIdx.x < 4) {
-        double s = l.wsum[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < BLOCK / 64; w++) s += l.wsum[w][threadIdx.x];      // wavefront order
-        (threadIdx.x == 0 ? row->sum_d2 : row->dipole[threadIdx.x - 1]) = s;
-    }
+    if (threadIdx.x < 4) (threadIdx.x == 0 ? row->sum_d2 : row->dipole[threadIdx.x - 1]) = sum4_total(l.sum);
     if (threadIdx.x < HB + 1) row->hist[threadIdx.x] = (long long)l.count[threadIdx.x];
     if (threadIdx.x == HB + 1) row->over = (long long)l.count[HB + 1];
     if (threadIdx.x == HB + 2) row->pairs = (long long)l.count[HB + 2];
@@ -115,13 +104,12 @@ __global__ __launch_bounds__(BLOCK) void drude_stats_kernel(const typename Prec<
     stats_block_row(l, s_d2, px, py, pz, best, best_i, rows + blockIdx.x);
 }
 
-// rows [0, nrows) -> *out.  One work-group: thread t adds the run of consecutive rows [t c, (t + 1) c), c = ceil(nrows / BLOCK), in
-// row order; the threads' sums then meet as a work-group's do in the pass.
+// rows [0, nrows) -> *out.  One work-group, a thread its chunk of the rows (row_chunk).
 __global__ __launch_bounds__(BLOCK) void drude_stats_sum_kernel(const DrudeStatsRow* __restrict__ rows, const int nrows, DrudeStatsRow* __restrict__ out) {
     __shared__ StatsLds<unsigned long long> l;
     stats_lds_clear(l);
-    const int chunk = (nrows + BLOCK - 1) / BLOCK;
-    const int r0 = min((int)threadIdx.x * chunk, nrows), r1 = min(r0 + chunk, nrows);
+    int r0, r1;
+    row_chunk(nrows, r0, r1);
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     unsigned long long best = 0ull;
     int best_i = NO_PAIR;
@@ -141,7 +129,7 @@ __global__ __launch_bounds__(BLOCK) void drude_stats_sum_kernel(const DrudeStats
 
 hipError_t launch_drude_stats(int precision, const void* posq, const void* posq_corr, const int* partner, int n, double threshold,
                               double hist_max, DrudeStatsRow* rows, int grid, hipStream_t s) {
-    if (n < 1 || grid < 1 || grid > DRUDE_STATS_GRID_CAP) return hipErrorInvalidValue;
+    if (n < 1 || grid < 1 || grid > INDEX_GRID_CAP) return hipErrorInvalidValue;
     const double thr2 = threshold * threshold;
     const float4* corr = static_cast<const float4*>(posq_corr);
     switch (precision) {

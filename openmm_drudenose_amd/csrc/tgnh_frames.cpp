@@ -36,11 +36,6 @@ static void box_args(const tgnh_context* c, WrapArgs& a) {
     a.box[0] = box.a[0]; a.box[1] = box.b[0]; a.box[2] = box.b[1]; a.box[3] = box.c[0]; a.box[4] = box.c[1]; a.box[5] = box.c[2];
 }
 
-static bool capturing(hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-}
-
 // the molecule table's part of the launch arguments, after molecules_device and molecules_launch_bounds
 static void table_args(const tgnh_context* c, WrapArgs& a) {
     const tgnh_context::Molecules& m = c->mol;
@@ -125,7 +120,7 @@ extern "C" tgnh_status tgnh_write_frame(tgnh_handle h, const tgnh_frame_desc* de
     if (wrap && !h->box.set) return fail(TGNH_ERR_STATE, "tgnh_write_frame: TGNH_FRAME_WRAP without a periodic box (tgnh_set_periodic_box)");
     tgnh_status rc = entry(h, true); if (rc) return rc;           // (buffers bound, not a host-only handle, no failure seen before)
     hipStream_t s = (hipStream_t)stream;
-    const bool cap = capturing(s);
+    const bool cap = stream_capturing(s);
     if (!cap) {                                                   // where the runtime knows the allocation behind out, it must hold `capacity` floats
         hipDeviceptr_t base = nullptr; size_t size = 0;
         if (hipMemGetAddressRange(&base, &size, out) != hipSuccess) (void)hipGetLastError();      // (mapped by other means: the caller's word is taken)

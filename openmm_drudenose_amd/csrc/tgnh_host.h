@@ -1,5 +1,5 @@
 // tgnh_host.h -- what the host units behind the C ABI (include/drude_tgnh.h) share: tgnh_topology.cpp, tgnh_lifecycle.cpp,
-// tgnh_exchange.cpp, tgnh_step.cpp, tgnh_queries.cpp, tgnh_positions.cpp, tgnh_frames.cpp, tgnh_minimize.cpp, tgnh_constraints.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
+// tgnh_exchange.cpp, tgnh_step.cpp, tgnh_velocities.cpp, tgnh_queries.cpp, tgnh_positions.cpp, tgnh_frames.cpp, tgnh_minimize.cpp, tgnh_constraints.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
 // live in tgnh_kernels.hip (tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h), tgnh_gather.hip, tgnh_velinit.hip,
 // tgnh_drude_stats.hip, tgnh_cm_motion.hip, tgnh_rescale.hip, tgnh_scale_positions.hip, tgnh_wrap.hip, tgnh_minimize.hip, tgnh_constraints.hip and tgnh_harness.hip.
 //
@@ -50,8 +50,13 @@ tgnh_status deferred_guard(tgnh_handle h, const char* what);
 // tgnh_step.cpp
 void note_status(tgnh_handle h, uint32_t flags);
 tgnh_status entry(tgnh_handle h, bool need_bufs);
+bool stream_capturing(hipStream_t s);                          // a stream capture is recording s: nothing synchronous may be done on it
+tgnh_status finish_query(tgnh_handle h, hipStream_t s);        // a query's tail: the status word behind what it enqueued, wait, the sticky failure
+tgnh_status allreduce_doubles(tgnh_handle h, double* device_ptr, int count, hipStream_t s);   // the hook on these sums, in place (TGNH_OK: none is set)
 bool resident_now(tgnh_handle h);
-tgnh_status allreduce_hook(tgnh_handle h, hipStream_t s);      // the hook, if one is set, on the summed kinetic energies
+tgnh_status allreduce_hook(tgnh_handle h, hipStream_t s);      // ... on the summed kinetic energies
+bool big_com_on(tgnh_handle h);
+tgnh_status run_big_com(tgnh_handle h, bool kick, hipStream_t s);
 tgnh_status run_tile(tgnh_handle h, int ops, int kid, hipStream_t s, const double* scale = nullptr);
 GatherArgs gather_args(tgnh_handle h, const double* scale);
 ChainArgs chain_args(tgnh_handle h);
@@ -61,8 +66,8 @@ tgnh_status settle_kick(tgnh_handle h, hipStream_t s);
 tgnh_status settle_end(tgnh_handle h, hipStream_t s);
 tgnh_status flush_impl(tgnh_handle h, hipStream_t s);
 tgnh_status ke_query_launches(tgnh_handle h, hipStream_t s);    // tgnh_queries.cpp: what tgnh_compute_kinetic_energies enqueues behind its entry checks
-tgnh_status cm_scratch(tgnh_handle h);                                          // the rows of the momentum pass, allocated once
-tgnh_status cm_momentum_launches(tgnh_handle h, hipStream_t s, CmRow** result);   // pass + row sum of the bound velm -> *result (device)
+tgnh_status cm_removal_due(tgnh_handle h, hipStream_t s);      // tgnh_velocities.cpp: tgnh_set_cm_motion_removal's launches where this step is due; a step begins with this
+tgnh_status rescale_due(tgnh_handle h, hipStream_t s);         // ... and then with tgnh_set_velocity_rescaling's
 // tgnh_positions.cpp
 tgnh_status molecules_ensure(tgnh_context* c, const char* what);              // the table in force: the caller's, or the default resolved now (TGNH_ERR_STATE: no resid)
 tgnh_status molecules_launch_bounds(const tgnh_context* c);                   // what the launches over the table are bound by, against what the tables hold
@@ -85,6 +90,14 @@ struct Timed {
     }
     ~Timed() { if (ev) (void)hipEventRecord(ev->b, s); }
 };
+template <typename Row> tgnh_status tgnh::RowScratch<Row>::ensure(int grid, bool zero, const char* too_small) {
+    if (!d_rows) {
+        HIP_OK(d_rows.alloc((size_t)grid + 1, zero));
+        rows_allocated = grid + 1;
+    }
+    if (grid < 1 || grid > INDEX_GRID_CAP || grid + 1 > rows_allocated) return fail(TGNH_ERR_STATE, too_small);
+    return TGNH_OK;
+}
 #pragma GCC visibility pop
 
 #endif

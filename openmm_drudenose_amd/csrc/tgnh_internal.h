@@ -338,34 +338,6 @@ constexpr int PLAIN_KE_PARTS = 2048;         // work-group partials of the plain
 hipError_t launch_plain_ke(int precision, const void* velm, const long long* force, int n, int padded,
                            double time_shift, double* out /*[1 + PLAIN_KE_PARTS] device: out[0] = the result*/, hipStream_t s);
 size_t tile_lds_bytes(int precision, int ops, bool hardwall, bool use_com);
-// the velocity draw (tgnh_velinit.hip): velm [n] mixed4, partner [n] as GatherArgs::partner, kT / kTD = kB T / kB T_D
-hipError_t launch_velinit(int precision, void* velm, const int* partner, int n, double kT, double kTD,
-                          unsigned long long seed, long long first_particle, hipStream_t s);
-// Drude pair statistics (tgnh_drude_stats.hip): a read-only pass by global index over posq (+ posq_corr) and the partner table,
-// one row per work-group, then one work-group that adds the rows into rows[grid].  The grid is a function of n alone.
-constexpr int DRUDE_STATS_GRID_CAP = 1024;   // work-groups (= rows) of the pass: beyond 1024 x BLOCK = 262 144 slots its threads take the grid-stride loop again
-struct DrudeStatsRow {
-    double sum_d2, dipole[3];
-    unsigned long long max_key;              // bit pattern of the largest d2 (orders as the double does: d2 >= 0)
-    long long over, pairs;
-    int worst, pad;                          // slot of the Drude particle of that pair; 0x7fffffff: the row saw no pair
-    long long hist[TGNH_DRUDE_HIST_BINS + 1];
-};
-inline int drude_stats_grid(int n) { const long long g = ((long long)n + BLOCK - 1) / BLOCK; return (int)(g < DRUDE_STATS_GRID_CAP ? g : DRUDE_STATS_GRID_CAP); }
-hipError_t launch_drude_stats(int precision, const void* posq, const void* posq_corr, const int* partner, int n, double threshold,
-                              double hist_max, DrudeStatsRow* rows /*[grid + 1]: the work-groups' rows, then the result*/, int grid, hipStream_t s);
-// Centre-of-mass motion (tgnh_cm_motion.hip): a read-only pass by global index over velm, one row per work-group, then one work-group
-// that adds the rows into rows[grid]; and the pass that subtracts P / M -- read from `sums` = {M, Px, Py, Pz} on the device, where an
-// all-reduce may have added the other ranks' in between -- or the explicit dv[3] (host; sums == nullptr) from every massive slot.
-// The grid is a function of n alone, by drude_stats_grid's rule.
-constexpr int CM_GRID_CAP = 1024;
-struct CmRow {
-    double mass, p[3];                       // (the four doubles an all-reduce sums in place: contiguous, first)
-    long long massive;                       // slots with w != 0
-};
-inline int cm_grid(int n) { const long long g = ((long long)n + BLOCK - 1) / BLOCK; return (int)(g < CM_GRID_CAP ? g : CM_GRID_CAP); }
-hipError_t launch_cm_momentum(int precision, const void* velm, int n, CmRow* rows /*[grid + 1]: the work-groups' rows, then the result*/, int grid, hipStream_t s);
-hipError_t launch_cm_shift(int precision, void* velm, int n, const double* sums, const double* dv, int grid, hipStream_t s);
 
 }  // namespace tgnh
 

@@ -48,8 +48,7 @@ extern "C" tgnh_status tgnh_minimize_begin(tgnh_handle h, const tgnh_minimize_de
     if (!h->bound.posq || !h->bound.force) return fail(TGNH_ERR_STATE, "tgnh_minimize_begin: positions or forces are not bound");
     rc = refusals(h, "tgnh_minimize_begin"); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    if (stream_capturing(s))
         return fail(TGNH_ERR_STATE, "tgnh_minimize_begin: the stream is capturing (begin uploads the mask and the state block: call it outside the "
                                     "capture and record tgnh_minimize_iterate)");
     const int N = h->d.num_particles;
@@ -66,7 +65,7 @@ extern "C" tgnh_status tgnh_minimize_begin(tgnh_handle h, const tgnh_minimize_de
     if (moving == 0) return fail(TGNH_ERR_STATE, "tgnh_minimize_begin: no slot moves (every slot is massless, masked out, or no Drude particle)");
     tgnh_context::Minimize& m = h->minim;
     m.drop();                                                     // (a begin without an end: the earlier minimisation's buffers go)
-    const int grid = cm_grid(N);
+    const int grid = index_grid(N);
     HIP_OK(m.d_mask.alloc((size_t)N));
     HIP_OK(m.d_rows.alloc(4 * ((size_t)grid + 1)));               // (every row is written by the pass before anybody reads it)
     HIP_OK(m.d_state.alloc(1));
@@ -92,12 +91,12 @@ extern "C" tgnh_status tgnh_minimize_iterate(tgnh_handle h, void* stream) {
         return fail(TGNH_ERR_STATE, "internal: the minimiser's buffers are not all there");
     hipStream_t s = (hipStream_t)stream;
     const MinArgs a = min_args(h);
-    const int grid = cm_grid(a.n);
+    const int grid = index_grid(a.n);
     const bool hook = h->xchg.allreduce != nullptr;
     Timed t(h, s, KID_OTHER);
     HIP_OK(launch_min_sums(a, grid, hook ? 0 : 1, s));
     if (hook) {                                                   // {P, FF, VV, moving} of every rank, added in place, in one call
-        if (h->xchg.allreduce(a.rows + 4 * (size_t)grid, 4, (void*)s, h->xchg.allreduce_user) != 0) return fail(TGNH_ERR_HIP, "all-reduce hook failed");
+        rc = allreduce_doubles(h, a.rows + 4 * (size_t)grid, 4, s); if (rc) return rc;
         HIP_OK(launch_min_decide(a, grid, s));
     }
     HIP_OK(launch_min_update(h->d.precision, a, grid, s));

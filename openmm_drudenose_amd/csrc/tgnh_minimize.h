@@ -3,7 +3,7 @@
 #ifndef TGNH_MINIMIZE_H_
 #define TGNH_MINIMIZE_H_
 
-#include "tgnh_internal.h"
+#include "tgnh_by_index.h"
 
 namespace tgnh {
 

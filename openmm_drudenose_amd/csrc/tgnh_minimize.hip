@@ -7,42 +7,29 @@
 // positions and `work`.  Between them one work-group adds the rows and one thread takes the decision -- in one launch, or, in a
 // sharded run, in two with the caller's all-reduce of the four sums between them.  Nothing here knows tiles, pairs or molecules.
 //
-// Same bits from any handle over the same slots: the grid is cm_grid's, a function of the slot count alone; a thread adds its
-// slots in ascending index order, a wavefront its lanes with wave_sum, a work-group its wavefronts in wavefront order through
-// LDS, the one work-group the rows by cm_momentum_sum_kernel's chunk rule.  No floating-point atomic; the count of moving slots
-// is a sum of 1.0s (exact below 2^53).
+// Same bits from any handle over the same slots: the sums are added in the fixed order of tgnh_rows_device.h, the rows by
+// min_rowsum_kernel, one work-group.  The count of moving slots is a sum of 1.0s (exact below 2^53).
 //
 // A unit of its own so that the step kernels' units compile to what they compiled to before.
 #include "tgnh_molecule_device.h"
 #include "tgnh_minimize.h"
+#include "tgnh_rows_device.h"
 
 namespace tgnh {
 
 // every product, quotient and sum below is rounded on its own, as the header writes them (no fused multiply-add: a test restates them in numpy)
 #pragma clang fp contract(off)
 
-static_assert(BLOCK % 64 == 0 && BLOCK >= 4, "whole wavefronts; one thread per sum");
-
 struct MinLds {
-    double wsum[BLOCK / 64][4];
+    Sum4Lds sum;
     double total[4];
 };
 
-// a thread's four sums -> l.total, the work-group's.  Every thread of the work-group calls this, outside any divergent branch
-// (wave_sum reads all 64 lanes); a barrier has passed when it returns.
+// a thread's four sums -> l.total, the work-group's.  Called as sum4_put is; a barrier has passed when it returns.
 __device__ __forceinline__ void min_block_sums(MinLds& l, double s0, double s1, double s2, double s3) {
-    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
-    if ((threadIdx.x & 63) == 0) {
-        double* w = l.wsum[threadIdx.x >> 6];
-        w[0] = s0; w[1] = s1; w[2] = s2; w[3] = s3;
-    }
+    sum4_put(l.sum, s0, s1, s2, s3);
     __syncthreads();
-    if (threadIdx.x < 4) {
-        double s = l.wsum[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < BLOCK / 64; w++) s += l.wsum[w][threadIdx.x];      // wavefront order
-        l.total[threadIdx.x] = s;
-    }
+    if (threadIdx.x < 4) l.total[threadIdx.x] = sum4_total(l.sum);
     __syncthreads();
 }
 
@@ -98,13 +85,12 @@ __device__ __forceinline__ void min_decide(const double* __restrict__ sums, MinS
     st->dt = dt; st->alpha = alpha; st->a = aa; st->b = bb;
 }
 
-// rows [0, nrows) -> rows[nrows], the four sums.  One work-group: thread t adds the run of consecutive rows [t c, (t + 1) c),
-// c = ceil(nrows / BLOCK), in row order; the threads' sums then meet as a work-group's do in the pass.  decide != 0: thread 0 goes on
-// to the decision (no all-reduce stands between the two).
+// rows [0, nrows) -> rows[nrows], the four sums.  One work-group, a thread its chunk of the rows (row_chunk).  decide != 0: thread 0
+// goes on to the decision (no all-reduce stands between the two).
 __global__ __launch_bounds__(BLOCK) void min_rowsum_kernel(const MinArgs a, const int nrows, const int decide) {
     __shared__ MinLds l;
-    const int chunk = (nrows + BLOCK - 1) / BLOCK;
-    const int r0 = min((int)threadIdx.x * chunk, nrows), r1 = min(r0 + chunk, nrows);
+    int r0, r1;
+    row_chunk(nrows, r0, r1);
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     for (int r = r0; r < r1; r++) {
         const double* w = a.rows + 4ll * r;
@@ -147,7 +133,7 @@ __global__ __launch_bounds__(BLOCK) void min_update_kernel(const MinArgs a) {
 }
 
 static bool min_args_ok(const MinArgs& a, const int grid) {
-    return a.n >= 1 && a.padded >= a.n && grid >= 1 && grid <= CM_GRID_CAP && a.force && a.work && a.mask && a.rows && a.state;
+    return a.n >= 1 && a.padded >= a.n && grid >= 1 && grid <= INDEX_GRID_CAP && a.force && a.work && a.mask && a.rows && a.state;
 }
 
 hipError_t launch_min_sums(const MinArgs& a, int grid, int decide, hipStream_t s) {

@@ -94,20 +94,12 @@ tgnh_status molecules_ensure(tgnh_context* c, const char* what) {
     return molecules_build(c, c->topo.resid.data(), what);
 }
 
-static tgnh_status capturing(hipStream_t s, bool* yes) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    *yes = s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-    return TGNH_OK;
-}
-
 // device copies of the tables the launches read, made once per table (never inside a stream capture: the uploads are synchronous)
 tgnh_status molecules_device(tgnh_context* c, hipStream_t s) {
     tgnh_context::Molecules& m = c->mol;
     if (m.on_device) return TGNH_OK;
     const tgnh_context::Molecules::Table& t = m.t;
-    bool cap = false;
-    capturing(s, &cap);
-    if (cap) return fail(TGNH_ERR_STATE, "tgnh_scale_positions: the molecule tables are not on the device yet and the stream is capturing "
+    if (stream_capturing(s)) return fail(TGNH_ERR_STATE, "tgnh_scale_positions: the molecule tables are not on the device yet and the stream is capturing "
                                          "(call tgnh_set_molecules or tgnh_scale_positions once outside the capture)");
     if (t.spans) {
         // (once per table, not per call: every span a wavefront's, its first lane a molecule's head)

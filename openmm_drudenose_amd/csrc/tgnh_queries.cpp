@@ -7,11 +7,7 @@ static tgnh_status read_state(tgnh_handle h, int off, int n, hipStream_t s, doub
     { tgnh_status rc = entry(h, false); if (rc) return rc; }
     { tgnh_status rc = materialize_chain(h, s); if (rc) return rc; }
     HIP_OK(hipMemcpyAsync(out, h->thermo.d_state + off, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(h->status.h_seen, h->status.d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    note_status(h, *h->status.h_seen);       // what was just read may come from a failed exchange: say so now
-    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);
-    return TGNH_OK;
+    return finish_query(h, s);
 }
 
 extern "C" tgnh_status tgnh_get_kinetic_energy(tgnh_handle h, int ke_sum_valid, void* stream, double* out) {
@@ -48,12 +44,9 @@ extern "C" tgnh_status tgnh_get_status_flags(tgnh_handle h, void* stream, uint32
     if (!flags) return fail(TGNH_ERR_ARG, "null flags");
     if (h->host_only) { *flags = 0; return TGNH_OK; }
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(hipMemcpyAsync(h->status.h_seen, h->status.d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
-    *flags = *h->status.h_seen;              // always handed back, also beside an error code
-    note_status(h, *flags);
-    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);
-    return TGNH_OK;
+    const tgnh_status rc = finish_query(h, (hipStream_t)stream);
+    if (rc != TGNH_ERR_HIP) *flags = *h->status.h_seen;      // handed back also beside a failure the device reported
+    return rc;
 }
 extern "C" tgnh_status tgnh_get_time(tgnh_handle h, double* time, int64_t* step_count) {
     CHECK_H(h);
@@ -197,13 +190,8 @@ extern "C" tgnh_status tgnh_get_drude_statistics(tgnh_handle h, double threshold
     r = DrudeStatsRow{};
     r.worst = 0x7fffffff;
     if (h->d.num_pairs > 0) {
-        const int grid = drude_stats_grid(h->d.num_particles);
-        if (!h->dstats.d_rows) {
-            HIP_OK(h->dstats.d_rows.alloc((size_t)grid + 1, true));
-            h->dstats.rows_allocated = grid + 1;
-        }
-        if (grid < 1 || grid > DRUDE_STATS_GRID_CAP || grid + 1 > h->dstats.rows_allocated)
-            return fail(TGNH_ERR_STATE, "internal: the Drude statistics' grid exceeds its rows");
+        const int grid = index_grid(h->d.num_particles);
+        rc = h->dstats.ensure(grid, true, "internal: the Drude statistics' grid exceeds its rows"); if (rc) return rc;
         if (h->d.precision == TGNH_PREC_MIXED && !h->bound.posq_corr) return fail(TGNH_ERR_STATE, "internal: mixed precision without a position correction");
         const int* partner = nullptr;
         rc = device_partner_table(h, &partner); if (rc) return rc;
@@ -214,10 +202,7 @@ extern "C" tgnh_status tgnh_get_drude_statistics(tgnh_handle h, double threshold
         }
         HIP_OK(hipMemcpyAsync(&r, h->dstats.d_rows + grid, sizeof(r), hipMemcpyDeviceToHost, s));
     }
-    HIP_OK(hipMemcpyAsync(h->status.h_seen, h->status.d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    note_status(h, *h->status.h_seen);
-    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);
+    rc = finish_query(h, s); if (rc) return rc;
     double max_d2;
     std::memcpy(&max_d2, &r.max_key, sizeof(max_d2));
     out->worst_particle = r.worst == 0x7fffffff ? -1 : r.worst;
@@ -226,37 +211,6 @@ extern "C" tgnh_status tgnh_get_drude_statistics(tgnh_handle h, double threshold
     out->sum_d2 = r.sum_d2;
     std::copy(r.dipole, r.dipole + 3, out->dipole);
     std::copy(r.hist, r.hist + TGNH_DRUDE_HIST_BINS + 1, out->hist);
-    return TGNH_OK;
-}
-
-// Total mass and momentum of this handle's slots (include/drude_tgnh.h has the contract; tgnh_cm_motion.hip the kernels).  A query
-// of the velocities, so what a step has left owed to velm is applied first, as tgnh_get_kinetic_energy does; the sweep direction is
-// left as it was found.
-extern "C" tgnh_status tgnh_get_momentum(tgnh_handle h, void* stream, tgnh_momentum* out) {
-    CHECK_H(h);
-    if (!out) return fail(TGNH_ERR_ARG, "null out");
-    if (out->struct_size != sizeof(tgnh_momentum)) return fail(TGNH_ERR_ARG, "tgnh_momentum size mismatch (ABI)");
-    tgnh_status rc = entry(h, true); if (rc) return rc;          // (buffers bound, not a host-only handle, no failure seen before)
-    hipStream_t s = (hipStream_t)stream;
-    const int dir = h->run.sweep_reverse;
-    rc = flush_impl(h, s);
-    h->run.sweep_reverse = dir;
-    if (rc) return rc;
-    CmRow& r = h->cmm.h_row;                                     // (the handle's: a copy still in flight when an error returns lands in live memory)
-    r = CmRow{};
-    CmRow* sums = nullptr;
-    {
-        Timed t(h, s, KID_OTHER);
-        rc = cm_momentum_launches(h, s, &sums); if (rc) return rc;
-    }
-    HIP_OK(hipMemcpyAsync(&r, sums, sizeof(r), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(h->status.h_seen, h->status.d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    note_status(h, *h->status.h_seen);
-    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);
-    out->reserved = 0;
-    out->massive = r.massive; out->mass = r.mass;
-    std::copy(r.p, r.p + 3, out->momentum);
     return TGNH_OK;
 }
 

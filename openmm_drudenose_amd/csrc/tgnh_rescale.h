@@ -1,5 +1,5 @@
 // tgnh_rescale.h -- the launchers of tgnh_rescale.hip, for the host code of tgnh_scale_velocities / tgnh_rescale_to_temperature
-// (tgnh_step.cpp).  A header of its own, not lines of tgnh_internal.h: no header the step kernels' unit reads changes with this feature.
+// (tgnh_velocities.cpp).  A header of its own, not lines of tgnh_internal.h: no header the step kernels' unit reads changes with this feature.
 #ifndef TGNH_RESCALE_H_
 #define TGNH_RESCALE_H_
 

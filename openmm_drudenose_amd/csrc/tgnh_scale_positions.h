@@ -3,14 +3,13 @@
 #ifndef TGNH_SCALE_POSITIONS_H_
 #define TGNH_SCALE_POSITIONS_H_
 
-#include "tgnh_internal.h"
+#include "tgnh_by_index.h"
 
 namespace tgnh {
 
 constexpr int SP_SPAN_SLOTS = 64;            // a span: whole molecules, consecutive slots, one wavefront
 constexpr int SP_WAVES = BLOCK / 64;         // spans (fast path) or molecules (table path) per work-group
-constexpr int SP_GRID_CAP = 1024;            // work-groups of the table path's per-slot pass: a grid-stride loop beyond
-inline int sp_slot_grid(int n) { const long long g = ((long long)n + BLOCK - 1) / BLOCK; return (int)(g < SP_GRID_CAP ? g : SP_GRID_CAP); }
+// (the table path's per-slot pass: index_grid work-groups, tgnh_by_index.h)
 inline int sp_wave_grid(int waves) { return (int)(((long long)waves + SP_WAVES - 1) / SP_WAVES); }
 
 struct ScalePosArgs {

@@ -103,7 +103,7 @@ hipError_t launch_scale_positions_table(int precision, const ScalePosArgs& a, hi
     TGNH_LAUNCH_PREC(sp_shift_kernel, precision, dim3(sp_wave_grid(a.num_molecules)), dim3(BLOCK), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    TGNH_LAUNCH_PREC(sp_apply_kernel, precision, dim3(sp_slot_grid(a.n)), dim3(BLOCK), 0, s, a);
+    TGNH_LAUNCH_PREC(sp_apply_kernel, precision, dim3(index_grid(a.n)), dim3(BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

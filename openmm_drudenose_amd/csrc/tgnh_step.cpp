@@ -1,4 +1,4 @@
-// tgnh_step.cpp -- step orchestration (A11): device-reported failures, the launch decisions by name, launch sizing, run_tile / run_gather / run_chain / run_resident, centre-of-mass removal, velocity rescaling, tgnh_step_*, flush, clock
+// tgnh_step.cpp -- step orchestration (A11): device-reported failures, the launch decisions by name, launch sizing, run_tile / run_gather / run_chain / run_resident, tgnh_step_*, flush, clock
 #include "tgnh_host.h"
 
 // ---------------------------------------------------------------------------
@@ -35,9 +35,22 @@ void note_status(tgnh_handle h, uint32_t flags) {
     }
 }
 
+tgnh_status finish_query(tgnh_handle h, hipStream_t s) {
+    HIP_OK(hipMemcpyAsync(h->status.h_seen, h->status.d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    note_status(h, *h->status.h_seen);       // what was just read may come from a failed exchange: say so now
+    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);
+    return TGNH_OK;
+}
+
 // ---------------------------------------------------------------------------
 // launches
 // ---------------------------------------------------------------------------
+bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
 static tgnh_status need_buffers(tgnh_handle h) {
     if (h->host_only) return fail(TGNH_ERR_STATE, "host-only handle (device -1): no GPU work can be launched on it");
     if (!h->bound.velm) return fail(TGNH_ERR_STATE, "tgnh_bind_buffers has not been called");
@@ -55,12 +68,13 @@ static bool rescale_sums_rows(tgnh_handle h, int rows) {
 // recomputes while its peers carry over would enter a collective alone)
 static bool ke_carries(tgnh_handle h) { return h->cfg.carry_ok && !h->xchg.allreduce && !h->xchg.on; }
 // molecules longer than a tile whose centre-of-mass velocities the rescale launches read from a table (run_big_com)
-static bool big_com_on(tgnh_handle h) { return h->topo.num_big && com_thermostat_on(h->d); }
-tgnh_status allreduce_hook(tgnh_handle h, hipStream_t s) {
-    if (h->xchg.allreduce && h->xchg.allreduce(h->thermo.d_state + h->thermo.L.off_ke_red, h->thermo.L.NT, (void*)s, h->xchg.allreduce_user) != 0)
+bool big_com_on(tgnh_handle h) { return h->topo.num_big && com_thermostat_on(h->d); }
+tgnh_status allreduce_doubles(tgnh_handle h, double* device_ptr, int count, hipStream_t s) {
+    if (h->xchg.allreduce && h->xchg.allreduce(device_ptr, count, (void*)s, h->xchg.allreduce_user) != 0)
         return fail(TGNH_ERR_HIP, "all-reduce hook failed");
     return TGNH_OK;
 }
+tgnh_status allreduce_hook(tgnh_handle h, hipStream_t s) { return allreduce_doubles(h, h->thermo.d_state + h->thermo.L.off_ke_red, h->thermo.L.NT, s); }
 static tgnh_status timed_chain(tgnh_handle h, const ChainArgs& a, hipStream_t s) { Timed t(h, s, KID_CHAIN); HIP_OK(launch_chain(a, s)); return TGNH_OK; }
 
 // the fields TileArgs and GatherArgs share by name
@@ -164,7 +178,7 @@ extern "C" tgnh_status tgnh_get_launch_bounds(tgnh_handle h, int32_t out[8]) {
     return TGNH_OK;
 }
 
-static tgnh_status run_big_com(tgnh_handle h, bool kick, hipStream_t s) {
+tgnh_status run_big_com(tgnh_handle h, bool kick, hipStream_t s) {
     BigComArgs b{};
     b.table = h->topo.d_big_table; b.n = h->topo.num_big; b.velm = h->bound.velm;
     b.force = reinterpret_cast<const long long*>(h->bound.force); b.padded = h->d.padded_num_particles;
@@ -488,8 +502,7 @@ tgnh_status entry(tgnh_handle h, bool need_bufs) {
 // looked at on a later entry): a caller that never asks for anything still learns of a failure within that many steps.
 static tgnh_status poll_status_async(tgnh_handle h, hipStream_t s) {
     if (!h->status.h_seen || h->run.step_count % STATUS_POLL_EVERY != 0) return TGNH_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (s != nullptr && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return TGNH_OK;
+    if (stream_capturing(s)) return TGNH_OK;
     HIP_OK(hipMemcpyAsync(h->status.h_seen, h->status.d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     return TGNH_OK;
 }
@@ -507,197 +520,6 @@ static void start_of_step(tgnh_handle h) {
 static tgnh_status advance_clock(tgnh_handle h, hipStream_t s) {
     h->run.time += h->d.step_size; h->run.step_count += 1;
     return poll_status_async(h, s);
-}
-
-// ---------------------------------------------------------------------------
-// centre-of-mass motion (include/drude_tgnh.h has the contract; tgnh_cm_motion.hip the kernels)
-// ---------------------------------------------------------------------------
-tgnh_status cm_scratch(tgnh_handle h) {
-    const int grid = cm_grid(h->d.num_particles);
-    if (!h->cmm.d_rows) {
-        HIP_OK(h->cmm.d_rows.alloc((size_t)grid + 1));           // (every row is written by the pass before anybody reads it)
-        h->cmm.rows_allocated = grid + 1;
-    }
-    if (grid < 1 || grid > CM_GRID_CAP || grid + 1 > h->cmm.rows_allocated)
-        return fail(TGNH_ERR_STATE, "internal: the momentum pass's grid exceeds its rows");
-    return TGNH_OK;
-}
-
-tgnh_status cm_momentum_launches(tgnh_handle h, hipStream_t s, CmRow** result) {
-    tgnh_status rc = cm_scratch(h); if (rc) return rc;
-    const int grid = cm_grid(h->d.num_particles);
-    HIP_OK(launch_cm_momentum(h->d.precision, h->bound.velm, h->d.num_particles, h->cmm.d_rows, grid, s));
-    *result = h->cmm.d_rows + grid;
-    return TGNH_OK;
-}
-
-// momentum pass, row sum, the ranks' four sums added in place where an all-reduce is set (a caller's hook or the library's own
-// RCCL, which is installed as that hook), shift.  Nothing here waits for the device.  The caller has seen to tgnh_state_changed.
-static tgnh_status cm_removal_launches(tgnh_handle h, hipStream_t s) {
-    if (h->xchg.on) return fail(TGNH_ERR_UNSUPPORTED, "centre-of-mass removal with a mailbox exchange attached: the mailboxes carry the kinetic-energy sums only "
-                                                      "(tgnh_get_momentum on every rank, add the sums, tgnh_shift_velocities with the same dv everywhere)");
-    CmRow* sums = nullptr;
-    Timed t(h, s, KID_OTHER);
-    tgnh_status rc = cm_momentum_launches(h, s, &sums); if (rc) return rc;
-    if (h->xchg.allreduce && h->xchg.allreduce(&sums->mass, 4, (void*)s, h->xchg.allreduce_user) != 0)
-        return fail(TGNH_ERR_HIP, "all-reduce hook failed");
-    HIP_OK(launch_cm_shift(h->d.precision, h->bound.velm, h->d.num_particles, &sums->mass, nullptr, cm_grid(h->d.num_particles), s));
-    return TGNH_OK;
-}
-
-// tgnh_set_cm_motion_removal: before the step whose number is a multiple of `every`, and before that step's own first launch.
-// Such a handle never lags (the setter refuses DEFER_SCALE), so tgnh_state_changed's effect is all there is to do.
-static tgnh_status cm_removal_due(tgnh_handle h, hipStream_t s) {
-    if (h->cmm.every <= 0 || h->run.step_count % h->cmm.every != 0) return TGNH_OK;
-    h->owed.ke_carry = false;
-    return cm_removal_launches(h, s);
-}
-
-extern "C" tgnh_status tgnh_remove_cm_motion(tgnh_handle h, void* stream) {
-    tgnh_status rc = entry(h, true); if (rc) return rc;           // (buffers bound, not a host-only handle, no failure seen before)
-    rc = tgnh_state_changed(h); if (rc) return rc;              // (first: refused between the steps of a deferred sequence, and then nothing is written)
-    return cm_removal_launches(h, (hipStream_t)stream);
-}
-
-extern "C" tgnh_status tgnh_shift_velocities(tgnh_handle h, const double dv[3], void* stream) {
-    CHECK_H(h);
-    if (!dv) return fail(TGNH_ERR_ARG, "tgnh_shift_velocities: null dv");
-    if (!std::isfinite(dv[0]) || !std::isfinite(dv[1]) || !std::isfinite(dv[2])) return fail(TGNH_ERR_ARG, "tgnh_shift_velocities: dv is not finite");
-    tgnh_status rc = entry(h, true); if (rc) return rc;
-    rc = tgnh_state_changed(h); if (rc) return rc;
-    Timed t(h, (hipStream_t)stream, KID_OTHER);
-    HIP_OK(launch_cm_shift(h->d.precision, h->bound.velm, h->d.num_particles, nullptr, dv, cm_grid(h->d.num_particles), (hipStream_t)stream));
-    return TGNH_OK;
-}
-
-extern "C" tgnh_status tgnh_set_cm_motion_removal(tgnh_handle h, int every) {
-    CHECK_H(h);
-    if (every < 0) return fail(TGNH_ERR_ARG, "tgnh_set_cm_motion_removal: negative interval");
-    if (every > 0) {
-        if (h->d.flags & TGNH_FLAG_DEFER_SCALE)
-            return fail(TGNH_ERR_UNSUPPORTED, "tgnh_set_cm_motion_removal: velocities lag between the steps of a TGNH_FLAG_DEFER_SCALE handle");
-        if (h->xchg.on) return fail(TGNH_ERR_UNSUPPORTED, "tgnh_set_cm_motion_removal: a mailbox exchange is attached (it carries the kinetic-energy sums only)");
-        if (!h->host_only) {                                    // the scratch now: the first removal may be enqueued inside a stream capture
-            HIP_OK(hipSetDevice(h->device));
-            tgnh_status rc = cm_scratch(h); if (rc) return rc;
-        }
-    }
-    h->cmm.every = every;
-    return TGNH_OK;
-}
-
-// ---------------------------------------------------------------------------
-// velocity rescaling (include/drude_tgnh.h has the contract; tgnh_rescale.hip the two small kernels; the rescale is run_tile's)
-// ---------------------------------------------------------------------------
-static tgnh_status rescale_scratch(tgnh_handle h) {
-    if (!h->resc.d_buf) HIP_OK(h->resc.d_buf.alloc(2 * (size_t)h->thermo.L.NT, true));
-    return TGNH_OK;
-}
-static double* rescale_factors(tgnh_handle h) { return h->resc.d_buf; }
-static double* rescale_targets(tgnh_handle h) { return h->resc.d_buf + h->thermo.L.NT; }
-
-// A6 with the factors in the scratch: the step's own rescale launch, told where its factors lie (so no chain is adopted and the
-// thermostat block is neither read nor written).  Molecules longer than a tile: the launch reads their centre-of-mass velocities
-// from a table -- of the velocities as they are (table_fresh: the kinetic-energy pass just before has left it) -- and the table is
-// made again of what the launch stored, as flush_impl does.  The gather path computes its own table inside run_gather unless a
-// kinetic-energy pass has left it since entry().  The sweep direction is left as it was found.
-static tgnh_status rescale_apply(tgnh_handle h, hipStream_t s, bool table_fresh) {
-    const int dir = h->run.sweep_reverse;
-    tgnh_status rc = big_com_on(h) && !table_fresh ? run_big_com(h, false, s) : TGNH_OK;
-    if (!rc) rc = run_tile(h, OP_SCALE, KID_SCALE, s, rescale_factors(h));
-    if (!rc && big_com_on(h)) rc = run_big_com(h, false, s);
-    h->run.sweep_reverse = dir;
-    if (!rc) h->resc.applied = true;
-    return rc;
-}
-
-static tgnh_status rescale_mailbox_refusal() {
-    return fail(TGNH_ERR_UNSUPPORTED, "velocity rescaling to a temperature with a mailbox exchange attached: the mailboxes carry the step's own kinetic-energy sums only "
-                                      "(tgnh_compute_kinetic_energies on every rank, form the factors, tgnh_scale_velocities with the same factors everywhere)");
-}
-
-// the kinetic-energy pass, its row sum [+ all-reduce], the factors, A6.  Nothing here waits for the device.  The caller has seen
-// to tgnh_state_changed (so nothing is owed to velm, and no chain waits for a rescale launch: materialize_chain commits a staged
-// block at the most) and to the scratch.
-static tgnh_status rescale_to_temperature_launches(tgnh_handle h, double temperature, double drude_temperature, hipStream_t s) {
-    if (h->xchg.on) return rescale_mailbox_refusal();
-    const ChainLayout& L = h->thermo.L;
-    std::vector<double> target = thermostat_nkt(h, h->d.kB * temperature, h->d.kB * drude_temperature);
-    for (int k = 0; k < L.NT; k++) if (h->thermo.dof[k] == 0.0) target[k] = RESCALE_INERT;     // (N kT = 0 at any temperature)
-    HIP_OK(launch_rescale_put(rescale_targets(h), target.data(), L.NT, s));
-    const int dir = h->run.sweep_reverse;
-    tgnh_status rc = ke_query_launches(h, s);
-    h->run.sweep_reverse = dir;
-    if (rc) return rc;
-    {
-        Timed t(h, s, KID_OTHER);
-        HIP_OK(launch_rescale_factors(h->thermo.d_state + L.off_ke_red, rescale_targets(h), L.NT, rescale_factors(h), h->status.d_word, s));
-    }
-    return rescale_apply(h, s, true);
-}
-
-// tgnh_set_velocity_rescaling: placed as cm_removal_due is, and after it
-static tgnh_status rescale_due(tgnh_handle h, hipStream_t s) {
-    if (h->resc.every <= 0 || h->run.step_count % h->resc.every != 0) return TGNH_OK;
-    h->owed.ke_carry = false;
-    return rescale_to_temperature_launches(h, h->resc.temperature, h->resc.drude_temperature, s);
-}
-
-extern "C" tgnh_status tgnh_scale_velocities(tgnh_handle h, const double* factors, int count, void* stream) {
-    CHECK_H(h);
-    const int NT = h->thermo.L.NT;
-    if (!factors) return fail(TGNH_ERR_ARG, "tgnh_scale_velocities: null factors");
-    if (count != NT) return fail(TGNH_ERR_ARG, "tgnh_scale_velocities: count is not the number of thermostats (tgnh_get_num_thermostats)");
-    std::vector<double> f(factors, factors + NT);
-    if (h->d.mode == TGNH_MODE_DUALNH) f[1] = 1.0;              // (dualNH's unused entry: whatever it holds)
-    for (double v : f) if (!(v >= 0) || !std::isfinite(v)) return fail(TGNH_ERR_ARG, "tgnh_scale_velocities: a factor is negative or not finite");
-    tgnh_status rc = entry(h, true); if (rc) return rc;           // (buffers bound, not a host-only handle, no failure seen before)
-    rc = tgnh_state_changed(h); if (rc) return rc;              // (first: refused between the steps of a deferred sequence, and then nothing is written)
-    hipStream_t s = (hipStream_t)stream;
-    rc = rescale_scratch(h); if (rc) return rc;
-    HIP_OK(launch_rescale_put(rescale_factors(h), f.data(), NT, s));    // (by value, with the launch: the caller's array is free again)
-    return rescale_apply(h, s, false);
-}
-
-extern "C" tgnh_status tgnh_rescale_to_temperature(tgnh_handle h, double temperature, double drude_temperature, void* stream) {
-    CHECK_H(h);
-    tgnh_status rc = check_temperatures(temperature, drude_temperature); if (rc) return rc;
-    rc = entry(h, true); if (rc) return rc;
-    if (h->xchg.on) return rescale_mailbox_refusal();           // (before anything of the handle changes)
-    rc = tgnh_state_changed(h); if (rc) return rc;
-    rc = rescale_scratch(h); if (rc) return rc;
-    return rescale_to_temperature_launches(h, temperature, drude_temperature, (hipStream_t)stream);
-}
-
-extern "C" tgnh_status tgnh_get_rescale_factors(tgnh_handle h, void* stream, double* factors) {
-    CHECK_H(h);
-    if (!factors) return fail(TGNH_ERR_ARG, "null out");
-    tgnh_status rc = entry(h, true); if (rc) return rc;
-    if (!h->resc.applied) return fail(TGNH_ERR_STATE, "tgnh_get_rescale_factors: neither tgnh_scale_velocities nor tgnh_rescale_to_temperature has run on this handle");
-    hipStream_t s = (hipStream_t)stream;
-    HIP_OK(hipMemcpyAsync(factors, rescale_factors(h), sizeof(double) * h->thermo.L.NT, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(h->status.h_seen, h->status.d_word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    note_status(h, *h->status.h_seen);
-    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);
-    return TGNH_OK;
-}
-
-extern "C" tgnh_status tgnh_set_velocity_rescaling(tgnh_handle h, int every, double temperature, double drude_temperature) {
-    CHECK_H(h);
-    if (every < 0) return fail(TGNH_ERR_ARG, "tgnh_set_velocity_rescaling: negative interval");
-    tgnh_status rc = check_temperatures(temperature, drude_temperature); if (rc) return rc;
-    if (every > 0) {
-        if (h->d.flags & TGNH_FLAG_DEFER_SCALE)
-            return fail(TGNH_ERR_UNSUPPORTED, "tgnh_set_velocity_rescaling: velocities lag between the steps of a TGNH_FLAG_DEFER_SCALE handle");
-        if (h->xchg.on) return fail(TGNH_ERR_UNSUPPORTED, "tgnh_set_velocity_rescaling: a mailbox exchange is attached (it carries the step's own kinetic-energy sums only)");
-        if (!h->host_only) {                                    // the scratch now: the first rescale may be enqueued inside a stream capture
-            HIP_OK(hipSetDevice(h->device));
-            rc = rescale_scratch(h); if (rc) return rc;
-        }
-    }
-    h->resc.every = every; h->resc.temperature = temperature; h->resc.drude_temperature = drude_temperature;
-    return TGNH_OK;
 }
 
 extern "C" tgnh_status tgnh_step_begin(tgnh_handle h, void* stream) {
@@ -864,22 +686,5 @@ extern "C" tgnh_status tgnh_state_changed(tgnh_handle h) {
     tgnh_status rc = deferred_guard(h, "tgnh_state_changed");
     if (rc) return rc;
     h->owed.ke_carry = false;              // TRUST_STATE_CHANGED: the next thermostat half step sums the kinetic energies again (Cu :474-488)
-    return TGNH_OK;
-}
-
-// Context::setVelocitiesToTemperature (include/drude_tgnh.h has the contract; tgnh_velinit.hip the kernel).  A setVelocities:
-// tgnh_state_changed's refusal and its effect come first, then one launch by global index whatever path the handle steps on.
-extern "C" tgnh_status tgnh_set_velocities_to_temperature(tgnh_handle h, double temperature, double drude_temperature,
-                                                          uint64_t seed, int64_t first_particle, void* stream) {
-    CHECK_H(h);
-    tgnh_status rc = check_temperatures(temperature, drude_temperature); if (rc) return rc;
-    if (first_particle < 0) return fail(TGNH_ERR_ARG, "tgnh_set_velocities_to_temperature: negative first_particle");
-    rc = entry(h, true); if (rc) return rc;                     // (buffers bound, not a host-only handle)
-    rc = tgnh_state_changed(h); if (rc) return rc;
-    const int* partner = nullptr;
-    rc = device_partner_table(h, &partner); if (rc) return rc;
-    Timed t(h, (hipStream_t)stream, KID_OTHER);
-    HIP_OK(launch_velinit(h->d.precision, h->bound.velm, partner, h->d.num_particles, h->d.kB * temperature, h->d.kB * drude_temperature,
-                          (unsigned long long)seed, (long long)first_particle, (hipStream_t)stream));
     return TGNH_OK;
 }

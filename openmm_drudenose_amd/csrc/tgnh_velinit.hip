@@ -12,7 +12,7 @@
 // A unit of its own so that the step kernels' units compile to what they compiled to before.
 #include <algorithm>
 
-#include "tgnh_internal.h"
+#include "tgnh_by_index.h"
 
 namespace tgnh {
 

@@ -181,7 +181,7 @@ hipError_t launch_wrap_table(int precision, const WrapArgs& a, hipStream_t s) {
     TGNH_LAUNCH_PREC(wr_shift_kernel, precision, dim3(sp_wave_grid(a.num_molecules)), dim3(BLOCK), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    TGNH_LAUNCH_PREC(wr_apply_kernel, precision, dim3(sp_slot_grid(a.n)), dim3(BLOCK), 0, s, a);
+    TGNH_LAUNCH_PREC(wr_apply_kernel, precision, dim3(index_grid(a.n)), dim3(BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
@@ -196,13 +196,13 @@ hipError_t launch_frame_table(int precision, const WrapArgs& a, hipStream_t s) {
     TGNH_LAUNCH_PREC(wr_shift_kernel, precision, dim3(sp_wave_grid(a.num_molecules)), dim3(BLOCK), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    TGNH_LAUNCH_PREC(fr_apply_kernel, precision, dim3(sp_slot_grid(a.n)), dim3(BLOCK), 0, s, a);
+    TGNH_LAUNCH_PREC(fr_apply_kernel, precision, dim3(index_grid(a.n)), dim3(BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_frame_plain(int precision, const WrapArgs& a, hipStream_t s) {
     if (!wr_args_ok(precision, a) || !wr_frame_ok(a) || (a.skip_drude && !a.out_index)) return hipErrorInvalidValue;
-    TGNH_LAUNCH_PREC(fr_plain_kernel, precision, dim3(sp_slot_grid(a.n)), dim3(BLOCK), 0, s, a);
+    TGNH_LAUNCH_PREC(fr_plain_kernel, precision, dim3(index_grid(a.n)), dim3(BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

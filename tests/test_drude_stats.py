@@ -101,7 +101,7 @@ def gpu_cases():
             "nacl": (synth.nacl, ("double", "mixed", "single")),
             "water216": (lambda: synth.water_box(216), ("double", "mixed", "single")),
             "drudes-at-the-end": (lambda: drudes_at_the_end(300), ("mixed",)),
-            # DRUDE_STATS_GRID_CAP x work-group size = 1024 x 256 = 262 144 slots in one trip of the grid-stride loop: 262 500 slots,
+            # INDEX_GRID_CAP x work-group size = 1024 x 256 = 262 144 slots in one trip of the grid-stride loop: 262 500 slots,
             # so the first 356 threads make two
             "water52500": (lambda: synth.water_box(52_500), ("mixed",))}
 
