@@ -808,7 +808,8 @@ tgnh_status tgnh_harness_set_virtual_sites(tgnh_handle h, int n, const int32_t* 
 tgnh_status tgnh_harness_virtual_sites(tgnh_handle h, void* stream);
 /* nsteps x { begin_kick, SHAKE, begin_move, virtual sites, harness force, end_kick, [TGNH: velocity stage], end_thermo };
  * with a table of tgnh_set_constraint_clusters (below), tgnh_apply_constraints behind SHAKE and tgnh_apply_velocity_constraints
- * behind the velocity stage -- with an empty one, the launches above and no other */
+ * behind the velocity stage -- with an empty one, the launches above and no other; with a table of tgnh_set_virtual_sites
+ * (further below), tgnh_compute_virtual_sites behind the harness' virtual sites -- with an empty one, the launches above and no other */
 tgnh_status tgnh_run_harness_constrained(tgnh_handle h, const void* x0, double k_drude, double k_tether,
                                          double tol, int nsteps, void* stream);
 
@@ -849,6 +850,55 @@ tgnh_status tgnh_set_constraint_clusters(tgnh_handle h, int n, const int32_t* at
 tgnh_status tgnh_get_num_constraint_clusters(tgnh_handle h, int* count);
 tgnh_status tgnh_apply_constraints(tgnh_handle h, double tol, void* stream);            /* on posDelta: where Cu :363 calls out */
 tgnh_status tgnh_apply_velocity_constraints(tgnh_handle h, double tol, void* stream);   /* on velm: where Cu :391 calls out */
+
+/* THE LIBRARY'S OWN VIRTUAL-SITE STAGE, for a host that has no OpenMM behind it (the OpenMM glue keeps calling OpenMM's
+ * computeVirtualSites): sites placed from their parents, and the forces that land on sites spread back over the parents, on the
+ * device.  It stands beside the harness call-out above (three-particle averages, no way back for forces) and does not replace it.
+ *
+ * tgnh_set_virtual_sites(n, kind, atoms, params): kind[n] one of TGNH_SITE_*; atoms [n][4] = (site, p1, p2, p3) slots of the bound
+ * arrays, p3 = -1 for a two-particle site (where it is not looked at); params [n][TGNH_SITE_PARAMS], of which a kind reads the first
+ * 2, 3, 3 or 12.  With x1, x2, x3 the parents' positions and r1k = xk - x1, OpenMM's four kinds:
+ *   TGNH_SITE_TWO_AVERAGE        w1, w2                       w1 x1 + w2 x2
+ *   TGNH_SITE_THREE_AVERAGE      w1, w2, w3                   (w1 x1 + w2 x2) + w3 x3
+ *   TGNH_SITE_OUT_OF_PLANE       w12, w13, wc                 x1 + w12 r12 + w13 r13 + wc (r12 x r13)
+ *   TGNH_SITE_LOCAL_COORDINATES  wo[3], wx[3], wy[3], p[3]    o + p.x X + p.y Y + p.z Z, with o = sum wo x, X = normalise(sum wx x),
+ *                                                             Z = normalise((sum wx x) x (sum wy x)), Y = Z x X
+ * The table replaces the one set before; n = 0 clears it.  The arrays are read before the call returns; the rows may come in any
+ * order.  Every check runs before any device work, so a host-only handle gives the same answers and the same count.  TGNH_ERR_ARG:
+ * n < 0 or a NULL array, an unknown kind, an index out of range, a slot listed as a site twice, a parent repeated within a site, a
+ * parent that is itself a site, p3 = -1 for a kind that needs three parents, a parameter (of those the kind reads) that is not
+ * finite, local-coordinates weights with |sum wo - 1|, |sum wx| or |sum wy| above 1e-6 (OpenMM's own gate).  TGNH_ERR_UNSUPPORTED,
+ * with the site's number in tgnh_last_error(): a site whose mass in the descriptor is not zero, a site that is a member of a Drude
+ * pair.  Not inside a stream capture (the table is uploaded synchronously).  tgnh_get_num_virtual_sites: the sites in force.
+ *
+ * Everything below in fp64 in every precision.  A parent's position is posq, + posq_correction in mixed precision, as
+ * tgnh_get_drude_statistics defines it.  For the two average kinds every operation is rounded on its own (no fused multiply-add), in
+ * the order written above, per component.
+ * tgnh_compute_virtual_sites: where the reference calls computeVirtualSites (Cu :377).  Stored as the harness stores its sites:
+ * mixed precision the fp32 value and, in posq_correction, the residual; single precision rounded once.  Only x, y, z of the sites'
+ * slots are written: posq.w and posq_correction.w, every other slot, velm, posDelta and the force buffer stay bit for bit.
+ * tgnh_distribute_virtual_site_forces(force): right after the force call-out.  `force` is int64 [3*padded] fixed point x 2^32,
+ * planes x|y|z -- normally the bound buffer.  Per site f = F_site / 2^32; each parent's share is the transpose of the placement's
+ * Jacobian, at the current parent positions, applied to f:
+ *   averages            w_m f
+ *   out of plane        f2 = w12 f + wc (r13 x f), f3 = w13 f - wc (r12 x f), f1 = f - f2 - f3
+ *   local coordinates   through the two normalisations and the cross product (csrc/tgnh_virtual_sites.hip writes them out)
+ * Each component of each share is converted on its own, llrint(c * 4294967296.0), and added to the parent's entry as an integer: the
+ * result is a function of the inputs alone -- not of grid, order or device -- and no atomic operation touches the buffer.  The
+ * sites' own entries are read and left as they are: TWO CALLS ADD TWICE.  Call it once per force evaluation.
+ * One launch each on `stream`, none with an empty table (TGNH_OK); neither call synchronises, both can be captured into a hipGraph.
+ * Both may run at any time with respect to kicks a step still owes (tgnh_get_pending_state): sites have no mass, and nothing the
+ * handle carries depends on their positions.  A degenerate local-coordinates frame (sum wx x parallel to sum wy x) stores the
+ * non-finite numbers it produces; there is no status bit for it.  TGNH_ERR_STATE: a host-only handle, buffers not bound,
+ * (distribute) force is NULL.  tgnh_run_harness_constrained runs the placement right after the harness' -- the sites of the two
+ * tables are the caller's to keep disjoint. */
+enum { TGNH_SITE_TWO_AVERAGE = 0, TGNH_SITE_THREE_AVERAGE = 1, TGNH_SITE_OUT_OF_PLANE = 2, TGNH_SITE_LOCAL_COORDINATES = 3 };
+#define TGNH_SITE_PARAMS 12
+tgnh_status tgnh_set_virtual_sites(tgnh_handle h, int n, const int32_t* kind /* [n] */, const int32_t* atoms /* [n][4], p3 = -1: two parents */,
+                                   const double* params /* [n][TGNH_SITE_PARAMS] */);
+tgnh_status tgnh_get_num_virtual_sites(tgnh_handle h, int* count);
+tgnh_status tgnh_compute_virtual_sites(tgnh_handle h, void* stream);                             /* where Cu :377 calls out */
+tgnh_status tgnh_distribute_virtual_site_forces(tgnh_handle h, void* force, void* stream);       /* right after the force call-out */
 
 /* The call-outs of the reference's own testWater (platforms/reference/tests/TestReferenceDrudeTGNHIntegrator.cpp:111-166),
  * harness only: its force field -- NonbondedForce with reaction field, cutoff `cutoff` in a cubic box of edge `box`, +

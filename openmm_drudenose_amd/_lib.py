@@ -65,6 +65,8 @@ class TgnhFrameDesc(C.Structure):
 
 
 MIN_DRUDE_ONLY = 1
+SITE_TWO_AVERAGE, SITE_THREE_AVERAGE, SITE_OUT_OF_PLANE, SITE_LOCAL_COORDINATES = range(4)      # TGNH_SITE_* (tgnh_set_virtual_sites)
+SITE_PARAMS = 12
 
 
 class TgnhMinimizeDesc(C.Structure):
@@ -187,6 +189,10 @@ SIGNATURES = {
     "tgnh_get_num_constraint_clusters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "tgnh_apply_constraints": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "tgnh_apply_velocity_constraints": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "tgnh_set_virtual_sites": (C.c_int, [C.c_void_p, C.c_int, c_i32p, c_i32p, c_f64p]),
+    "tgnh_get_num_virtual_sites": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "tgnh_compute_virtual_sites": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tgnh_distribute_virtual_site_forces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tgnh_harness_water_force": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "tgnh_harness_remove_cm_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tgnh_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),

@@ -160,6 +160,16 @@ struct tgnh_context {
         tgnh::DeviceBuf<uint32_t> d_pairs;    // [count]
         void drop() { count = 0; d_atoms.reset(); d_invmass.reset(); d_d2.reset(); d_pairs.reset(); }
     } cons;
+    struct VirtualSites {             // tgnh_set_virtual_sites (tgnh_virtual_sites.cpp): the site table, rows sorted by site slot, and its inverse
+        int count = 0;                    // sites in force (a host-only handle keeps the count and nothing else)
+        int receivers = 0;                // slots that receive a share of some site's force
+        tgnh::DeviceBuf<int4> d_atoms;    // [count] (site, p1, p2, p3), uploaded at set time, never inside a capture
+        tgnh::DeviceBuf<int> d_kind;      // [count]
+        tgnh::DeviceBuf<double> d_params; // [12][count]
+        tgnh::DeviceBuf<int> d_recv_slot, d_recv_start, d_recv_row;    // [receivers], [receivers + 1], [entries]: the inverse in CSR form
+        tgnh::DeviceBuf<unsigned char> d_recv_role;                    // [entries]
+        void drop() { count = receivers = 0; d_atoms.reset(); d_kind.reset(); d_params.reset(); d_recv_slot.reset(); d_recv_start.reset(); d_recv_row.reset(); d_recv_role.reset(); }
+    } vsites;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block
         std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction

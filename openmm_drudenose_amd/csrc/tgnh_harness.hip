@@ -580,6 +580,7 @@ extern "C" tgnh_status tgnh_run_harness_constrained(tgnh_handle h, const void* x
         rc = tgnh_apply_constraints(h, tol, stream); if (rc) return rc;                  // ... the direct solver's clusters (disjoint from the harness': any order; none: no launch)
         rc = tgnh_step_begin_move(h, stream); if (rc) return rc;                         // Cu :366-376
         rc = tgnh_harness_virtual_sites(h, stream); if (rc) return rc;                   // Cu :377 call-out
+        rc = tgnh_compute_virtual_sites(h, stream); if (rc) return rc;                   // ... the library's own site table (disjoint from the harness': any order; none: no launch)
         rc = tgnh_harness_force(h, x0, k_drude, k_tether, const_cast<void*>(h->bound.force), stream); if (rc) return rc;   // Cu :380 call-out
         rc = tgnh_step_end_kick(h, stream); if (rc) return rc;                           // Cu :384-388
         if (h->d.mode == TGNH_MODE_TGNH) {                                               // Cu :391 call-out (the Reference platform has none)

@@ -306,6 +306,25 @@ class _HandleQueries:
         _check(self.lib.tgnh_get_num_constraint_clusters(self.h, C.byref(n)))
         return n.value
 
+    # ---- the library's own virtual-site table (include/drude_tgnh.h: tgnh_set_virtual_sites) ----
+    def set_virtual_sites(self, kinds, atoms, params):
+        """tgnh_set_virtual_sites: kinds [S] (_lib.SITE_*), atoms [S,4] = (site, p1, p2, p3) with p3 = -1 for a two-particle site,
+        params [S,12]; an empty table clears it.  The checks run on a host-only handle too."""
+        kinds = np.ascontiguousarray(kinds, np.int32).reshape(-1)
+        atoms = np.ascontiguousarray(atoms, np.int32).reshape(-1, 4)
+        params = np.ascontiguousarray(params, np.float64).reshape(-1, _lib.SITE_PARAMS)
+        if not len(kinds) == len(atoms) == len(params):
+            raise TgnhError(_lib.ERR_ARG, "set_virtual_sites: one kind, one row of atoms and one row of twelve parameters per site")
+        _check(self.lib.tgnh_set_virtual_sites(self.h, len(kinds), kinds.ctypes.data_as(_lib.c_i32p), atoms.ctypes.data_as(_lib.c_i32p),
+                                               params.ctypes.data_as(_lib.c_f64p)))
+
+    @property
+    def num_virtual_sites(self):
+        """tgnh_get_num_virtual_sites: the sites of the library's table"""
+        n = C.c_int()
+        _check(self.lib.tgnh_get_num_virtual_sites(self.h, C.byref(n)))
+        return n.value
+
     # ---- the periodic box and the size of a frame (include/drude_tgnh.h: tgnh_set_periodic_box, tgnh_get_frame_count) ----
     def setPeriodicBoxVectors(self, a, b, c):
         """tgnh_set_periodic_box: the three box vectors (nm) in OpenMM's reduced form -- a = (ax, 0, 0), b = (bx, by, 0),
@@ -463,11 +482,16 @@ class HipContext(_HandleQueries):
     flag only takes three degrees of freedom off the thermostats); an integer = tgnh_set_cm_motion_removal(every).
     direct_constraints: True hands the system's clusters of at most three constraints to the library's direct solver
     (split_clusters, tgnh_set_constraint_clusters) and only the rest to the harness' SHAKE; False (the default): all to the harness.
+    library_sites: True hands the system's three-particle-average sites to the library's own site table (tgnh_set_virtual_sites)
+    instead of the harness'; False (the default): to the harness.  A system's set_site_table goes to the library's table either way.
+    site_forces (an attribute, default False): True lets every compute_forces() end with one distribute_site_forces(), for a force_fn
+    that leaves forces on sites; the harness' water force spreads its M site's force itself and wants it off.
     """
+    _only_library_sites = False            # (minimizeEnergy: a context that says nothing else about itself is refused as a constrained one)
 
     def __init__(self, system, integrator, mode="TGNH", precision="mixed", device=0, flags=0, kB=KB,
                  k_drude=None, k_tether=None, allreduce=None, global_dof_sum=None, lattice_sites=True, cm_motion_removal=None,
-                 direct_constraints=False):
+                 direct_constraints=False, library_sites=False):
         import torch
         self.torch = torch
         self.lib = _lib.load()
@@ -537,11 +561,26 @@ class HipContext(_HandleQueries):
                 _check(self.lib.tgnh_harness_set_clusters(self.h, len(harness[0]), harness[0].ctypes.data_as(_lib.c_i32p),
                                                           harness[1].ctypes.data_as(_lib.c_f64p)))
             self.constrained = True
+        self.site_forces = False           # True: every compute_forces() is followed by one distribute_site_forces()
+        self._harness_sites = False        # the harness' site table holds sites (the system's three-particle averages, unless library_sites)
+        table = [np.zeros(0, np.int32), np.zeros((0, 4), np.int32), np.zeros((0, _lib.SITE_PARAMS))]     # what goes to the library's table
+        if system.site_table_kinds is not None and len(system.site_table_kinds):
+            table = [system.site_table_kinds, system.site_table_atoms, system.site_table_params]
         if system.site_atoms is not None and len(system.site_atoms):
-            _check(self.lib.tgnh_harness_set_virtual_sites(self.h, len(system.site_atoms),
-                                                           system.site_atoms.ctypes.data_as(_lib.c_i32p),
-                                                           system.site_weights.ctypes.data_as(_lib.c_f64p)))
+            if library_sites:
+                params = np.zeros((len(system.site_atoms), _lib.SITE_PARAMS))
+                params[:, :3] = system.site_weights
+                table = [np.concatenate([table[0], np.full(len(system.site_atoms), _lib.SITE_THREE_AVERAGE, np.int32)]),
+                         np.concatenate([table[1], system.site_atoms]), np.concatenate([table[2], params])]
+            else:
+                _check(self.lib.tgnh_harness_set_virtual_sites(self.h, len(system.site_atoms),
+                                                               system.site_atoms.ctypes.data_as(_lib.c_i32p),
+                                                               system.site_weights.ctypes.data_as(_lib.c_f64p)))
+                self._harness_sites = True
             self.constrained = True        # the split path is the one with the virtual-site call-out
+        self._only_library_sites = not self._has_clusters and not self._harness_sites     # what makes the context `constrained` is at most sites of the library's table
+        if len(table[0]):
+            self.set_virtual_sites(*table)
         if system.positions is not None:
             self.setPositions(system.positions)
             self.set_sites(system.positions)
@@ -878,13 +917,13 @@ class HipContext(_HandleQueries):
 
     def _minimize_batch(self, iterations):
         """`iterations` x {virtual sites where the context has them, the force call-out, one iteration}, enqueued back to back"""
-        sites = self.system.site_atoms is not None and len(self.system.site_atoms) > 0
+        sites = self._harness_sites or self.num_virtual_sites > 0
         if self.force_fn is None and not sites:
             _check(self.lib.tgnh_run_harness_minimize(self.h, self._x0_arg(), self.k_drude, self.k_tether, int(iterations), self._stream()))
             return
         for _ in range(iterations):
             if sites:
-                _check(self.lib.tgnh_harness_virtual_sites(self.h, self._stream()))
+                self._place_sites()
             self.compute_forces()
             self.minimize_iterate()
 
@@ -894,9 +933,13 @@ class HipContext(_HandleQueries):
         converged).  drude_only=True moves only the Drude particles (the relaxation a Drude system needs before its first step);
         moving: a mask, one entry per slot.  Massless slots never move.  The state is read back every check_every iterations;
         nothing else waits for the device.  **fire: FIRE_DEFAULTS' names.  Constraints are not projected: a constrained context
-        is refused unless drude_only or a mask says which slots are free to move.  Velocities, thermostat and step count stay as
+        is refused unless drude_only or a mask says which slots are free to move, and so is one whose virtual sites live in the
+        harness' table; sites in the library's table (library_sites=True, set_virtual_sites) are placed before every force
+        call-out and, with site_forces set, their forces spread after it, so every massive slot may move.  Velocities, thermostat and step count stay as
         they are.  Returns a MinimizeState; unless it says converged == 1 the forces are recomputed at the final positions."""
-        if self.constrained and not drude_only and moving is None:
+        # (sites in the library's table are placed before every force call-out and, with site_forces, their forces spread after it:
+        # such a context may move every massive slot; constraints, and sites in the harness' table, are refused as before)
+        if self.constrained and not self._only_library_sites and not drude_only and moving is None:
             raise TgnhError(_lib.ERR_STATE, "minimizeEnergy: the context has constraints or virtual sites and the minimiser projects no "
                                             "constraints: pass drude_only=True or a `moving` mask of slots that no constraint touches")
         if check_every < 1 or maxIterations < 0:
@@ -916,8 +959,7 @@ class HipContext(_HandleQueries):
         finally:
             self.minimize_end()
         if st.converged != 1:                                # (the buffer holds the forces of the positions before the last update)
-            if self.system.site_atoms is not None and len(self.system.site_atoms) > 0:
-                _check(self.lib.tgnh_harness_virtual_sites(self.h, self._stream()))
+            self._place_sites()
             self.compute_forces()
         return st
 
@@ -992,6 +1034,29 @@ class HipContext(_HandleQueries):
         _check(self.lib.tgnh_apply_velocity_constraints(self.h, tol, self._stream()))
         self.ke_sum_valid = False
 
+    # ---- the library's own virtual-site stage (include/drude_tgnh.h: tgnh_set_virtual_sites, ...) ----
+    def set_virtual_sites(self, kinds, atoms, params):
+        """tgnh_set_virtual_sites (see _HandleQueries.set_virtual_sites); a context with sites steps along the split path, the one
+        with the virtual-site call-out."""
+        super().set_virtual_sites(kinds, atoms, params)
+        if self.num_virtual_sites:
+            self.constrained = True
+
+    def compute_virtual_sites(self):
+        """tgnh_compute_virtual_sites: every site of the library's table placed from its parents.  No synchronisation."""
+        _check(self.lib.tgnh_compute_virtual_sites(self.h, self._stream()))
+
+    def distribute_site_forces(self):
+        """tgnh_distribute_virtual_site_forces on the context's force buffer: what the buffer holds on sites is spread over their
+        parents (and left on the sites, which have no mass: a second call adds a second time).  No synchronisation."""
+        _check(self.lib.tgnh_distribute_virtual_site_forces(self.h, self.force.data_ptr(), self._stream()))
+
+    def _place_sites(self):
+        """the virtual-site call-out (Cu :377): the harness' table where it holds sites, then the library's (none: no launch)"""
+        if self._harness_sites:
+            _check(self.lib.tgnh_harness_virtual_sites(self.h, self._stream()))
+        _check(self.lib.tgnh_compute_virtual_sites(self.h, self._stream()))
+
     def setCharges(self, q):
         """posq.w of every slot (OpenMM keeps the charge there; setPositions leaves it alone).  No step kernel reads it."""
         self.posq[:, 3] = self.torch.from_numpy(np.ascontiguousarray(q, np.float64)).to(self.dev, self.rdt)
@@ -1030,6 +1095,8 @@ class HipContext(_HandleQueries):
         else:
             _check(self.lib.tgnh_harness_force(self.h, self._x0_arg(), self.k_drude, self.k_tether,
                                                self.force.data_ptr(), self._stream()))
+        if self.site_forces:
+            self.distribute_site_forces()
 
     def step_begin(self):
         _check(self.lib.tgnh_step_begin(self.h, self._stream()))
@@ -1065,7 +1132,7 @@ class HipContext(_HandleQueries):
             _check(lib.tgnh_harness_shake_positions(h, tol, self._stream()))   # Cu :363
             _check(lib.tgnh_apply_constraints(h, tol, self._stream()))         # ... the direct solver's clusters
             _check(lib.tgnh_step_begin_move(h, self._stream()))          # Cu :366-376
-            _check(lib.tgnh_harness_virtual_sites(h, self._stream()))    # Cu :377
+            self._place_sites()                                          # Cu :377
             self.compute_forces()                                        # Cu :380
             _check(lib.tgnh_step_end_kick(h, self._stream()))            # Cu :384-388
             if self.mode == MODE_TGNH:

@@ -22,6 +22,10 @@ class DrudeSystem:
     cluster_dist: np.ndarray = None        # [K,6] distances for pairs (0,1)(0,2)(0,3)(1,2)(1,3)(2,3), 0 = none
     site_atoms: np.ndarray = None          # [S,4] (site, p1, p2, p3)
     site_weights: np.ndarray = None        # [S,3]
+    # the library's own site table (tgnh_set_virtual_sites): set_site_table
+    site_table_kinds: np.ndarray = None    # [T] 0 two-particle average, 1 three-particle average, 2 out of plane, 3 local coordinates
+    site_table_atoms: np.ndarray = None    # [T,4] (site, p1, p2, p3), p3 = -1 for a two-particle site
+    site_table_params: np.ndarray = None   # [T,12]
     # harness only: the box repeats ONE molecule on a simple cubic lattice (synth.water_box) -- (slots per molecule, side, spacing nm,
     # geometry [slots][3], index of this system's first molecule in the box); a hint for the harness force's tether sites, checked
     # slot by slot by the library before it is used
@@ -51,6 +55,16 @@ class DrudeSystem:
     def set_virtual_sites(self, atoms, weights):
         self.site_atoms = np.ascontiguousarray(atoms, np.int32).reshape(-1, 4)
         self.site_weights = np.ascontiguousarray(weights, np.float64).reshape(-1, 3)
+
+    def set_site_table(self, kinds, atoms, params):
+        """Virtual sites of any of the library's four kinds (tgnh_set_virtual_sites): kinds [S], atoms [S,4] = (site, p1, p2, p3) with
+        p3 = -1 for a two-particle site, params [S,12] (a row shorter than 12 is padded with zeros).  They go to the library's own
+        site table, whatever HipContext's library_sites says; set_virtual_sites' three-particle averages are kept beside them."""
+        self.site_table_kinds = np.ascontiguousarray(kinds, np.int32).reshape(-1)
+        self.site_table_atoms = np.ascontiguousarray(atoms, np.int32).reshape(-1, 4)
+        p = np.asarray(params, np.float64).reshape(len(self.site_table_kinds), -1)
+        self.site_table_params = np.zeros((len(p), 12))
+        self.site_table_params[:, :p.shape[1]] = p
 
     @property
     def num_particles(self):
