@@ -262,7 +262,9 @@ tgnh_status tgnh_step_begin_move(tgnh_handle h, void* stream);
 tgnh_status tgnh_step_end_kick(tgnh_handle h, void* stream);
 tgnh_status tgnh_step_end_thermo(tgnh_handle h, void* stream);
 /* Apply the half kick and rescale still pending (TGNH_FLAG_DEFER_SCALE) so velm is the
- * reference's end-of-step state; call before anything else reads velm. */
+ * reference's end-of-step state; call before anything else reads OR WRITES velm -- between tgnh_step_begin and tgnh_step_end
+ * too on a DEFER_SCALE | RESIDENT_STEP handle, where the velocities may live in the library's own planes (bit 10 of
+ * tgnh_get_pending_state) and the flush is what writes them to velm.  Nothing pending: no launch. */
 tgnh_status tgnh_flush(tgnh_handle h, void* stream);
 /* A caller that captured `nsteps` steps into a hipGraph and replays it tells the handle here: the host-side
  * clock and step count advance only when the step functions are called, not when a graph is replayed.
@@ -278,12 +280,32 @@ tgnh_status tgnh_note_replayed_steps(tgnh_handle h, int nsteps);
  * 2 velm lags by the second half kick, 3 the next step's first thermostat half has already run (DEFER_SCALE), 4 the summed
  * kinetic energies wait for the next rescale launch to run the chain, 5 the partial rows are not summed yet, 6 an exchange is
  * sent but not yet waited for, 7 the advanced thermostat block sits in the staging copy, 8 direction of the next sweep,
- * 9 the next thermostat half step starts from the kinetic energies the last one left (TGNH_FLAG_TRUST_STATE_CHANGED). */
+ * 9 the next thermostat half step starts from the kinetic energies the last one left (TGNH_FLAG_TRUST_STATE_CHANGED),
+ * 10 the velocities live in the library's own x | y | z planes and velm's x, y, z are as old as the last flush or query that
+ * needed them (the one-launch step of DEFER_SCALE | RESIDENT_STEP, see tgnh_get_velocity_planes; tgnh_flush brings velm up to date). */
 tgnh_status tgnh_get_pending_state(tgnh_handle h, uint32_t* bits);
+/* The one-launch step's private velocity layout (inspection only).  A handle whose whole deferred step is one launch over wave
+ * tiles of identical molecules keeps the velocities, between two flushes, in three planes of its own without velm's 1/m word:
+ * the launch then moves 24 B per slot less (mixed and double precision; a single-precision handle stays on velm).  Results are bit for bit those of a handle that stays on
+ * velm; the flush contract is unchanged (tgnh_flush, or any call that hands velocities out, first writes velm).  The planes are
+ * entered after out[3] one-launch steps in a row and left by whatever settles velm.  TGNH_VELOCITY_PLANES=0 in the environment
+ * at tgnh_create keeps a handle on velm.
+ * out[0] 1: the velocities live in the planes now (bit 10 of tgnh_get_pending_state); out[1] 1: this handle can take them (its
+ * topology qualifies, they were allocated at create, velm's w has not been found to differ from 1 / mass, and no steps were
+ * recorded into a graph while velm held the velocities); out[2] one-launch steps in a row since the last settle; out[3] the
+ * threshold. */
+tgnh_status tgnh_get_velocity_planes(tgnh_handle h, int32_t out[4]);
 /* Restore the clock of a checkpointed run (time, stepCount: ReferenceDrudeTGNHKernels.cpp:413-414, CudaDrudeTGNHKernels.cpp:405-406). */
 tgnh_status tgnh_set_time(tgnh_handle h, double time, int64_t step_count);
 /* Velocities were changed behind the integrator's back (setVelocities, CMMotionRemover,
- * barostat): cached kinetic energies are stale.  DrudeTGNHIntegrator.cpp:166-170 */
+ * barostat): cached kinetic energies are stale.  DrudeTGNHIntegrator.cpp:166-170
+ * Host-side bookkeeping, with one exception.  While bit 10 of tgnh_get_pending_state is set (a DEFER_SCALE | RESIDENT_STEP
+ * handle between tgnh_step_begin and tgnh_step_end: the velocities live in the library's planes) the call first WRITES velm's
+ * x, y, z from the planes -- one launch on the stream of the last tgnh_step_begin, which must still exist -- so that the
+ * planes are not carried on past the change.  A caller that writes velm on such a handle therefore calls tgnh_flush(stream)
+ * first, then writes, then calls this (after the flush bit 10 is clear and nothing is launched here); called after a write that no
+ * flush preceded, it overwrites that write.  tgnh_bind_buffers with another velm array does the same for the array that goes.
+ * HipContext.setVelocities and the library's own velocity setters keep this order. */
 tgnh_status tgnh_state_changed(tgnh_handle h);
 
 /* Context::setVelocitiesToTemperature for a Drude system: draws x, y, z of EVERY slot of the bound velm on the device, one

@@ -109,6 +109,7 @@ SIGNATURES = {
     "tgnh_rccl_shutdown": (C.c_int, [C.c_void_p]),
     "tgnh_exchange_wait_stats": (C.c_int, [C.c_void_p, C.c_void_p, c_f64p, c_f64p, C.POINTER(C.c_int64)]),
     "tgnh_get_pending_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "tgnh_get_velocity_planes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "tgnh_set_resident_share": (C.c_int, [C.c_void_p, C.c_int]),
     "tgnh_get_resident_work_groups": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "tgnh_get_resident_kernel": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),

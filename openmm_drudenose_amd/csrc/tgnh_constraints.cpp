@@ -131,6 +131,7 @@ extern "C" tgnh_status tgnh_apply_velocity_constraints(tgnh_handle h, double tol
     h->owed.ke_carry = false;                 // velocities are about to change behind the integrator, as in tgnh_harness_shake_velocities
     if (h->cons.count == 0) return TGNH_OK;
     HIP_OK(hipSetDevice(h->device));
+    rc = velm_current(h, (hipStream_t)stream); if (rc) return rc;
     HIP_OK(launch_constrain_velocities(h->d.precision, constraint_args(h, tol), (hipStream_t)stream));
     return TGNH_OK;
 }

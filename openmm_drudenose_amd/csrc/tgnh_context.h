@@ -74,6 +74,8 @@ struct tgnh_context {
         std::vector<uint32_t> wmeta;
         std::vector<uint32_t> tile_pat, wtile_pat;    // per 512-slot tile: period | molecules << 8 | pattern << 16; per wave tile: period | pattern << 8; 0 = none
         std::vector<uint32_t> pattern, wpattern;      // 64 words per pattern
+        std::vector<double> wpat_mass;                // beside wpattern: the descriptor masses of a wave pattern's slots, 64 per pattern
+        bool wpat_all_uniform = false;                // every wave tile is patterned, and every slot's mass is its pattern entry's
         int num_wtiles = 0;
         tgnh::DeviceBuf<uint32_t> d_meta, d_wmeta, d_tile_pat, d_pattern, d_wpattern;
         tgnh::DeviceBuf<int> d_tile_start, d_tile_res;
@@ -196,6 +198,18 @@ struct tgnh_context {
         int wresident_per_cu = 0, wresident_grid = 0;   // the same for wstep_kernel (0: none, or no wave tiles)
         int resident_per_cu = 0;          // work-groups of step_kernel per compute unit that the census at create found resident together (0: none -- the handle steps the DEFER_SCALE way)
     } cfg;
+    // The one-launch step's velocities as three planes (tgnh_vplanes.hip): the library's own copy of velm's x, y, z
+    // between flushes of a DEFER_SCALE | RESIDENT_STEP sequence.  Owed::planes_live says which of the two holds the velocities.
+    struct VelPlanes {
+        tgnh::DeviceBytes d_planes;       // x | y | z of Prec::mixed, stride padded: allocated at create where the handle can take them, never later
+        tgnh::DeviceBytes d_invm;         // [patterns][64] Prec::mixed: 1 / Topology::wpat_mass (0 for a massless slot), what velm's w must hold
+        tgnh::DeviceBuf<uint32_t> d_mismatch;   // the first conversion of a bind ORs 1 in here when some slot's w is not its table entry
+        int verdict = 0;                  // of that check: 0 not made yet, 1 the table is velm's w, -1 it is not (the handle stays on velm)
+        int streak = 0;                   // one-launch steps in a row since the last settle (enter_planes' hysteresis)
+        bool pinned = false;              // steps were recorded into a graph while velm held the velocities: the handle stays there
+        hipStream_t stream = nullptr;     // of the launch that last wrote the planes (tgnh_state_changed has no stream of its own)
+        bool usable() const { return d_planes.get() != nullptr && verdict >= 0 && !pinned; }
+    } vp;
     // What a step still owes: work an entry point has left to a later launch, and what the last launches left behind.
     struct Owed {
         // the first eight are bits 0..7 of tgnh_get_pending_state, in this order; the last five are not reported
@@ -208,6 +222,7 @@ struct tgnh_context {
         bool xwait_pending = false;       // with chain_pending: the sums were sent over the mailboxes, nobody has waited for the peers' yet
         bool stage_pending = false;       // d_stage is newer than d_state; the next chain_kernel launch commits it
         bool ke_carry = false;            // (bit 9) TRUST_STATE_CHANGED: ke_post of the last end half IS the kinetic energy of the stored velocities
+        bool planes_live = false;         // (bit 10) the velocities live in VelPlanes::d_planes; velm's x, y, z are as old as the last settle (settle_end leaves)
         bool chain_pending_twice = false; // with chain_pending: both chain halves (DEFER_SCALE)
         bool carry_pending = false;       // ... and that KE is the last chain's ke_post (ChainArgs::ke_carry), not ke_red
         bool tail_summed = false;         // the last KE launch summed its rows itself (wke_kernel's tail sum): no row-sum launch
@@ -216,7 +231,7 @@ struct tgnh_context {
         enum : uint32_t { BIT_SWEEP_REVERSE = 1u << 8 };      // (Run::sweep_reverse, reported beside these)
         uint32_t bits() const {           // the layout include/drude_tgnh.h documents, written down here and nowhere else
             return end_pending | scale_pending << 1 | kick_pending << 2 | first_half_done << 3 | chain_pending << 4 | sum_pending << 5 |
-                   xwait_pending << 6 | stage_pending << 7 | ke_carry << 9;
+                   xwait_pending << 6 | stage_pending << 7 | ke_carry << 9 | planes_live << 10;
         }
         void chain_owed(bool twice) { chain_pending = true; chain_pending_twice = twice; }           // (whoever leaves it says what else the rescale launch does: sum_pending, xwait_pending, carry_pending)
         void chain_ran() { chain_pending = sum_pending = xwait_pending = carry_pending = false; }     // (whoever ran it says where the block now lies: stage_pending)

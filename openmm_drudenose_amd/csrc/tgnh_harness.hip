@@ -497,6 +497,8 @@ using namespace tgnh;
 #define H_FAIL(code, msg) do { tgnh_set_error(msg); return code; } while (0)
 #define H_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { tgnh_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return TGNH_ERR_HIP; } } while (0)
 
+tgnh_status velm_current(tgnh_handle h, hipStream_t s) __attribute__((visibility("hidden")));     // tgnh_step.cpp (tgnh_host.h): before velm is written without a settle
+
 static tgnh_status harness_ready(tgnh_handle h) {
     if (!h) H_FAIL(TGNH_ERR_ARG, "null handle");
     if (h->host_only) H_FAIL(TGNH_ERR_STATE, "host-only handle (device -1): no GPU work can be launched on it");
@@ -541,6 +543,7 @@ extern "C" tgnh_status tgnh_harness_shake_velocities(tgnh_handle h, double tol, 
     h->owed.ke_carry = false;                 // velocities are about to change behind the integrator (TRUST_STATE_CHANGED: recompute)
     if (h->harness.num_clusters == 0) return TGNH_OK;
     H_HIP(hipSetDevice(h->device));
+    rc = velm_current(h, (hipStream_t)stream); if (rc) return rc;
     H_HIP(launch_shake<true>(h->d.precision, cluster_args(h, tol), (hipStream_t)stream));
     return TGNH_OK;
 }
@@ -616,6 +619,7 @@ extern "C" tgnh_status tgnh_harness_remove_cm_motion(tgnh_handle h, void* stream
     h->owed.ke_carry = false;                 // (OpenMM's CMMotionRemover does not tell the integrator: the glue does not set TRUST_STATE_CHANGED beside one)
     H_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
+    rc = velm_current(h, s); if (rc) return rc;
     auto fn = with_precision(h->d.precision, [](auto P) { return &cmm_kernel<decltype(P)::value>; });
     if (!fn) H_FAIL(TGNH_ERR_ARG, "unknown precision");
     TGNH_LAUNCH(fn, dim3(1), dim3(BLOCK), 0, s, h->bound.velm, h->d.num_particles);

@@ -1,7 +1,7 @@
 // tgnh_host.h -- what the host units behind the C ABI (include/drude_tgnh.h) share: tgnh_topology.cpp, tgnh_lifecycle.cpp,
 // tgnh_exchange.cpp, tgnh_step.cpp, tgnh_velocities.cpp, tgnh_queries.cpp, tgnh_positions.cpp, tgnh_frames.cpp, tgnh_minimize.cpp, tgnh_constraints.cpp, tgnh_virtual_sites.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
 // live in tgnh_kernels.hip (tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h), tgnh_gather.hip, tgnh_velinit.hip,
-// tgnh_drude_stats.hip, tgnh_cm_motion.hip, tgnh_rescale.hip, tgnh_scale_positions.hip, tgnh_wrap.hip, tgnh_minimize.hip, tgnh_constraints.hip, tgnh_virtual_sites.hip and tgnh_harness.hip.
+// tgnh_drude_stats.hip, tgnh_cm_motion.hip, tgnh_rescale.hip, tgnh_scale_positions.hip, tgnh_wrap.hip, tgnh_minimize.hip, tgnh_constraints.hip, tgnh_virtual_sites.hip, tgnh_vplanes.hip and tgnh_harness.hip.
 //
 // Reference semantics followed (scychon/openmm_drudeNose):
 //   Ref = platforms/reference/src/ReferenceDrudeTGNHKernels.cpp
@@ -20,6 +20,7 @@
 #include "tgnh_minimize.h"
 #include "tgnh_rescale.h"
 #include "tgnh_scale_positions.h"
+#include "tgnh_vplanes.h"
 
 using namespace tgnh;
 
@@ -64,6 +65,7 @@ tgnh_status run_chain_gather(tgnh_handle h, hipStream_t s, bool sum_only);
 tgnh_status materialize_chain(tgnh_handle h, hipStream_t s);
 tgnh_status settle_kick(tgnh_handle h, hipStream_t s);
 tgnh_status settle_end(tgnh_handle h, hipStream_t s);
+tgnh_status velm_current(tgnh_handle h, hipStream_t s);        // velocity planes left live with nothing else pending go back to velm (before velm is touched without a settle)
 tgnh_status flush_impl(tgnh_handle h, hipStream_t s);
 tgnh_status ke_query_launches(tgnh_handle h, hipStream_t s);    // tgnh_queries.cpp: what tgnh_compute_kinetic_energies enqueues behind its entry checks
 tgnh_status cm_removal_due(tgnh_handle h, hipStream_t s);      // tgnh_velocities.cpp: tgnh_set_cm_motion_removal's launches where this step is due; a step begins with this

@@ -226,6 +226,11 @@ struct TileArgs {
     const double* st_in;
     double* st_out;
     ChainArgs chain;
+    // wstep_kernel, velocities as planes (tgnh_vplanes.h): vplanes != nullptr = x | y | z of Prec::mixed, stride `padded`, hold the
+    // velocities and velm is neither read nor written; a slot's 1/m is wpat_invm[pattern * PATTERN_WORDS + position in the pattern]
+    // (Prec::mixed, bit for bit velm's w: every tile of such a launch is patterned).  Last, so that no other field moves.
+    void* vplanes;
+    const void* wpat_invm;
 };
 
 struct BigComArgs {
@@ -319,8 +324,8 @@ int tile_blocks_per_cu(int precision, int ops, int gb, size_t lds, bool multi = 
 hipError_t launch_step(int precision, int gb, int kind, const TileArgs& a, int grid, size_t lds, hipStream_t s);
 int step_blocks_per_cu(int precision, int gb, int kind, size_t lds);
 int step_kind_ops2(int kind);       // operations of the kind's second pass (its LDS needs)
-hipError_t launch_wstep(int precision, int gb, bool multi, const TileArgs& a, int grid, hipStream_t s);   // a whole deferred step over wave tiles
-int wstep_blocks_per_cu(int precision, int gb, bool multi);
+hipError_t launch_wstep(int precision, int gb, bool multi, const TileArgs& a, int grid, hipStream_t s);   // a whole deferred step over wave tiles (a.vplanes set: wstep_planes_kernel)
+int wstep_blocks_per_cu(int precision, int gb, bool multi, bool planes = false);
 hipError_t launch_wke(int precision, int ops, int gb, const TileArgs& a, int grid, hipStream_t s);   // KE passes over wave tiles
 int wke_blocks_per_cu(int precision, int ops, int gb);
 hipError_t launch_chain(const ChainArgs& a, hipStream_t s);

@@ -191,6 +191,30 @@ static tgnh_status resident_census(tgnh_context* c) {
                   &c->cfg.wresident_per_cu);
 }
 
+// The one-launch step's velocity planes (tgnh_context.h VelPlanes), for a handle that can take them: it steps with wstep_kernel
+// (a whole deferred step over wave tiles: the census above found a grid), every wave tile is patterned and every slot's mass is
+// its pattern entry's -- then 1/m is a function of a lane's place in the pattern and the kernel needs no w per slot.  Allocated
+// here and never later (an allocation inside somebody's stream capture would fail it): 3 x padded x sizeof(mixed), 120 MB for
+// 5 M slots in mixed precision.  TGNH_VELOCITY_PLANES=0 in the environment keeps a handle on velm (both forms from one build).
+static tgnh_status allocate_velocity_planes(tgnh_context* c) {
+    if (const char* e = getenv("TGNH_VELOCITY_PLANES")) if (e[0] == '0') return TGNH_OK;
+    if (!(c->d.flags & TGNH_FLAG_DEFER_SCALE) || c->cfg.wresident_per_cu <= 0 || !c->topo.wpat_all_uniform) return TGNH_OK;
+    // Single precision stays on velm: there the two kernels do not give the same bits (tgnh_wave_kernels.h, wstep_fn_gb)
+    if (c->d.precision == TGNH_PREC_SINGLE) return TGNH_OK;
+    // (the census counted work-groups of wstep_kernel: wstep_planes_kernel meets on the same grid, so it must hold as many per compute unit)
+    if (wstep_blocks_per_cu(c->d.precision, c->cfg.gb, c->thermo.L.C > 1, true) < c->cfg.wresident_per_cu) return TGNH_OK;
+    const bool single = c->d.precision == TGNH_PREC_SINGLE;
+    const size_t word = single ? sizeof(float) : sizeof(double), n = c->topo.wpat_mass.size();
+    // what velm's w holds for a slot of mass m: 1 / m in fp64, rounded to velm's type; 0 for a massless slot
+    std::vector<double> inv(n);
+    for (size_t k = 0; k < n; k++) inv[k] = c->topo.wpat_mass[k] == 0.0 ? 0.0 : 1.0 / c->topo.wpat_mass[k];
+    std::vector<float> inv_f(inv.begin(), inv.end());
+    HIP_OK(c->vp.d_invm.upload(reinterpret_cast<const unsigned char*>(single ? (const void*)inv_f.data() : (const void*)inv.data()), n * word));
+    HIP_OK(c->vp.d_mismatch.alloc(1, true));
+    HIP_OK(c->vp.d_planes.alloc(3 * (size_t)c->d.padded_num_particles * word, true));
+    return TGNH_OK;
+}
+
 extern "C" tgnh_status tgnh_create(const tgnh_desc* d, tgnh_handle* out) {
     if (!d || !out) return fail(TGNH_ERR_ARG, "null argument");
     bool long_chain = false;
@@ -229,6 +253,7 @@ extern "C" tgnh_status tgnh_create(const tgnh_desc* d, tgnh_handle* out) {
     if (!host_only) {
         rc = allocate(c); if (rc) return rc;
         rc = resident_census(c); if (rc) return rc;
+        rc = allocate_velocity_planes(c); if (rc) return rc;
     }
     rc = finalize_thermostat(c); if (rc) return rc;
     *out = owner.release();
@@ -274,6 +299,13 @@ extern "C" tgnh_status tgnh_bind_buffers(tgnh_handle h, void* posq, void* posq_c
         }
     }
     h->owed.ke_carry = false;                                  // (other buffers: nothing computed from the old ones carries over)
+    if (velm != h->bound.velm) {
+        // Velocity planes live here: the call comes between tgnh_step_begin and tgnh_step_end (nothing is pending, see above).  The
+        // array that goes gets the velocities back first, as a caller who copies it expects; the new one's w is checked anew, and
+        // steps recorded on the old one no longer pin the handle (their graph holds the old pointer).
+        tgnh_status rc = velm_current(h, h->vp.stream); if (rc) return rc;
+        h->vp.verdict = 0; h->vp.pinned = false; h->vp.streak = 0;
+    }
     if (posq != h->bound.posq || posq_correction != h->bound.posq_corr) h->snap.valid = false;      // (tgnh_restore_positions: its snapshot is of the old arrays)
     h->bound.posq = posq; h->bound.posq_corr = posq_correction; h->bound.velm = velm; h->bound.force = force; h->bound.pos_delta = pos_delta;
     return TGNH_OK;

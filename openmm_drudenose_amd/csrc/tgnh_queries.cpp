@@ -270,7 +270,8 @@ extern "C" tgnh_status tgnh_algorithmic_bytes(tgnh_handle h, int kernel, double*
         case KID_FORCE: b = N * (X + F); break;                 // harness: X r, F w (x0 excluded)
         case KID_STEP:       // step_kernel: its two passes.  Deferred: (V r, F r) + (V r/w, F r, X r/w); the reference's pass
                              // structure: begin (V r) + (V r/w, F r, X r/w) and end (V r, F r) + (V r/w, F r), averaged per launch
-            b = (h->d.flags & TGNH_FLAG_DEFER_SCALE) ? N * (3 * V + 2 * F + 2 * X) : N * (6 * V + 3 * F + 2 * X) / 2; break;
+                             // (velocities in the library's planes, owed.planes_live: x, y, z without the 1/m word -- three quarters of V)
+            b = (h->d.flags & TGNH_FLAG_DEFER_SCALE) ? N * (3 * (h->owed.planes_live ? 0.75 * V : V) + 2 * F + 2 * X) : N * (6 * V + 3 * F + 2 * X) / 2; break;
         default: b = 0;
     }
     *bytes = b;

@@ -418,16 +418,79 @@ extern "C" tgnh_status tgnh_get_resident_kernel(tgnh_handle h, int* which) {
     return TGNH_OK;
 }
 
+// ---- wstep_kernel's velocities as three planes (tgnh_vplanes.hip) ----
+// Between the steps of a DEFER_SCALE | RESIDENT_STEP sequence velm is stale by contract (owed.end_pending), and everybody who
+// needs real velocities comes through settle_end.  So between two settles the library may keep the velocities where the kernel
+// moves fewest bytes: x | y | z planes of its own, without the 1/m word (owed.planes_live; VelPlanes in tgnh_context.h).  Both
+// layouts give the same bits: where the velocities live changes no result, only the bytes a step moves.
+//
+// Entered by the one-launch step after PLANES_AFTER_STEPS such steps in a row since the last settle.  The two conversions of
+// one stay on the planes move 56 + 88 B per slot (mixed) and a step there saves 24, so a stay pays from its seventh step.  A
+// caller that settles every step never reaches the threshold and never converts; one that settles every 100 steps or more --
+// a reporter -- loses the gain of 8 steps in 100; the worst case, a settle every 10 steps, converts for one step on the planes and is
+// 4 % of its ten steps' bytes slower.  With 4 that worst case is 8 %, with 16 it is 2 % and a stay shorter than 16 steps gains nothing.
+constexpr int PLANES_AFTER_STEPS = 8;
+
+// planes -> velm (no Timed scope: tests/test_launch_structure_gpu.py counts the scopes of a settle)
+static tgnh_status leave_planes(tgnh_handle h, hipStream_t s) {
+    if (!h->owed.planes_live) return TGNH_OK;
+    HIP_OK(launch_planes_to_velm(h->d.precision, h->vp.d_planes, h->bound.velm, h->d.num_particles, h->d.padded_num_particles, s));
+    h->owed.planes_live = false;
+    return TGNH_OK;
+}
+
+// velm -> planes, when the one-launch step about to go out is due to run on them.  Never inside a stream capture: a conversion
+// baked into a graph would be replayed from stale data, and the first conversion of a bind waits for the device (it checks that
+// the inverse masses the kernel will take from its pattern table are velm's w, bit for bit; the verdict is kept).  Steps
+// recorded while velm holds the velocities pin the handle there: their graph may be replayed between eager steps for good.
+static tgnh_status enter_planes(tgnh_handle h, hipStream_t s) {
+    tgnh_context::VelPlanes& vp = h->vp;
+    if (h->owed.planes_live || !vp.usable()) return TGNH_OK;
+    if (stream_capturing(s)) { vp.pinned = true; return TGNH_OK; }
+    if (vp.streak < PLANES_AFTER_STEPS) return TGNH_OK;
+    const bool check = vp.verdict == 0;
+    if (check) HIP_OK(hipMemsetAsync(vp.d_mismatch, 0, sizeof(uint32_t), s));
+    HIP_OK(launch_velm_to_planes(h->d.precision, h->bound.velm, vp.d_planes, h->topo.d_wave_tile, h->topo.num_wtiles, vp.d_invm,
+                                 h->d.padded_num_particles, check ? vp.d_mismatch.get() : nullptr, s));
+    if (check) {
+        uint32_t differs = 1;
+        HIP_OK(hipMemcpyAsync(&differs, vp.d_mismatch, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_OK(hipStreamSynchronize(s));
+        vp.verdict = differs ? -1 : 1;
+        if (differs) return TGNH_OK;                        // some w is not 1 / (descriptor mass) as the table has it: velm it stays, same results
+    }
+    h->owed.planes_live = true;
+    return TGNH_OK;
+}
+
+// velm holds what the handle's other flags say it holds: planes that a one-launch step left live with nothing else pending
+// (between tgnh_step_begin and tgnh_step_end) are written back.  For the entry points that touch velm without settling anything.
+tgnh_status velm_current(tgnh_handle h, hipStream_t s) {
+    return h->owed.planes_live && !h->owed.end_pending ? settle_end(h, s) : TGNH_OK;
+}
+
+extern "C" tgnh_status tgnh_get_velocity_planes(tgnh_handle h, int32_t out[4]) {
+    CHECK_H(h);
+    if (!out) return fail(TGNH_ERR_ARG, "null out");
+    out[0] = h->owed.planes_live ? 1 : 0; out[1] = h->vp.usable() ? 1 : 0; out[2] = h->vp.streak; out[3] = PLANES_AFTER_STEPS;
+    return TGNH_OK;
+}
+
 // One launch of step_kernel.  kind 0: a whole deferred step (the last step's end half + this step's begin half, both chain
 // halves); 1 / 2: the begin / end half of the reference's pass structure; 3 / 4: the same around the constraint call-outs.
 static tgnh_status run_resident(tgnh_handle h, hipStream_t s, int kind) {
     if (h->owed.stage_pending) { tgnh_status rc = commit_stage(h, s); if (rc) return rc; }
+    const bool wstep = resident_kernel(h, kind) == 2;
+    // where this launch finds the velocities (only the one-launch step ever leaves them in the planes, and every other way to a
+    // launch goes through settle_end first: tgnh_step_begin, second_half, split_entry)
+    if (wstep && kind == 0) { tgnh_status rc = enter_planes(h, s); if (rc) return rc; }
+    else if (h->owed.planes_live) return fail(TGNH_ERR_STATE, "internal: a launch that reads velm while the velocities live in the planes");
     TileArgs a = tile_args(h, nullptr);
+    if (h->owed.planes_live) { a.vplanes = h->vp.d_planes; a.wpat_invm = h->vp.d_invm; h->vp.stream = s; }
     const int ops2 = step_kind_ops2(kind);
     if ((ops2 & OP_POSDELTA) && !h->bound.pos_delta) return fail(TGNH_ERR_STATE, "posDelta buffer not bound");
     const bool hw = a.hardwall != 0 && (ops2 & (OP_DRIFT | OP_MOVE));
     const size_t lds = tile_lds_bytes(h->d.precision, ops2, hw, a.use_com != 0);
-    const bool wstep = resident_kernel(h, kind) == 2;
     int& grid = h->cfg.resident_grid[kind][hw ? 1 : 0];
     if (grid == 0 && !wstep) {       // the work-groups that are resident at once (counted at create; never more than this kind's own occupancy)
         int per_cu = std::min(h->cfg.resident_per_cu, step_blocks_per_cu(h->d.precision, h->cfg.gb, kind, lds));
@@ -457,6 +520,7 @@ static tgnh_status run_resident(tgnh_handle h, hipStream_t s, int kind) {
     }
     // the first pass walked the tiles in direction sweep_reverse, the second one back: the next launch starts here
     h->owed.resident_settled();
+    if (wstep && kind == 0 && h->vp.usable()) h->vp.streak = std::min(h->vp.streak + 1, 1 << 30);         // (enter_planes' count; a recording on velm has pinned the handle and counts nothing)
     return TGNH_OK;
 }
 
@@ -528,10 +592,8 @@ extern "C" tgnh_status tgnh_step_begin(tgnh_handle h, void* stream) {
     rc = cm_removal_due(h, s); if (rc) return rc;
     rc = rescale_due(h, s); if (rc) return rc;
     start_of_step(h);
-    if (h->owed.end_pending) {
-        if (resident_now(h)) return run_resident(h, s, 0);           // the last step's end half and this begin half: one launch
-        rc = settle_end(h, s); if (rc) return rc;
-    }
+    if (h->owed.end_pending && resident_now(h)) return run_resident(h, s, 0);      // the last step's end half and this begin half: one launch
+    rc = settle_end(h, s); if (rc) return rc;                        // (an end half that waits; velocity planes a step without an end half left live)
     if (!(h->d.flags & TGNH_FLAG_DEFER_SCALE) && resident_now(h) && !h->owed.ke_carry)
         return run_resident(h, s, 1);                                // reference pass structure: KE, chain, rescale+kick+drift in one launch
     rc = first_half(h, s); if (rc) return rc;                       // (kinetic energies carried over: no first pass, no meeting -- the tile launch with its in-kernel chain)
@@ -546,6 +608,7 @@ static tgnh_status second_half(tgnh_handle h, hipStream_t s, int kick_ops) {
     const bool defer = (h->d.flags & TGNH_FLAG_DEFER_SCALE) != 0;
     h->owed.ke_carry = false;                                   // (an end half without a begin half before it: its own KE pass runs in any case)
     if (h->owed.scale_pending || h->owed.kick_pending || h->owed.end_pending) { rc = flush_impl(h, s); if (rc) return rc; }   // two end halves in a row
+    if (!(defer && kick_ops && resident_now(h))) { rc = velm_current(h, s); if (rc) return rc; }     // (every branch but the one that launches nothing reads velm)
     if (!defer && resident_now(h)) {
         // reference pass structure: kick, KE, chain, rescale (Cu :384-402) in one launch; velocities are final when it ends
         rc = run_resident(h, s, kick_ops ? 2 : 4); if (rc) return rc;
@@ -583,15 +646,19 @@ extern "C" tgnh_status tgnh_step_end(tgnh_handle h, void* stream) {
 
 // The split entry points work on stored velocities: a deferred half kick is materialised first.
 tgnh_status settle_kick(tgnh_handle h, hipStream_t s) {
-    return (h->owed.kick_pending || h->owed.end_pending) ? flush_impl(h, s) : TGNH_OK;
+    return (h->owed.kick_pending || h->owed.end_pending || h->owed.planes_live) ? flush_impl(h, s) : TGNH_OK;
 }
 
 // TGNH_FLAG_RESIDENT_STEP left the end half of the last step to the next tgnh_step_begin; somebody needs it now:
 // the classic launches (kick+KE without a velocity store, row sum [+ exchange], both chain halves pending)
+// Velocities that live in the library's planes go back to velm first -- here and nowhere else -- and the count towards the next
+// stay on them starts again.
 tgnh_status settle_end(tgnh_handle h, hipStream_t s) {
+    if (h->owed.planes_live || h->owed.end_pending) h->vp.streak = 0;
+    tgnh_status rc = leave_planes(h, s); if (rc) return rc;
     if (!h->owed.end_pending) return TGNH_OK;
     h->owed.end_pending = false;
-    tgnh_status rc = run_tile(h, OP_KICK | OP_KE | OP_NOSTORE, KID_KICK_KE, s); if (rc) return rc;
+    rc = run_tile(h, OP_KICK | OP_KE | OP_NOSTORE, KID_KICK_KE, s); if (rc) return rc;
     rc = run_chain(h, s, true); if (rc) return rc;
     h->owed.end_half_deferred(true);
     return TGNH_OK;
@@ -651,7 +718,7 @@ tgnh_status flush_impl(tgnh_handle h, hipStream_t s) {
 
 extern "C" tgnh_status tgnh_flush(tgnh_handle h, void* stream) {
     CHECK_H(h);
-    if (!h->owed.scale_pending && !h->owed.kick_pending && !h->owed.end_pending) return TGNH_OK;
+    if (!h->owed.scale_pending && !h->owed.kick_pending && !h->owed.end_pending && !h->owed.planes_live) return TGNH_OK;
     tgnh_status rc = entry(h, true); if (rc) return rc;
     return flush_impl(h, (hipStream_t)stream);
 }
@@ -686,5 +753,10 @@ extern "C" tgnh_status tgnh_state_changed(tgnh_handle h) {
     tgnh_status rc = deferred_guard(h, "tgnh_state_changed");
     if (rc) return rc;
     h->owed.ke_carry = false;              // TRUST_STATE_CHANGED: the next thermostat half step sums the kinetic energies again (Cu :474-488)
+    // Velocity planes live here means the call comes between tgnh_step_begin and tgnh_step_end (the guard has passed): what the
+    // caller is about to write -- positions, or velm after the flush the contract asks for -- must find velm current and stay.
+    // The call has no stream of its own: the one the planes were last written on.  velm's w may be rewritten too: checked again.
+    if (h->owed.planes_live) { HIP_OK(hipSetDevice(h->device)); rc = settle_end(h, h->vp.stream); if (rc) return rc; }
+    if (h->vp.verdict > 0) h->vp.verdict = 0;
     return TGNH_OK;
 }

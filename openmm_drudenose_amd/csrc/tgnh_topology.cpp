@@ -303,15 +303,21 @@ tgnh_status build_topology(tgnh_context* c, const tgnh_desc* d) {
     // tiles of identical molecules (PATTERN_WORDS, tgnh_internal.h)
     {
         std::map<std::vector<uint32_t>, uint32_t> ids, wids;
+        // mass != nullptr: the key is the P words AND the P descriptor masses behind them (the wave tiles: two tiles share a
+        // pattern only if their masses agree too -- a pattern then has ONE table of inverse masses, wpat_mass, for the one-launch
+        // step's velocity planes); known_only: an id is handed out only for a pattern some earlier tile has made
         auto intern = [&](std::map<std::vector<uint32_t>, uint32_t>& m, std::vector<uint32_t>& store, const uint32_t* w, int P,
-                          uint32_t limit, uint32_t* id) {
+                          uint32_t limit, uint32_t* id, const double* mass = nullptr, bool known_only = false) {
             std::vector<uint32_t> key(w, w + P);
+            if (mass) { key.resize(3 * (size_t)P); std::memcpy(key.data() + P, mass, sizeof(double) * P); }
             auto it = m.find(key);
             if (it == m.end()) {
-                if (m.size() >= limit) return false;
+                if (known_only || m.size() >= limit) return false;
                 it = m.emplace(key, (uint32_t)m.size()).first;
-                key.resize(PATTERN_WORDS, 0u);
-                store.insert(store.end(), key.begin(), key.end());
+                std::vector<uint32_t> words(w, w + P);
+                words.resize(PATTERN_WORDS, 0u);
+                store.insert(store.end(), words.begin(), words.end());
+                if (mass) { c->topo.wpat_mass.insert(c->topo.wpat_mass.end(), mass, mass + P); c->topo.wpat_mass.resize(store.size(), 0.0); }
             }
             *id = it->second;
             return true;
@@ -334,18 +340,25 @@ tgnh_status build_topology(tgnh_context* c, const tgnh_desc* d) {
                 break;
             }
         }
-        c->topo.wtile_pat.assign(std::max(c->topo.num_wtiles, 1), 0u); c->topo.wpattern.clear();
+        c->topo.wtile_pat.assign(std::max(c->topo.num_wtiles, 1), 0u); c->topo.wpattern.clear(); c->topo.wpat_mass.clear();
+        c->topo.wpat_all_uniform = c->topo.num_wtiles > 0;
         for (int t = 0; t < c->topo.num_wtiles; t++) {
             const int ws = c->topo.wave_tile[t].x, n = c->topo.wave_tile[t + 1].x - ws;
-            for (int P = 1; P <= PATTERN_WORDS && P < n; P++) {
+            // (P == n: a tile of one period -- the single molecule a box ends with -- takes the pattern the tiles before it made)
+            for (int P = 1; P <= PATTERN_WORDS && P <= n; P++) {
                 bool same = true;
                 for (int k = 0; k < n && same; k++) same = c->topo.wmeta[ws + k] == c->topo.wmeta[ws + k % P];
                 if (!same) continue;
                 uint32_t id;
-                if (intern(wids, c->topo.wpattern, c->topo.wmeta.data() + ws, P, 1u << 16, &id))
+                if (intern(wids, c->topo.wpattern, c->topo.wmeta.data() + ws, P, 1u << 16, &id, c->topo.mass.data() + ws, P == n)) {
                     c->topo.wtile_pat[t] = (uint32_t)P | (id << 8);
+                    // the words repeat with period P; do the masses?  (bit for bit: what the pattern's table of inverse masses stands for)
+                    for (int k = 0; k < n; k++)
+                        if (std::memcmp(&c->topo.mass[ws + k], &c->topo.wpat_mass[(size_t)id * PATTERN_WORDS + k % P], sizeof(double))) c->topo.wpat_all_uniform = false;
+                }
                 break;
             }
+            if (!c->topo.wtile_pat[t]) c->topo.wpat_all_uniform = false;
         }
         if (c->topo.pattern.empty()) c->topo.pattern.assign(PATTERN_WORDS, 0u);
         if (c->topo.wpattern.empty()) c->topo.wpattern.assign(PATTERN_WORDS, 0u);

@@ -11,16 +11,21 @@ namespace tgnh {
 // pattern comes by -- for a water box once per launch.  pat = period | pattern << 8, 0 = this tile's words are read from wmeta.
 struct PatternWord {
     uint32_t pat = 0u, word = 0u;
-    __device__ __forceinline__ bool of(const TileArgs& a, const uint32_t p, const int lane) {     // wavefront-uniform
+    // also(at): what else the lane keeps of its place `at` in the pattern tables, fetched when the word is
+    template <typename Also>
+    __device__ __forceinline__ bool of(const TileArgs& a, const uint32_t p, const int lane, Also&& also) {     // wavefront-uniform
         if ((p & 255u) == 0u) return false;
         if (p != pat) {
             const int period = (int)(p & 255u);
             const int q = (int)(((float)lane + 0.5f) * __builtin_amdgcn_rcpf((float)period));     // lane div period (never within rounding of an integer)
-            word = a.wpattern[(p >> 8) * PATTERN_WORDS + (uint32_t)(lane - q * period)];
+            const uint32_t at = (p >> 8) * PATTERN_WORDS + (uint32_t)(lane - q * period);
+            word = a.wpattern[at];
+            also(at);
             pat = p;
         }
         return true;
     }
+    __device__ __forceinline__ bool of(const TileArgs& a, const uint32_t p, const int lane) { return of(a, p, lane, [](uint32_t) {}); }
 };
 
 // wke_kernel's register image and load (two images in flight, forces only for a kicking pass: its budget of <= 102 VGPRs).
@@ -74,7 +79,10 @@ template <int PREC> struct WStepIn {
 // ---------------------------------------------------------------------------
 struct WaveBounds { int ws, y, n; };        // first slot; the tile's largest molecule | pattern word << 8; slots
 
-template <int PREC, int GB> struct WaveStep {
+// PLANES: the velocities are read from and stored to the library's x | y | z planes (TileArgs::vplanes) and a slot's 1/m comes with
+// its pattern word.  A template parameter, so that the velm form is compiled without a trace of the other (as a launch-uniform
+// branch in one kernel the planes' code cost the velm path 2.2 % of its steps/s).
+template <int PREC, int GB, bool PLANES = false> struct WaveStep {
     typedef typename Prec<PREC>::real real;
     typedef typename Prec<PREC>::mixed mixed;
     typedef typename Prec<PREC>::real4 real4;
@@ -84,6 +92,9 @@ template <int PREC, int GB> struct WaveStep {
     const double* s_scale;
     mixed *ix, *iy, *iz, *im, *jx, *jy, *jz;
     mixed4* __restrict__ velm; real4* __restrict__ posq; float4* __restrict__ pcorr;
+    // PLANES: x | y | z, and the lane's 1/m beside its pattern word
+    mixed* __restrict__ vpl;
+    mixed pinvm;
     int lane, G, nw;
     bool use_com, hardwall;
     mixed dt, fscale;
@@ -93,7 +104,7 @@ template <int PREC, int GB> struct WaveStep {
         : a(a_), e(e_), s_scale(s_scale_), ix(img), iy(img + WAVE_SLOTS), iz(img + 2 * WAVE_SLOTS), im(img + 3 * WAVE_SLOTS),
           jx(img + 4 * WAVE_SLOTS), jy(img + 5 * WAVE_SLOTS), jz(img + 6 * WAVE_SLOTS),
           velm(reinterpret_cast<mixed4*>(a_.velm)), posq(reinterpret_cast<real4*>(a_.posq)), pcorr(reinterpret_cast<float4*>(a_.posq_corr)),
-          lane(lane_), G(a_.num_groups), nw(a_.num_wtiles), use_com(a_.use_com != 0), hardwall(a_.hardwall != 0),
+          vpl(reinterpret_cast<mixed*>(a_.vplanes)), pinvm((mixed)0), lane(lane_), G(a_.num_groups), nw(a_.num_wtiles), use_com(a_.use_com != 0), hardwall(a_.hardwall != 0),
           dt((mixed)a_.dt), fscale((mixed)(0.5 * a_.dt / 4294967296.0)) {}     // Cu :295
     __device__ __forceinline__ static void wfence() {      // a wavefront's LDS operations are processed in order: only the compiler is held
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -106,12 +117,15 @@ template <int PREC, int GB> struct WaveStep {
     }
     __device__ __forceinline__ void load_vf(const WaveBounds& b, WStepIn<PREC>& in) {          // what pass 1 needs
         const int idx = b.ws + lane;
-        const bool patterned = pw.of(a, (uint32_t)b.y >> 8, lane);
+        const bool patterned = pw.of(a, (uint32_t)b.y >> 8, lane, [&](const uint32_t at) {
+            if (PLANES) pinvm = reinterpret_cast<const mixed*>(a.wpat_invm)[at];
+        });
         mixed4 v = mk4((mixed)0, (mixed)0, (mixed)0, (mixed)0);
         uint32_t meta = 64u << 10;
         long long fx = 0, fy = 0, fz = 0;
         if (lane < b.n) {
-            v = reinterpret_cast<const mixed4*>(a.velm)[idx];
+            if (PLANES) v = mk4(vpl[idx], vpl[idx + a.padded], vpl[idx + 2 * a.padded], pinvm);     // (w: the bits velm holds, checked on entry)
+            else v = reinterpret_cast<const mixed4*>(a.velm)[idx];
             if (!patterned) meta = a.wmeta[idx];
             fx = a.force[idx]; fy = a.force[idx + a.padded]; fz = a.force[idx + 2 * a.padded];
         }
@@ -264,7 +278,8 @@ template <int PREC, int GB> struct WaveStep {
         wfence();                                                        // the next tile's image comes after this tile's reads
         if (lane < bd.n) {
             const int idx = bd.ws + lane;
-            velm[idx] = v;
+            if (PLANES) { vpl[idx] = v.x; vpl[idx + a.padded] = v.y; vpl[idx + 2 * a.padded] = v.z; }
+            else velm[idx] = v;
             store_position<PREC>(posq, pcorr, idx, px, py, pz, pq);
         }
     }

@@ -208,8 +208,8 @@ __global__ __launch_bounds__(TBLOCK, TGNH_MINWAVES) void wke_kernel(const TileAr
 //   pass 2   the kick again, rescale, half kick, drift, hard wall   (Cu :351-376 ; K :249-301, :307-365, :435-466, :471-574)
 // ---------------------------------------------------------------------------
 
-template <int PREC, int GB, bool MULTI = false>
-__global__ __launch_bounds__(WBLOCK) void wstep_kernel(const TileArgs a) {
+template <int PREC, int GB, bool MULTI, bool PLANES>
+__device__ __forceinline__ void wstep_body(const TileArgs& a) {
     typedef typename Prec<PREC>::mixed mixed;
     static_assert(GB > 0, "register bins only");
     __shared__ double s_scale[MAX_GROUPS + 2];
@@ -228,14 +228,14 @@ __global__ __launch_bounds__(WBLOCK) void wstep_kernel(const TileArgs a) {
     TileEnv<PREC, GB> e;                                   // the kinetic-energy bins, in the shape ke_reduce takes them
     e.tid = tid; e.G = G; e.smem = nullptr; e.wbins0 = nullptr; e.s_scale = s_scale;
     e.clear_ke();
-    WaveStep<PREC, GB> ws(a, &e, s_scale, &s_img[wv][0][0], lane);    // the per-tile work (tgnh_wave_device.h)
+    WaveStep<PREC, GB, PLANES> ws(a, &e, s_scale, &s_img[wv][0][0], lane);    // the per-tile work (tgnh_wave_device.h)
     typedef WaveBounds Bounds;
     auto bounds = [&](const int ww, Bounds& b) { ws.bounds(ww, b); };
     auto load_vf = [&](const Bounds& b, WStepIn<PREC>& in) { ws.load_vf(b, in); };
     auto load_x = [&](const Bounds& b, WStepIn<PREC>& in) { ws.load_x(b, in); };
     auto prepare = [&](WStepIn<PREC>& t, const Bounds& bd, const bool ke) { ws.template prepare<true>(t, bd, ke); };
     auto finish = [&](WStepIn<PREC>& t, const Bounds& bd) { ws.finish(t, bd); };
-    auto wfence = [] { WaveStep<PREC, GB>::wfence(); };
+    auto wfence = [] { WaveStep<PREC, GB, PLANES>::wfence(); };
 
     // launch number, exchange number and the thermostat state: read before anything is handed in (step_kernel)
     unsigned gen0 = 0;
@@ -312,6 +312,14 @@ __global__ __launch_bounds__(WBLOCK) void wstep_kernel(const TileArgs a) {
     TRACE(15);
 }
 
+// The step with the velocities in velm, and the same step with them in the library's x | y | z planes (TileArgs::vplanes set: every
+// wave tile patterned, 1/m from wpat_invm).  Two kernels of one body: each is compiled without the other's loads and stores, and
+// wstep_kernel is the code it was before the planes existed.
+template <int PREC, int GB, bool MULTI = false>
+__global__ __launch_bounds__(WBLOCK) void wstep_kernel(const TileArgs a) { wstep_body<PREC, GB, MULTI, false>(a); }
+template <int PREC, int GB, bool MULTI = false>
+__global__ __launch_bounds__(WBLOCK) void wstep_planes_kernel(const TileArgs a) { wstep_body<PREC, GB, MULTI, true>(a); }
+
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
@@ -340,22 +348,31 @@ hipError_t launch_wke(int precision, int ops, int gb, const TileArgs& a, int gri
 }
 int wke_blocks_per_cu(int precision, int ops, int gb) { return blocks_per_cu(wke_fn(precision, ops, gb), TBLOCK, 0); }
 
-template <int PREC, bool MULTI> static tile_fn_t wstep_fn_gb(int gb) {
+template <int PREC, bool MULTI> static tile_fn_t wstep_fn_gb(int gb, bool planes) {
+    // (mixed and double only: in single precision the compiler packs the arithmetic of a float4 that is stored whole otherwise than
+    // that of three floats stored apart, and contracts it otherwise -- other bits than the velm form's)
+    // Neither a store of the three components as one value nor hiding from the compiler that 1/m is the same for every tile changed that.
+    if (planes && PREC == TGNH_PREC_SINGLE) return nullptr;
+    constexpr int PLANES_PREC = PREC == TGNH_PREC_SINGLE ? TGNH_PREC_MIXED : PREC;      // (no single-precision instantiation is made)
+    if (planes) return gb <= 1 ? wstep_planes_kernel<PLANES_PREC, 1, MULTI>
+                     : gb <= 4 ? wstep_planes_kernel<PLANES_PREC, 4, MULTI>
+                               : wstep_planes_kernel<PLANES_PREC, 8, MULTI>;
     return gb <= 1 ? wstep_kernel<PREC, 1, MULTI> : gb <= 4 ? wstep_kernel<PREC, 4, MULTI> : wstep_kernel<PREC, 8, MULTI>;
 }
-static tile_fn_t wstep_fn(int precision, int gb, bool multi) {
+static tile_fn_t wstep_fn(int precision, int gb, bool multi, bool planes) {
     if (gb == 0) return nullptr;
     return with_precision(precision, [&](auto P) -> tile_fn_t {
-        return multi ? wstep_fn_gb<decltype(P)::value, true>(gb) : wstep_fn_gb<decltype(P)::value, false>(gb);
+        return multi ? wstep_fn_gb<decltype(P)::value, true>(gb, planes) : wstep_fn_gb<decltype(P)::value, false>(gb, planes);
     });
 }
 hipError_t launch_wstep(int precision, int gb, bool multi, const TileArgs& a, int grid, hipStream_t s) {
-    tile_fn_t fn = wstep_fn(precision, gb, multi);
+    if (a.vplanes && !a.wpat_invm) return hipErrorInvalidValue;
+    tile_fn_t fn = wstep_fn(precision, gb, multi, a.vplanes != nullptr);
     if (!fn) return hipErrorInvalidValue;
     TGNH_LAUNCH(fn, dim3(grid), dim3(WBLOCK), 0, s, a);
     return hipGetLastError();
 }
-int wstep_blocks_per_cu(int precision, int gb, bool multi) { return blocks_per_cu(wstep_fn(precision, gb, multi), WBLOCK, 0); }
+int wstep_blocks_per_cu(int precision, int gb, bool multi, bool planes) { return blocks_per_cu(wstep_fn(precision, gb, multi, planes), WBLOCK, 0); }
 
 }  // namespace tgnh
 #endif

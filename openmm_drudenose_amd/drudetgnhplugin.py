@@ -1192,9 +1192,9 @@ class HipContext(_HandleQueries):
                     _check(self.lib.tgnh_run_harness(self.h, self._x0_arg(), self.k_drude, self.k_tether, int(steps), self._stream()))
             return g
         for _ in range(4):
-            owed_before = self.pending_state() & 0x2ff
+            owed_before = self.pending_state() & 0x6ff
             first = record()
-            if self.pending_state() & 0x2ff == owed_before:
+            if self.pending_state() & 0x6ff == owed_before:
                 break
             first.replay()                                   # a transition: taken for real (the recording has advanced the clock)
             torch.cuda.synchronize(self.dev)
@@ -1203,7 +1203,7 @@ class HipContext(_HandleQueries):
             raise TgnhError(_lib.ERR_STATE, "capture_steps: the handle does not reach a steady state of its step sequence")
         clock = self.time()
         graphs = [first, record()]
-        if self.pending_state() & 0x2ff != owed_before:
+        if self.pending_state() & 0x6ff != owed_before:
             raise TgnhError(_lib.ERR_STATE, "capture_steps: the step sequence is not periodic")
         # a capture advances the host-side clock without running anything: the first one stands for the first replay,
         # the second one is taken back
@@ -1212,7 +1212,14 @@ class HipContext(_HandleQueries):
         turn = [0]
         baths = self._bath_epoch
 
+        planes = owed_before & 0x400
+
         def replay():
+            # the launches of a recording read the velocities where they lived when it was made (bit 10: the one-launch step's own
+            # planes, or velm): a query or a flush since has moved them, and a replay would step from stale ones
+            if (self.pending_state() ^ planes) & 0x400:
+                raise TgnhError(_lib.ERR_STATE, "capture_steps: the velocities no longer live where these steps were recorded "
+                                "(a flush or a query moved them between the library's planes and velm): capture them again")
             if self._bath_epoch != baths:
                 raise TgnhError(_lib.ERR_STATE, "capture_steps: the temperatures were changed after these steps were recorded "
                                 "(their launches hold the old kT): capture them again")
@@ -1232,6 +1239,13 @@ class HipContext(_HandleQueries):
         bits = C.c_uint32()
         _check(self.lib.tgnh_get_pending_state(self.h, C.byref(bits)))
         return bits.value
+
+    def velocity_planes(self):
+        """tgnh_get_velocity_planes: (live, usable, one-launch steps in a row since the last settle, the threshold) -- whether the
+        one-launch step keeps the velocities in its own x | y | z planes right now, and whether this handle ever can."""
+        out = (C.c_int32 * 4)()
+        _check(self.lib.tgnh_get_velocity_planes(self.h, out))
+        return bool(out[0]), bool(out[1]), int(out[2]), int(out[3])
 
     def status_flags(self):
         """The device's status word (bit 0 Drude beyond 2x the hard wall, bit 1 harness SHAKE not converged or the direct solver's result outside the tolerance, bit 2 mailbox

@@ -5,6 +5,7 @@
 #include "../../openmm_drudenose_amd/csrc/tgnh_scale_positions.h"
 #include "../../openmm_drudenose_amd/csrc/tgnh_wrap.h"
 #include "../../openmm_drudenose_amd/csrc/tgnh_minimize.h"
+#include "../../openmm_drudenose_amd/csrc/tgnh_vplanes.h"
 
 namespace tgnh {
 hipError_t launch_tile(int, int, int, const TileArgs&, int, size_t, hipStream_t) { return hipErrorNoDevice; }
@@ -13,7 +14,7 @@ hipError_t launch_step(int, int, int, const TileArgs&, int, size_t, hipStream_t)
 int step_blocks_per_cu(int, int, int, size_t) { return 2; }
 int step_kind_ops2(int) { return 0; }
 hipError_t launch_wstep(int, int, bool, const TileArgs&, int, hipStream_t) { return hipErrorNoDevice; }
-int wstep_blocks_per_cu(int, int, bool) { return 2; }
+int wstep_blocks_per_cu(int, int, bool, bool) { return 2; }
 hipError_t launch_wke(int, int, int, const TileArgs&, int, hipStream_t) { return hipErrorNoDevice; }
 int wke_blocks_per_cu(int, int, int) { return 5; }
 hipError_t launch_chain(const ChainArgs&, hipStream_t) { return hipErrorNoDevice; }
@@ -27,6 +28,8 @@ hipError_t launch_cm_momentum(int, const void*, int, CmRow*, int, hipStream_t) {
 hipError_t launch_cm_shift(int, void*, int, const double*, const double*, int, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_rescale_put(double*, const double*, int, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_rescale_factors(const double*, const double*, int, double*, uint32_t*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_velm_to_planes(int, const void*, void*, const int2*, int, const void*, int, uint32_t*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_planes_to_velm(int, const void*, void*, int, int, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_scale_positions_spans(int, const ScalePosArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_scale_positions_table(int, const ScalePosArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_wrap_spans(int, const WrapArgs&, hipStream_t) { return hipErrorNoDevice; }
