@@ -204,7 +204,9 @@ tgnh_status tgnh_rccl_shutdown(tgnh_handle h);
  * share it, or their launches wait for each other's work-groups until the meeting times out (status bit 3). */
 tgnh_status tgnh_set_resident_share(tgnh_handle h, int share);
 /* Work-groups of the resident step kernel per compute unit that tgnh_create found resident together (a census launch checks
- * the occupancy query); 0 = the handle steps the DEFER_SCALE way (flag not set, or nothing passed the census). */
+ * the occupancy query); 0 = the handle steps the DEFER_SCALE way (flag not set, or nothing passed the census).  The count is
+ * that of the kernel tgnh_get_resident_kernel names (a handle may have one for step_kernel and a smaller one for wstep_kernel):
+ * the one-launch step's grid is min(work to hand out, this count x compute units / resident share). */
 tgnh_status tgnh_get_resident_work_groups(tgnh_handle h, int* per_compute_unit);
 /* How this handle steps: *gather = 0 the tiled kernels (every Drude partner and molecular centre of mass an on-chip look-up inside
  * a tile of <= 512 consecutive slots, <= 32 temperature groups), 1 the GATHER path -- the reference's own un-fused kernels by
@@ -776,7 +778,11 @@ tgnh_status tgnh_set_thermostat_state(tgnh_handle h, int which, void* stream, co
  * (one more than tiles; none: a molecule or pair longer than a wavefront), 10 the wave tiles' per-slot words,
  * 11 per 512-slot tile: period | molecules per period << 8 | pattern << 16, 12 per wave tile: period | pattern << 8, where
  * the tile repeats one kind of molecule (or a few) and its kernels form the per-slot words from a pattern instead of
- * reading them (0: they read them), 13 / 14 the patterns of the two, 64 words each. */
+ * reading them (0: they read them), 13 / 14 the patterns of the two, 64 words each, 15 the descriptor masses behind the
+ * wave patterns' words, 64 doubles per pattern in 14's order, each as two int32 (a wave pattern is interned by words AND
+ * masses; empty where 14 holds its one placeholder row), 16 one word: 1 where every wave tile is patterned and every slot's
+ * mass is its pattern entry's bit for bit -- the host's half of what qualifies a handle for the velocity planes --, else 0.
+ * All read-only, all answered by a host-only handle. */
 tgnh_status tgnh_get_topology_len(tgnh_handle h, int which, int* len);
 tgnh_status tgnh_get_topology(tgnh_handle h, int which, int32_t* out);
 /* The sizes the launches of this handle are bound by, against the sizes of what the library allocated for them (inspection;

@@ -247,7 +247,11 @@ extern "C" tgnh_status tgnh_rccl_shutdown(tgnh_handle h) {
 extern "C" tgnh_status tgnh_get_resident_work_groups(tgnh_handle h, int* per_compute_unit) {
     CHECK_H(h);
     if (!per_compute_unit) return fail(TGNH_ERR_ARG, "null out");
-    *per_compute_unit = resident_now(h) ? std::max(h->cfg.resident_per_cu, h->cfg.wresident_per_cu) : 0;
+    // of the kernel tgnh_get_resident_kernel names: with tgnh_set_resident_share and the compute units it says which grid steps
+    // (wstep_kernel's count is the smaller of the two where a handle has both)
+    int which = 0;
+    tgnh_status rc = tgnh_get_resident_kernel(h, &which); if (rc) return rc;
+    *per_compute_unit = which == 2 ? h->cfg.wresident_per_cu : which == 1 ? h->cfg.resident_per_cu : 0;
     return TGNH_OK;
 }
 

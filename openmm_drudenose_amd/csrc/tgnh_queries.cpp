@@ -124,6 +124,8 @@ extern "C" tgnh_status tgnh_get_topology_len(tgnh_handle h, int which, int* len)
     if (which == 12) { *len = (int)h->topo.wtile_pat.size(); return TGNH_OK; }       // per wave tile: period | pattern << 8
     if (which == 13) { *len = (int)h->topo.pattern.size(); return TGNH_OK; }         // the patterns, 64 words each
     if (which == 14) { *len = (int)h->topo.wpattern.size(); return TGNH_OK; }
+    if (which == 15) { *len = 2 * (int)h->topo.wpat_mass.size(); return TGNH_OK; }  // the wave patterns' descriptor masses, 64 doubles each, as pairs of words
+    if (which == 16) { *len = 1; return TGNH_OK; }                                   // wpat_all_uniform: every wave tile patterned, every mass its pattern entry's
     const std::vector<int>* v = topo_vec(h, which);
     if (!v) return fail(TGNH_ERR_ARG, "bad topology array id");
     *len = (int)v->size();
@@ -140,6 +142,8 @@ extern "C" tgnh_status tgnh_get_topology(tgnh_handle h, int which, int32_t* out)
     if (which == 12) return put(h->topo.wtile_pat.data(), sizeof(uint32_t) * h->topo.wtile_pat.size());
     if (which == 13) return put(h->topo.pattern.data(), sizeof(uint32_t) * h->topo.pattern.size());
     if (which == 14) return put(h->topo.wpattern.data(), sizeof(uint32_t) * h->topo.wpattern.size());
+    if (which == 15) return put(h->topo.wpat_mass.data(), sizeof(double) * h->topo.wpat_mass.size());
+    if (which == 16) { *out = h->topo.wpat_all_uniform ? 1 : 0; return TGNH_OK; }
     const std::vector<int>* v = topo_vec(h, which);
     if (!v) return fail(TGNH_ERR_ARG, "bad topology array id");
     std::copy(v->begin(), v->end(), out);

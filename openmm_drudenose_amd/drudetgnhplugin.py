@@ -711,7 +711,8 @@ class HipContext(_HandleQueries):
         _check(self.lib.tgnh_set_resident_share(self.h, int(share)))
 
     def resident_work_groups(self):
-        """Work-groups of step_kernel per compute unit found resident together at create (0: the deferred launches run)."""
+        """Work-groups per compute unit found resident together at create, of the kernel resident_kernel() names (0: the deferred
+        launches run)."""
         n = C.c_int()
         _check(self.lib.tgnh_get_resident_work_groups(self.h, C.byref(n)))
         return n.value
@@ -811,6 +812,19 @@ class HipContext(_HandleQueries):
     def setVelocities(self, vel):
         self._state_changed()                                # (first: refused between the steps of a deferred sequence, and then nothing is written)
         self.velm[:, :3] = self.torch.from_numpy(np.ascontiguousarray(vel, np.float64)).to(self.dev, self.mdt)
+
+    def rebind_velocities(self, velm):
+        """tgnh_bind_buffers with another velm array (same shape, type and device) and every other array as bound; the context
+        steps on it from here on.  Refused (TGNH_ERR_STATE) while a deferred half kick is pending: flush first, or call it between
+        step_begin and step_end.  The array that goes holds the current velocities when the call returns; what the new one holds
+        is the caller's business (its w must be 1/m)."""
+        if velm.shape != self.velm.shape or velm.dtype != self.velm.dtype or velm.device != self.velm.device or not velm.is_contiguous():
+            raise TgnhError(_lib.ERR_ARG, "rebind_velocities: a contiguous array of velm's shape, type and device")
+        _check(self.lib.tgnh_bind_buffers(self.h, self.posq.data_ptr(),
+                                          self.posq_corr.data_ptr() if self.posq_corr is not None else None,
+                                          velm.data_ptr(), self.force.data_ptr(), self.pos_delta.data_ptr()))
+        old, self.velm = self.velm, velm
+        return old
 
     # ---- centre-of-mass motion (include/drude_tgnh.h: tgnh_get_momentum, tgnh_remove_cm_motion, ...) ----
     def momentum(self):

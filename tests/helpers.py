@@ -148,6 +148,52 @@ def random_clusters(rng, mass, pd, pp, sizes, first, pos):
     return np.array(atoms, np.int32).reshape(-1, 4), np.array(dist, np.float64).reshape(-1, 6)
 
 
+# ---- water boxes with more than one wave pattern (tests/test_host_logic.py, tests/test_velocity_planes_gpu.py) ----
+def water_variants(n, group_of=None, heavy_of=None):
+    """synth.water_box(n) with temperature groups dealt per molecule and some molecules' hydrogens made heavy: group_of and heavy_of
+    take the array of molecule indices 0 .. n - 1 and return a group (0 .. G - 1, every one of them used) resp. a truth value per
+    molecule; the two H masses are 2.0 where heavy_of holds, set before the velocities are drawn (they are thermal for the masses
+    the box really has).  With neither it IS synth.water_box(n): same seed, same draws.  -> (DrudeSystem, group[N], G)"""
+    rng = np.random.default_rng(synth.SEED)
+    mass, pd, pp, resid, pos = synth._molecules(n, synth._W_TEST, 0.31)
+    m = np.arange(n)
+    g = np.zeros(n, np.int64) if group_of is None else np.asarray(group_of(m), np.int64)
+    ng = int(g.max()) + 1
+    assert g.shape == (n,) and g.min() >= 0 and len(np.unique(g)) == ng
+    if heavy_of is not None:
+        heavy = np.asarray(heavy_of(m), bool)
+        mass.reshape(n, 5)[heavy, 2:4] = 2.0               # slots 2, 3: H1, H2 (synth._W_TEST)
+    out = synth._finish(mass, pd, pp, resid, pos, np.repeat(g, 5).astype(np.int32), ng, rng, 300.0, 1.0, f"swm4-{n}-variant")
+    out[0].lattice = (5, int(np.ceil(n ** (1.0 / 3.0) - 1e-9)), 0.31, np.asarray(synth._W_TEST["geom"], np.float64), 0)   # (synth.water_box)
+    return out
+
+
+# The rows of the wave-pattern table (DESIGN.md 3.1): name -> (group_of, heavy_of, what the row is).  A wave tile of these boxes
+# holds 12 molecules = 60 slots; the groups of `mod k` repeat after k molecules = 5 k slots.
+def _mod(k):
+    return lambda m: m % k
+
+
+WATER_ROWS = {
+    "mod2": (_mod(2), None), "mod3": (_mod(3), None), "mod4": (_mod(4), None), "mod5": (_mod(5), None), "mod6": (_mod(6), None),
+    "mod8": (_mod(8), None),
+    "group-per-tile": (lambda m: (m // 12) % 4, None),
+    "group-per-tile3": (lambda m: (m // 12) % 3, None),
+    "heavy-tiles": (None, lambda m: (m // 12) % 2 == 1),           # equal words, other masses: a pattern id of their own
+    "heavy-every-third-tile": (None, lambda m: (m // 12) % 3 == 1),
+    "heavy-odd": (None, lambda m: m % 2 == 1),                     # the words repeat after 5 slots, the masses after 10
+    "plain": (None, None),
+}
+_WATER_VARIANTS = {}
+
+
+def water_row(name, n):
+    """water_variants of a row of WATER_ROWS, built once per (row, n) and shared: nobody writes to what this returns"""
+    if (name, n) not in _WATER_VARIANTS:
+        _WATER_VARIANTS[name, n] = water_variants(n, *WATER_ROWS[name])
+    return _WATER_VARIANTS[name, n]
+
+
 # ---- topologies the tiled kernels cannot hold: they step on the gather path (tgnh_gather.hip; tests/test_gather_gpu.py) ----
 def drudes_at_the_end(n_mol, seed=3):
     """A water box as some builders write it: all atoms first (O, H, H, M per molecule), all Drude particles appended behind them.

@@ -459,3 +459,83 @@ def test_random_topologies_tile_and_count_like_the_oracle(seed):
     assert np.array_equal(((meta >> 2) & 255).astype(np.int32), group)
     assert np.array_equal(np.flatnonzero((meta & 3) == 1), np.sort(s.pair_drude))
     assert np.bincount(tile_of, minlength=len(ts) - 1).max() <= 512
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Wave patterns, their masses and the host's half of what qualifies a handle for the velocity planes: topology
+# queries 12, 14, 15, 16 on water boxes whose groups or hydrogen masses vary from molecule to molecule (helpers.WATER_ROWS).
+# A wave tile of these boxes is 12 molecules = 60 slots; the t-th full tile starts at molecule 12 t.
+# ---------------------------------------------------------------------------------------------------------------------
+def _phases(k, n):
+    """groups m % k: a tile's words are those of its first molecule's phase 12 t mod k -> the distinct phases of the full tiles"""
+    return len({(12 * t) % k for t in range(n // 12)})
+
+
+def _wave_pattern_cases():
+    """(row, n, periods, pattern ids, unpatterned tiles, query 16)"""
+    out = []
+    for k in (2, 3, 4):                                      # the period divides the tile: every tile starts in phase 0
+        out += [(f"mod{k}", n, {5 * k}, 1, 0, 1) for n in (48, 60, 1001)]
+    out += [("mod5", n, {25}, 5, 0, 1) for n in (60, 1001)]  # (1001: the last tile, 5 molecules, is ONE period: it takes the id an earlier tile made)
+    out += [("mod8", n, {40}, 2, 0, 1) for n in (48, 60)]
+    out += [("group-per-tile", n, {5}, 4, 0, 1) for n in (48, 49, 61, 1001)]
+    out += [("heavy-tiles", n, {5}, 2, 0, 1) for n in (48, 49, 1001)]
+    out += [("heavy-odd", n, {5}, 1, 0, 0) for n in (48, 49, 1001)]       # the words repeat after 5 slots, the masses after 10
+    # a last tile shorter than one period -- the single molecule these boxes end with -- has no pattern: the box stays on velm
+    out += [(f"mod{k}", n, {0, 5 * k}, _phases(k, n), 1, 0) for k in (2, 3, 4, 5, 6, 8) for n in (49, 61)]
+    out += [("mod6", 1001, {0, 30}, 1, 1, 0), ("mod8", 1001, {0, 40}, 2, 1, 0)]      # (the last tile: 5 molecules = 25 slots)
+    return out
+
+
+@pytest.mark.parametrize("com", [True, False])
+@pytest.mark.parametrize("row,n,periods,ids,unpatterned,uniform", _wave_pattern_cases())
+def test_wave_patterns_are_interned_by_words_and_masses(row, n, periods, ids, unpatterned, uniform, com):
+    from helpers import water_row
+    s, g, ng = water_row(row, n)
+    it = DrudeTGNHIntegrator(300.0, 0.1, 1.0, 0.005, 0.001, 20, 1, True, com)
+    for _ in range(ng):
+        it.addTempGroup()
+    it._particleTempGroup = np.ascontiguousarray(g, np.int32)
+    t = HostTopology(s, it, mode="TGNH")
+    wt = t.topology(9).reshape(-1, 2)
+    assert np.all(np.diff(wt[:, 0])[:-1] == 60) and len(wt) - 1 == (n + 11) // 12
+    wmeta, wpat = t.topology(10).view(np.uint32), t.topology(12).view(np.uint32)
+    wwords = t.topology(14).view(np.uint32).reshape(-1, 64)
+    wmass = t.topology(15).view(np.float64).reshape(-1, 64)
+    q16 = t.topology(16)
+    assert q16.shape == (1,) and int(q16[0]) == uniform
+    assert len(wpat) == len(wt) - 1 and wmass.shape == wwords.shape
+    P, pid = (wpat & 255).astype(np.int64), (wpat >> 8).astype(np.int64)
+    assert set(P.tolist()) == periods and len(set(pid[P > 0].tolist())) == ids == len(wwords) and int((P == 0).sum()) == unpatterned
+    masses_reproduced, seen = True, {}
+    for k in np.flatnonzero(P > 0):
+        ws, m = int(wt[k, 0]), int(wt[k + 1, 0] - wt[k, 0])
+        at = np.arange(m) % P[k]
+        assert np.array_equal(wwords[pid[k]][at], wmeta[ws:ws + m]), (row, n, k)
+        assert np.all(wwords[pid[k]][P[k]:] == 0) and np.all(wmass[pid[k]][P[k]:] == 0)
+        masses_reproduced &= wmass[pid[k]][at].tobytes() == s.mass[ws:ws + m].tobytes()       # bit for bit
+        # one id per (words, masses) of a period: equal words with other masses must not share a table of inverse masses
+        key = (int(P[k]), wmeta[ws:ws + P[k]].tobytes())
+        assert seen.setdefault(key, {}).setdefault(s.mass[ws:ws + P[k]].tobytes(), int(pid[k])) == pid[k], (row, n, k)
+    assert all(len(set(v.values())) == len(v) for v in seen.values())
+    assert bool(uniform) == (masses_reproduced and unpatterned == 0)
+    assert masses_reproduced == (row != "heavy-odd")
+    if row == "heavy-tiles":                                 # ... and that case occurs: light and heavy tiles, word for word the same
+        assert [len(v) for v in seen.values()] == [2]
+    t.close()
+
+
+def test_the_kernels_place_in_a_pattern_is_lane_mod_period():
+    """PatternWord::of (tgnh_wave_device.h) takes a lane's table entry at lane - q * period with q = int((lane + 0.5f) * rcp(period)),
+    "never within rounding of an integer"; the entry check of velm_to_planes_kernel takes it at lane % period.  Restated in float32
+    for every lane and every period a pattern can have, with the reciprocal correctly rounded and one unit in the last place off
+    either way -- v_rcp_f32's error bound: the two are the same place."""
+    lane = np.arange(64, dtype=np.int64)
+    half = lane.astype(np.float32) + np.float32(0.5)
+    for period in range(1, 65):
+        exact = np.float32(1.0) / np.float32(period)
+        for rcp in (np.nextafter(exact, np.float32(0.0)), exact, np.nextafter(exact, np.float32(2.0))):
+            prod = half * rcp
+            assert prod.dtype == np.float32
+            q = prod.astype(np.int64)                        # (the cast truncates, as the kernel's does)
+            assert np.array_equal(lane - q * period, lane % period), (period, float(rcp))

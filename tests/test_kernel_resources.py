@@ -46,6 +46,14 @@ def test_hot_kernels_keep_their_occupancy():
             w = rows[f"wstep_kernel<{prec},{gb},false>"]
             assert w[2] == 4 and 2 * w[5] <= 160 * 1024, w
             assert rows[f"wstep_kernel<{prec},{gb},true>"][2] == 2
+            # the same step on the velocity planes (mixed and double): tgnh_create hands the planes out only where
+            # wstep_planes_kernel holds as many work-groups per compute unit as wstep_kernel does (allocate_velocity_planes), so a
+            # few registers more here turn the planes off for every handle -- with equal results, which no other test would see
+            if prec in (1, 2):
+                p, pm = rows[f"wstep_planes_kernel<{prec},{gb},false>"], rows[f"wstep_planes_kernel<{prec},{gb},true>"]
+                assert p[0] <= 128 and p[2] == 4 and 2 * p[5] <= 160 * 1024, (prec, gb, p)
+                assert pm[0] <= 256 and pm[2] == 2, (prec, gb, pm)
+                assert p[2] >= w[2] and pm[2] >= rows[f"wstep_kernel<{prec},{gb},true>"][2], (prec, gb, p, pm)
             for ops in (8, 10, 138):
                 k = rows[f"wke_kernel<{prec},{ops},{gb}>"]
                 assert k[2] >= 5 and k[2] * k[5] <= 160 * 1024, k      # (4 wavefronts per work-group: occupancy = work-groups per CU)
