@@ -928,6 +928,79 @@ tgnh_status tgnh_get_num_virtual_sites(tgnh_handle h, int* count);
 tgnh_status tgnh_compute_virtual_sites(tgnh_handle h, void* stream);                             /* where Cu :377 calls out */
 tgnh_status tgnh_distribute_virtual_site_forces(tgnh_handle h, void* force, void* stream);       /* right after the force call-out */
 
+/* THE LIBRARY'S OWN DRUDEFORCE, for a host that has no OpenMM behind it (inside OpenMM the System's DrudeForce keeps acting, and the
+ * glue calls none of this): the springs that hold the Drude particles, their anisotropy, the Thole-screened pairs and the energy, on
+ * the device.  It stands beside the harness forces (tgnh_harness_force: a bench workload with a tether; tgnh_harness_water_force:
+ * testWater's one isotropic spring per molecule) and replaces neither.  Coulomb and Lennard-Jones forces are not here.
+ *
+ * tgnh_set_drude_force: OpenMM's DrudeForce::addParticle / addScreenedPair as a table.  particles [n][5] = (p, p1, p2, p3, p4) slots
+ * of the bound arrays, -1 = none for p2..p4; params [n][4] = (charge e, polarizability nm^3, aniso12, aniso34); screened
+ * [num_screened][2] = rows (i, j) of that table; thole [num_screened].  ROW k NAMES THE DESCRIPTOR'S PAIR k: p == pair_drude[k],
+ * p1 == pair_parent[k] and n == num_pairs (tgnh_desc takes the pairs "in DrudeForce order" for this).  The table replaces the one set
+ * before; n = 0 clears it.  The arrays are read before the call returns.  Every check runs before any device work, so a host-only
+ * handle gives the same answers and the same counts (tgnh_get_num_drude_force_terms).  Not inside a stream capture: the table, its
+ * inverse and the energy's scratch are uploaded and allocated here, synchronously, and never later.
+ * The constants are formed on the host, once, in fp64, with C = ONE_4PI_EPS0 = 138.935456 kJ nm / (mol e^2):
+ *   a1 = aniso12 if p2 != -1, else 1;   a2 = aniso34 if p3 != -1 and p4 != -1, else 1;   a3 = 3 - a1 - a2
+ *   k3 = C q^2 / (alpha a3);   k1 = C q^2 / (alpha a1) - k3;   k2 = C q^2 / (alpha a2) - k3     (k1, k2: 0 where the row has no such axis)
+ *   per screened pair:  a = thole / (alpha_i alpha_j)^(1/6),   K = C q_i q_j
+ * (This mapping from polarizability and aniso values to k1, k2, k3 is believed to be OpenMM's; OpenMM was not at hand to check
+ * against.  The reference embeds DrudeForce's two kernels with k1, k2, k3 handed in -- the per-term forms below are theirs -- and its
+ * testWater uses the isotropic case only, k3 = C q^2 / alpha.)
+ * TGNH_ERR_ARG, the row's or the pair's number in tgnh_last_error(): n neither 0 nor num_pairs, a NULL array, num_screened < 0; a
+ * row that does not name its pair; an index out of range; p2 equal to p or p1, p3 == p4, exactly one of p3 and p4 equal to -1; a
+ * charge that is not finite; a polarizability that is not finite or <= 0; an aniso value (of those the row reads) that is not
+ * finite or <= 0, or a3 <= 0; a screened pair that names a row out of range, one row twice, or a pair of rows listed before, in
+ * either order; a thole that is negative or not finite.  A refused table leaves the one in force as it was, and so does a table whose
+ * upload fails (TGNH_ERR_HIP): the new one is built aside and replaces the old one only when it is complete.
+ *
+ * tgnh_compute_drude_force(force, want_energy).  Everything in fp64 in every precision.  A position x(i) is posq, + posq_correction
+ * in mixed precision, as tgnh_get_drude_statistics defines it.  Charges come from the table, never from posq.w.  The terms:
+ *   per row, delta = x(p) - x(p1):
+ *     the isotropic spring          t = k3 delta;   p: -t,  p1: +t;   E = 1/2 k3 |delta|^2
+ *     the first axis (p2 != -1)     d = x(p1) - x(p2), e = d / |d|, s = e . delta, f1 = (k1 s) e, f2 = (k1 s / |d|)(delta - s e);
+ *                                   p: -f1,  p1: f1 - f2,  p2: f2;   E = 1/2 k1 s^2
+ *     the second axis (p3, p4)      d = x(p3) - x(p4), the same e, s, f1, f2 with k2;   p: -f1,  p1: +f1,  p3: -f2,  p4: +f2;   E = 1/2 k2 s^2
+ *   per screened pair of rows (i, j) its four site pairs (first in {p_i, p1_i}, second in {p_j, p1_j}), each a term of its own,
+ *   sigma = +1 for Drude-Drude and parent-parent, -1 for the two mixed ones; delta = x(first) - x(second), r = |delta|, u = a r,
+ *   S = 1 - (1 + u/2) exp(-u):
+ *     E = sigma K S / r;   first: delta sigma K (S / r - 1/2 (1 + u) exp(-u) a) / r^2,   second: its negative
+ * Each component of each particle's share of each term is converted on its own, llrint(c * 4294967296.0), and added to the particle's
+ * entry as an integer (tgnh_distribute_virtual_site_forces' rule): the result is a function of the inputs alone -- not of grid,
+ * order, device or step path -- and no atomic operation touches the buffer.  The isotropic shares are formed without fused
+ * multiply-add, every operation rounded on its own as written: bit for bit what a numpy restatement gives.  sqrt, exp and the
+ * divisions are the IEEE ones.  A thole of 0 gives S = 0 and shares of exactly 0.
+ * `force` is int64 [3*padded] fixed point x 2^32, planes x|y|z -- normally the bound buffer.  The call ADDS: two calls add twice.
+ * Padding and slots in no term are neither read nor written; positions, velm and posDelta are only read or not touched at all.
+ * A pair at r = 0 or an axis of length 0 stores the non-finite numbers it produces; there is no status bit for it.
+ * One launch on `stream` (one lane per receiving slot over the table inverted at set time; a term is recomputed by every particle
+ * that receives from it), none with an empty table (TGNH_OK).  It does not synchronise and can be captured into a hipGraph.  It is
+ * not a tgnh_state_changed, and may run at any time with respect to kicks a step still owes (tgnh_get_pending_state), as the site
+ * calls may: it reads positions, and only velm ever lags.  TGNH_ERR_STATE: a host-only handle, buffers not bound, force is NULL.
+ * Follows tgnh_get_status_flags' rule for sticky failures.
+ *
+ * THE ENERGY.  want_energy != 0: the same launch also leaves a row of partial sums {springs, screened pairs} per work-group, in
+ * scratch allocated at set time.  tgnh_get_drude_energy enqueues the one-work-group sum of the rows, synchronises `stream` and
+ * returns out[0] = the springs' energy (isotropic and both axes), out[1] = the screened pairs', kJ/mol.  Each term is counted by
+ * exactly one lane: a row by the lane of its p, a screened pair (its four site pairs, added in the order Drude_i-Drude_j,
+ * Drude_i-parent_j, parent_i-Drude_j, parent_i-parent_j) by the lane of row i's p.  No floating-point atomic; the grid is a function
+ * of the number of receiving slots alone and every order of additions is fixed by it, so the same positions give the same bits from
+ * any handle over the same slots and the same table, tiled or TGNH_FLAG_GATHER, TGNH or DUALNH, asked once or twice.
+ * TGNH_ERR_STATE: no tgnh_compute_drude_force with want_energy since the table was set -- a launch that was only RECORDED into a
+ * stream capture does not count (nothing has run; the replayed graph fills the rows, and an eager want_energy launch before or after
+ * the capture opens the query) --; a host-only handle, buffers not bound.
+ * TGNH_ERR_ARG: out is NULL.
+ * SHARDED RUNS: shards are whole molecules; every rank hands over the rows of its own pairs with local indices, and a
+ * term that names a particle outside the shard is refused by the index check.  Nothing is exchanged: the forces are local and the
+ * two energies are additive over ranks. */
+tgnh_status tgnh_set_drude_force(tgnh_handle h, int n, const int32_t* particles /* [n][5]: p, p1, p2, p3, p4; -1 = none for p2..p4 */,
+                                 const double* params /* [n][4]: charge, polarizability, aniso12, aniso34 */,
+                                 int num_screened, const int32_t* screened /* [num_screened][2]: rows of the table above */,
+                                 const double* thole /* [num_screened] */);
+tgnh_status tgnh_get_num_drude_force_terms(tgnh_handle h, int* rows, int* screened_pairs);
+tgnh_status tgnh_compute_drude_force(tgnh_handle h, void* force, int want_energy, void* stream);    /* in the force call-out */
+tgnh_status tgnh_get_drude_energy(tgnh_handle h, void* stream, double out[2] /* springs, screened pairs */);   /* synchronises */
+
 /* The call-outs of the reference's own testWater (platforms/reference/tests/TestReferenceDrudeTGNHIntegrator.cpp:111-166),
  * harness only: its force field -- NonbondedForce with reaction field, cutoff `cutoff` in a cubic box of edge `box`, +
  * DrudeForce + the M site's force spread over O, H1, H2, for slots laid out O, D, H1, H2, M per molecule -- written into

@@ -21,7 +21,11 @@ template <typename T> class DeviceBuf {
     bool pinned_ = false;
 public:
     DeviceBuf() = default;
-    DeviceBuf(DeviceBuf&& o) noexcept : p_(o.p_), pinned_(o.pinned_) { o.p_ = nullptr; }      // (move-only: no copies, no assignment)
+    DeviceBuf(DeviceBuf&& o) noexcept : p_(o.p_), pinned_(o.pinned_) { o.p_ = nullptr; }      // (move-only: no copies)
+    DeviceBuf& operator=(DeviceBuf&& o) noexcept {           // what it held is released: a table built aside replaces the one in force
+        if (this != &o) { reset(); p_ = o.p_; pinned_ = o.pinned_; o.p_ = nullptr; }
+        return *this;
+    }
     ~DeviceBuf() { reset(); }
     void reset() { if (p_) (void)(pinned_ ? hipHostFree(p_) : hipFree(p_)); p_ = nullptr; }
     // n elements; ext_flags != 0: hipExtMallocWithFlags (TGNH_MEETING_MEM, hipDeviceMallocUncached)
@@ -172,6 +176,24 @@ struct tgnh_context {
         tgnh::DeviceBuf<unsigned char> d_recv_role;                    // [entries]
         void drop() { count = receivers = 0; d_atoms.reset(); d_kind.reset(); d_params.reset(); d_recv_slot.reset(); d_recv_start.reset(); d_recv_row.reset(); d_recv_role.reset(); }
     } vsites;
+    struct DrudeForce {               // tgnh_set_drude_force (tgnh_drude_force.cpp): the rows in the descriptor's pair order, the screened pairs, the inverse
+        int rows = 0, screened = 0;       // terms in force (a host-only handle keeps the counts and nothing else)
+        int receivers = 0;                // slots that receive a share of some term
+        bool energy_launched = false;     // a want_energy launch has filled d_energy's rows since the table was set
+        tgnh::DeviceBuf<int4> d_atoms;    // [rows] (p, p1, p2, p3), uploaded at set time, never inside a capture
+        tgnh::DeviceBuf<int> d_p4;        // [rows]
+        tgnh::DeviceBuf<double> d_k;      // [3][rows] k1, k2, k3
+        tgnh::DeviceBuf<int2> d_pair_rows;        // [screened]
+        tgnh::DeviceBuf<double2> d_pair_par;      // [screened] (a, K)
+        tgnh::DeviceBuf<int> d_recv_slot, d_recv_start, d_recv_term;   // [receivers], [receivers + 1], [entries]: the inverse in CSR form
+        tgnh::DeviceBuf<unsigned char> d_recv_role;                    // [entries]
+        tgnh::DeviceBuf<double> d_energy; // [index_grid(receivers) + 1][4]: a row per work-group of the launch, then the totals; allocated at set time
+        void drop() {
+            rows = screened = receivers = 0; energy_launched = false;
+            d_atoms.reset(); d_p4.reset(); d_k.reset(); d_pair_rows.reset(); d_pair_par.reset();
+            d_recv_slot.reset(); d_recv_start.reset(); d_recv_term.reset(); d_recv_role.reset(); d_energy.reset();
+        }
+    } dforce;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block
         std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction

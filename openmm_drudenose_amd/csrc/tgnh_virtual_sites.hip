@@ -25,30 +25,11 @@
 // A degenerate frame (a parallel to b) divides by zero and stores what comes out; llrint of a non-finite share is whatever the
 // conversion instruction gives.  No LDS, no atomic, no inline assembly.
 #include "tgnh_virtual_sites.h"
-#include "tgnh_device_math.h"
+#include "tgnh_position_device.h"      // Vec3, and a parent's position as include/drude_tgnh.h defines it (slot_position)
 
 namespace tgnh {
 
 #pragma clang fp contract(off)
-
-struct Vec3 { double x, y, z; };
-__device__ __forceinline__ Vec3 operator+(const Vec3 a, const Vec3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ Vec3 operator-(const Vec3 a, const Vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ Vec3 operator*(const double s, const Vec3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ double dot(const Vec3 a, const Vec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ Vec3 cross(const Vec3 a, const Vec3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-
-// a parent's position as include/drude_tgnh.h defines it
-template <int PREC>
-__device__ __forceinline__ Vec3 vs_position(const void* posq, const void* corr, const int i) {
-    const typename Prec<PREC>::real4 p = static_cast<const typename Prec<PREC>::real4*>(posq)[i];
-    Vec3 x = {(double)p.x, (double)p.y, (double)p.z};
-    if (PREC == TGNH_PREC_MIXED) {
-        const float4 c = static_cast<const float4*>(corr)[i];
-        x.x = x.x + (double)c.x; x.y = x.y + (double)c.y; x.z = x.z + (double)c.z;
-    }
-    return x;
-}
 
 __device__ __forceinline__ double vs_param(const SiteTable& t, const int k, const int row) { return t.params[(size_t)k * t.n + row]; }
 __device__ __forceinline__ Vec3 vs_param3(const SiteTable& t, const int k, const int row) { return {vs_param(t, k, row), vs_param(t, k + 1, row), vs_param(t, k + 2, row)}; }
@@ -77,10 +58,10 @@ __global__ __launch_bounds__(BLOCK) void place_sites_kernel(const SitePlaceArgs 
     if (row >= a.t.n) return;
     const int4 at = a.t.atoms[row];
     const int kind = a.t.kind[row];
-    const Vec3 x1 = vs_position<PREC>(a.posq, a.posq_corr, at.y), x2 = vs_position<PREC>(a.posq, a.posq_corr, at.z);
+    const Vec3 x1 = slot_position<PREC>(a.posq, a.posq_corr, at.y), x2 = slot_position<PREC>(a.posq, a.posq_corr, at.z);
     // the third parent and the first three planes are read whatever the kind, so that no load waits for the branch on the kind word (a
     // two-particle site: p3 = -1 reads p2 again, and the third plane holds the host's zero; neither is used)
-    const Vec3 x3 = vs_position<PREC>(a.posq, a.posq_corr, at.w >= 0 ? at.w : at.z);
+    const Vec3 x3 = slot_position<PREC>(a.posq, a.posq_corr, at.w >= 0 ? at.w : at.z);
     const Vec3 w = vs_param3(a.t, 0, row);
     Vec3 s;
     if (kind == VS_TWO_AVERAGE) {
@@ -124,8 +105,8 @@ __global__ __launch_bounds__(BLOCK) void spread_site_forces_kernel(const SiteSpr
         if (kind == VS_TWO_AVERAGE || kind == VS_THREE_AVERAGE) {
             share = vs_param(a.t, role, row) * f;
         } else {
-            const Vec3 x1 = vs_position<PREC>(a.posq, a.posq_corr, at.y), x2 = vs_position<PREC>(a.posq, a.posq_corr, at.z),
-                       x3 = vs_position<PREC>(a.posq, a.posq_corr, at.w);
+            const Vec3 x1 = slot_position<PREC>(a.posq, a.posq_corr, at.y), x2 = slot_position<PREC>(a.posq, a.posq_corr, at.z),
+                       x3 = slot_position<PREC>(a.posq, a.posq_corr, at.w);
             if (kind == VS_OUT_OF_PLANE) {
                 const Vec3 w = vs_param3(a.t, 0, row), r12 = x2 - x1, r13 = x3 - x1;
                 const Vec3 f2 = w.x * f + w.z * cross(r13, f), f3 = w.y * f - w.z * cross(r12, f);

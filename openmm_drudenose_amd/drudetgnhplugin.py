@@ -325,6 +325,30 @@ class _HandleQueries:
         _check(self.lib.tgnh_get_num_virtual_sites(self.h, C.byref(n)))
         return n.value
 
+    # ---- the library's own DrudeForce table (include/drude_tgnh.h: tgnh_set_drude_force) ----
+    def set_drude_force(self, force):
+        """tgnh_set_drude_force: a forces.DrudeForce, or its four tables (particles [n,5], params [n,4], screened [m,2], thole [m]);
+        row k names the system's pair k; None or an empty table clears it.  The checks run on a host-only handle too."""
+        if force is None:
+            _check(self.lib.tgnh_set_drude_force(self.h, 0, None, None, 0, None, None))
+            return
+        particles, params, screened, thole = force.tables() if hasattr(force, "tables") else force
+        particles = np.ascontiguousarray(particles, np.int32).reshape(-1, 5)
+        params = np.ascontiguousarray(params, np.float64).reshape(-1, 4)
+        screened = np.ascontiguousarray(screened, np.int32).reshape(-1, 2)
+        thole = np.ascontiguousarray(thole, np.float64).reshape(-1)
+        if len(particles) != len(params) or len(screened) != len(thole):
+            raise TgnhError(_lib.ERR_ARG, "set_drude_force: one row of four parameters per row of particles, one thole per screened pair")
+        _check(self.lib.tgnh_set_drude_force(self.h, len(particles), particles.ctypes.data_as(_lib.c_i32p), params.ctypes.data_as(_lib.c_f64p),
+                                             len(screened), screened.ctypes.data_as(_lib.c_i32p), thole.ctypes.data_as(_lib.c_f64p)))
+
+    @property
+    def num_drude_force_terms(self):
+        """tgnh_get_num_drude_force_terms: (rows, screened pairs) of the table in force"""
+        n, m = C.c_int(), C.c_int()
+        _check(self.lib.tgnh_get_num_drude_force_terms(self.h, C.byref(n), C.byref(m)))
+        return n.value, m.value
+
     # ---- the periodic box and the size of a frame (include/drude_tgnh.h: tgnh_set_periodic_box, tgnh_get_frame_count) ----
     def setPeriodicBoxVectors(self, a, b, c):
         """tgnh_set_periodic_box: the three box vectors (nm) in OpenMM's reduced form -- a = (ax, 0, 0), b = (bx, by, 0),
@@ -486,6 +510,10 @@ class HipContext(_HandleQueries):
     instead of the harness'; False (the default): to the harness.  A system's set_site_table goes to the library's table either way.
     site_forces (an attribute, default False): True lets every compute_forces() end with one distribute_site_forces(), for a force_fn
     that leaves forces on sites; the harness' water force spreads its M site's force itself and wants it off.
+    drude_force (an attribute, default False): True lets every compute_forces() add the library's own DrudeForce
+    (compute_drude_force()) after force_fn and before the sites' forces are spread.  A system that carries a forces.DrudeForce
+    (DrudeSystem.set_drude_force) hands it to the handle here; nothing is launched for it until the attribute is set or
+    compute_drude_force() is called.
     """
     _only_library_sites = False            # (minimizeEnergy: a context that says nothing else about itself is refused as a constrained one)
 
@@ -562,6 +590,7 @@ class HipContext(_HandleQueries):
                                                           harness[1].ctypes.data_as(_lib.c_f64p)))
             self.constrained = True
         self.site_forces = False           # True: every compute_forces() is followed by one distribute_site_forces()
+        self.drude_force = False           # True: every compute_forces() adds the library's DrudeForce after force_fn (compute_drude_force)
         self._harness_sites = False        # the harness' site table holds sites (the system's three-particle averages, unless library_sites)
         table = [np.zeros(0, np.int32), np.zeros((0, 4), np.int32), np.zeros((0, _lib.SITE_PARAMS))]     # what goes to the library's table
         if system.site_table_kinds is not None and len(system.site_table_kinds):
@@ -581,6 +610,8 @@ class HipContext(_HandleQueries):
         self._only_library_sites = not self._has_clusters and not self._harness_sites     # what makes the context `constrained` is at most sites of the library's table
         if len(table[0]):
             self.set_virtual_sites(*table)
+        if system.drude_force is not None:
+            self.set_drude_force(system.drude_force)
         if system.positions is not None:
             self.setPositions(system.positions)
             self.set_sites(system.positions)
@@ -932,7 +963,7 @@ class HipContext(_HandleQueries):
     def _minimize_batch(self, iterations):
         """`iterations` x {virtual sites where the context has them, the force call-out, one iteration}, enqueued back to back"""
         sites = self._harness_sites or self.num_virtual_sites > 0
-        if self.force_fn is None and not sites:
+        if self.force_fn is None and not self.drude_force and not sites:      # (the C loop knows the harness force alone, as step()'s do)
             _check(self.lib.tgnh_run_harness_minimize(self.h, self._x0_arg(), self.k_drude, self.k_tether, int(iterations), self._stream()))
             return
         for _ in range(iterations):
@@ -1065,6 +1096,20 @@ class HipContext(_HandleQueries):
         parents (and left on the sites, which have no mass: a second call adds a second time).  No synchronisation."""
         _check(self.lib.tgnh_distribute_virtual_site_forces(self.h, self.force.data_ptr(), self._stream()))
 
+    # ---- the library's own DrudeForce (include/drude_tgnh.h: tgnh_set_drude_force, ...) ----
+    def compute_drude_force(self, energy=False):
+        """tgnh_compute_drude_force on the context's force buffer: the springs, their anisotropy and the screened pairs of the table
+        in force are ADDED to what the buffer holds (an empty table: no launch).  energy=True: the same launch leaves the partial
+        sums drude_energy() adds.  No synchronisation."""
+        _check(self.lib.tgnh_compute_drude_force(self.h, self.force.data_ptr(), 1 if energy else 0, self._stream()))
+
+    def drude_energy(self):
+        """tgnh_get_drude_energy: (springs, screened pairs) in kJ/mol, of the positions the last compute_drude_force(energy=True)
+        read.  Synchronises."""
+        out = np.zeros(2)
+        _check(self.lib.tgnh_get_drude_energy(self.h, self._stream(), out.ctypes.data_as(_lib.c_f64p)))
+        return float(out[0]), float(out[1])
+
     def _place_sites(self):
         """the virtual-site call-out (Cu :377): the harness' table where it holds sites, then the library's (none: no launch)"""
         if self._harness_sites:
@@ -1109,6 +1154,8 @@ class HipContext(_HandleQueries):
         else:
             _check(self.lib.tgnh_harness_force(self.h, self._x0_arg(), self.k_drude, self.k_tether,
                                                self.force.data_ptr(), self._stream()))
+        if self.drude_force:
+            self.compute_drude_force()
         if self.site_forces:
             self.distribute_site_forces()
 
@@ -1120,13 +1167,14 @@ class HipContext(_HandleQueries):
         self.ke_sum_valid = True                             # DrudeTGNHIntegrator.cpp:192
 
     def step(self, steps):
-        if self.force_fn is None and self.constrained:
+        harness_loop = self.force_fn is None and not self.drude_force      # (the C loops know the harness force alone)
+        if harness_loop and self.constrained:
             _check(self.lib.tgnh_run_harness_constrained(self.h, self._x0_arg(), self.k_drude, self.k_tether,
                                                          self.integrator.getConstraintTolerance(), int(steps), self._stream()))
             if steps > 0:
                 self.ke_sum_valid = True
             return
-        if self.force_fn is None:
+        if harness_loop:
             _check(self.lib.tgnh_run_harness(self.h, self._x0_arg(), self.k_drude, self.k_tether, int(steps), self._stream()))
             if steps > 0:
                 self.ke_sum_valid = True
@@ -1171,7 +1219,7 @@ class HipContext(_HandleQueries):
         (no setters).  A handle that is not in the steady state of its step sequence is brought there first, by up to
         three times `steps` real steps (see below): read the step count afterwards if it matters."""
         torch = self.torch
-        if self.force_fn is not None:
+        if self.force_fn is not None or self.drude_force:
             raise TgnhError(_lib.ERR_STATE, "capture_steps supports the harness force call-out only")
         # A recording bakes in the centre-of-mass removals of the steps it recorded (set_cm_motion_removal): it replays the loop's
         # own launches only if every replay starts at a multiple of the interval, and so ends at one

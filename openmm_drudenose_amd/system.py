@@ -30,6 +30,8 @@ class DrudeSystem:
     # geometry [slots][3], index of this system's first molecule in the box); a hint for the harness force's tether sites, checked
     # slot by slot by the library before it is used
     lattice: tuple = None
+    # the library's own DrudeForce (tgnh_set_drude_force): set_drude_force
+    drude_force: object = None             # forces.DrudeForce, row k on pair k
 
     def __post_init__(self):
         self.mass = np.ascontiguousarray(self.mass, np.float64)
@@ -65,6 +67,21 @@ class DrudeSystem:
         p = np.asarray(params, np.float64).reshape(len(self.site_table_kinds), -1)
         self.site_table_params = np.zeros((len(p), 12))
         self.site_table_params[:, :p.shape[1]] = p
+
+    def set_drude_force(self, force):
+        """The library's own DrudeForce for this system (forces.DrudeForce; None takes it off): a HipContext over the system hands it
+        to its handle (tgnh_set_drude_force).  Row k must name pair k -- (pair_drude[k], pair_parent[k]) --, one row per pair.
+        slice_molecules does not carry it over: a shard sets the rows of its own pairs, with its local indices."""
+        if force is not None:
+            particles = force.tables()[0]
+            if len(particles) != self.num_pairs:
+                raise ValueError(f"set_drude_force: {len(particles)} rows for {self.num_pairs} Drude pairs")
+            wrong = np.flatnonzero((particles[:, 0] != self.pair_drude) | (particles[:, 1] != self.pair_parent))
+            if len(wrong):
+                k = int(wrong[0])
+                raise ValueError(f"set_drude_force: row {k} names ({particles[k, 0]}, {particles[k, 1]}), pair {k} is "
+                                 f"({self.pair_drude[k]}, {self.pair_parent[k]})")
+        self.drude_force = force
 
     @property
     def num_particles(self):
