@@ -10,6 +10,10 @@ ERR_ARG, ERR_GROUP_MISMATCH, ERR_HARDWALL, ERR_UNSUPPORTED, ERR_HIP, ERR_STATE =
 MODE_DUALNH, MODE_TGNH = 0, 1
 PREC_SINGLE, PREC_MIXED, PREC_DOUBLE = 0, 1, 2
 FLAG_DEFER_SCALE, FLAG_RESIDENT_STEP, FLAG_WAVE_TILES, FLAG_TRUST_STATE_CHANGED, FLAG_GATHER = 2, 4, 8, 16, 32
+# bits of tgnh_get_pending_state (include/drude_tgnh.h) that the Python side masks: 8 the direction of the next sweep, 10 the
+# velocities live in the library's own planes; OWED: all eleven bits but the direction -- what a recorded step must leave as found
+PENDING_SWEEP_DIRECTION, PENDING_VELOCITY_PLANES = 1 << 8, 1 << 10
+PENDING_OWED = 0x7ff & ~PENDING_SWEEP_DIRECTION
 KID_SKD, KID_KICK_KE, KID_SCALE, KID_KE, KID_CHAIN, KID_FORCE, KID_OTHER, KID_STEP = range(8)
 KERNEL_NAMES = {KID_SKD: "scale+kick+drift", KID_KICK_KE: "kick+KE", KID_SCALE: "rescale", KID_KE: "KE",
                 KID_CHAIN: "chain", KID_FORCE: "harness force", KID_OTHER: "other", KID_STEP: "resident step"}
