@@ -131,14 +131,7 @@ __global__ __launch_bounds__(BLOCK) void chain_kernel(const ChainArgs a) {
     if (!a.do_chain) return;
     if (!a.do_sum) __syncthreads();
     CHAIN_TRACE(1);
-    if (L.mode == TGNH_MODE_TGNH && L.C > 4 && L.C <= 16 && a.lanes) {
-        chain_lanes_run(a, st, tid, BLOCK, s_ke);                    // 5-16 links: a link per lane, in registers
-        if (tid == 0) {                                              // Cu :493-497
-            double s = 0.0;
-            for (int i = 0; i < NT; i++) s += s_ke[i];
-            st[L.off_kesum] = 0.5 * s;
-        }
-    } else if (L.mode == TGNH_MODE_TGNH) {
+    if (L.mode == TGNH_MODE_TGNH) {
         // real thermostats on lanes 0..NT-2 of wave 0, the Drude thermostat on lane 0 of wave 1: the two code
         // paths then run side by side on two SIMDs instead of one after the other under one exec mask
         int itg = -1;
@@ -183,8 +176,8 @@ __global__ __launch_bounds__(BLOCK) void chain_kernel(const ChainArgs a) {
 // of 2-4 links (no range test inside the loop, the exponentials that repeat within a sub-step taken once, the wide form when an
 // equilibrating box leaves the short polynomial's range).  A thermostat's half step is 2 C S link updates, each waiting for the one
 // before (the sweeps of Cu :566-571 / :586-592 bounce from end to end), run by one wavefront that issues one fp64 instruction per
-// ~8 cycles: what it costs is instructions per update.  A link per lane (chain_lanes_run, round 3) pays per update two DPP moves
-// for the neighbour's value, a range-tested exponential in EVERY lane and four conditional moves to commit in one: ~340
+// ~8 cycles: what it costs is instructions per update.  A link per lane (round 3's form, removed: profiles/r04_chain_cost.md) paid per update two
+// DPP moves for the neighbour's value, a range-tested exponential in EVERY lane and four conditional moves to commit in one: ~340
 // instructions per sub-step of ten links against ~150 here.  Kernels of their own so that chain_kernel's code stays what it was
 // (a launch starts with a cold instruction cache); a thermostat per lane, the Drude thermostat on the second wavefront.
 template <int CC>
@@ -335,7 +328,7 @@ __global__ __launch_bounds__(BLOCK) void plain_ke_sum_kernel(double* out, int np
 
 hipError_t launch_chain(const ChainArgs& a, hipStream_t s) {
     if (!a.do_chain) TGNH_LAUNCH(rowsum_kernel, dim3(1), dim3(BLOCK), 0, s, a);
-    else if (a.L.mode == TGNH_MODE_TGNH && a.L.C > 4 && a.L.C <= 16 && !a.lanes) {
+    else if (a.L.mode == TGNH_MODE_TGNH && a.L.C > 4 && a.L.C <= 16) {
         switch (a.L.C) {
 #define TGNH_LONG(c) case c: TGNH_LAUNCH(chain_long_kernel<c>, dim3(1), dim3(BLOCK), 0, s, a); break;
             TGNH_LONG(5) TGNH_LONG(6) TGNH_LONG(7) TGNH_LONG(8) TGNH_LONG(9) TGNH_LONG(10) TGNH_LONG(11) TGNH_LONG(12)

@@ -164,7 +164,9 @@ struct ChainArgs {
     int do_sum;                // sum partials -> ke_red
     int do_chain;              // run the chain from ke_red
     int chain_twice;           // DEFER_SCALE: second half of step n and first half of step n+1 back to back
-    int lanes;                 // chains of 5-16 links (TGNH): a link per lane (chain_lanes_run) instead of LDS-resident links
+    int : 32;                  // (a hole where round 3's `lanes` word was.  The struct is this size either way -- dt is 8-aligned -- but with
+                               // ke_carry four bytes lower the compiler regroups the kernels' scalar argument loads: 66 kernels beside
+                               // chain_kernel come out as other code, most with another instruction count, profiles/chain_forms.md)
     int ke_carry;              // the chain's kinetic energies are the last chain's ke_post (= s^2 KE: the bins of the velocities that
                                // chain's rescale left, TGNH_FLAG_TRUST_STATE_CHANGED) -- no KE pass, no row sum ran for this half step
     double dt;

@@ -315,11 +315,6 @@ ChainArgs chain_args(tgnh_handle h) {
     a.dt = h->d.step_size; a.S = h->d.drude_steps_per_real_step;
     a.dtc = a.dt / a.S; a.inv_dtc = 1.0 / a.dtc;                               // Cu :440-443
     a.realkbT = h->thermo.realkbT; a.drudekbT = h->thermo.drudekbT;
-    // chains of 5-16 links: chain_long_kernel<C>, the links in registers (round 3 ran them a link per lane, chain_lanes_run: kept
-    // behind a switch for the comparison in profiles/r04_chain_cost.md)
-#ifdef TGNH_TUNING
-    if (const char* e = getenv("TGNH_CHAIN_LANES")) a.lanes = e[0] != '0';
-#endif
     a.stage = h->thermo.d_stage;
     a.status = h->status.d_word;
     if (h->xchg.on) a.x = h->xchg.args;

@@ -53,6 +53,7 @@ SYSTEMS = {
     "il40": lambda: synth.ionic_liquid(40),
     "mixed": lambda: synth.mixed(300, 20),
     "ragged6": lambda: ragged_system(6),                       # random molecule sizes / pair placements, 4 groups
+    "groups40": lambda: synth.many_groups(300, 20, 40),         # 42 thermostats, more than chain_kernel's 34: gather_rowsum / gather_chain
 }
 
 
@@ -352,7 +353,7 @@ def test_trust_state_changed_is_ignored_where_it_cannot_hold():
     ctx.close()
 
 
-FAR_CASES = [   # (mode, links, flags): every form of the chain -- chain_kernel's, the in-kernel ones, a link per lane, LDS-resident links
+FAR_CASES = [   # (mode, links, flags): every form of the chain -- chain_kernel's, the in-kernel ones, register-resident long chains, LDS-resident links
     ("TGNH", 1, 0), ("TGNH", 1, FLAG_DEFER_SCALE | FLAG_RESIDENT_STEP), ("TGNH", 1, FLAG_DEFER_SCALE),
     ("TGNH", 3, 0), ("TGNH", 3, FLAG_DEFER_SCALE | FLAG_RESIDENT_STEP), ("TGNH", 3, FLAG_DEFER_SCALE), ("TGNH", 2, 0), ("TGNH", 4, FLAG_DEFER_SCALE),
     ("TGNH", 10, 0), ("TGNH", 17, 0),
@@ -396,6 +397,68 @@ def test_chain_far_from_equilibrium(mode, chains, flags, amp):
     print(f"{mode} {chains} links flags {flags} amp {amp:g}: pos {ep:.2e} vel {ev:.2e} thermostat {worst:.2e} |v|max {np.abs(vel_o).max():.3g}")
     assert ep <= 1e-10 and ev <= 1e-10 and worst <= 1e-10 and ctx.check() == 0
     ctx.close()
+
+
+_DR = FLAG_DEFER_SCALE | FLAG_RESIDENT_STEP
+DUMMY_CASES = [   # (mode, links, useDrudeNHChains, flags): every form of the chain that reads a dummy link's etaDot
+    ("TGNH", 1, True, 0), ("TGNH", 1, True, _DR), ("TGNH", 3, True, 0), ("TGNH", 3, True, _DR), ("TGNH", 3, False, 0),
+    ("TGNH", 10, True, 0), ("TGNH", 17, True, 0),
+    ("dualNH", 1, True, 0), ("dualNH", 1, False, 0), ("dualNH", 1, False, _DR), ("dualNH", 3, True, 0), ("dualNH", 3, False, 0),
+    ("dualNH", 10, True, 0), ("dualNH", 10, False, 0), ("dualNH", 17, False, 0),
+    ("TGNH", 1, True, FLAG_GATHER),              # the gather path's streaming kernels; its chain is chain_kernel's chain1_run (34 thermostats or fewer)
+]
+
+
+def _moving_dummy(sysname, gather, mode, chains, drude_chains, flags, amp):
+    """3 steps with every dummy link's etaDot at +-amp * U(0.5, 1) against the oracle at 1e-10, the dummies back bit for bit as set;
+    `gather`: the handle must step on the gather path."""
+    s, g, ng, it, ctx = make(sysname, mode, "double", chains=chains, drude_chains=drude_chains, flags=flags, tiles="lds")
+    assert (ctx.step_path()[0] == "gather") == gather
+    o = make_oracle(s, g, ng, mode, it)
+    ed = ctx.thermostat_state(1)
+    assert np.all(ed == 0) and np.array_equal(o.chain(1), ed)
+    dummy = np.zeros(len(ed), bool)
+    if mode == "TGNH":
+        dummy[chains::chains + 1] = True                     # every thermostat's row of chains + 1 ends in its dummy (Cu :252)
+    else:
+        dummy[-2:] = True                                    # the interleaved vectors' two dummies (Ref :215)
+    rng = np.random.default_rng(int(amp) + chains)
+    ed[dummy] = amp * rng.choice([-1.0, 1.0], dummy.sum()) * rng.uniform(0.5, 1.0, dummy.sum())
+    ctx.set_thermostat_state(1, ed)
+    o.set_chain(1, ed)
+    pos_o, vel_o = oracle_run(o, s, 3, x0=ctx.sites())
+    assert np.isfinite(vel_o).all() and np.isfinite(o.chain(1)).all()
+    ctx.step(3)
+    vscale = max(np.abs(vel_o).max(), 1e-3 * np.abs(s.velocities).max())
+    ep, ev = rel_err(ctx.getPositions(), pos_o), np.abs(ctx.getVelocities() - vel_o).max() / vscale
+    if flags & FLAG_DEFER_SCALE:                             # (deferred: the library's chain has run the coming step's first half already)
+        o.propagate_nhc(vel_o.copy())
+    worst = 0.0
+    for which in (0, 1, 2):
+        a, b = ctx.thermostat_state(which), o.chain(which)
+        worst = max(worst, np.abs(a - b).max() / max(1.0, np.abs(b).max()))
+    kept = np.array_equal(ctx.thermostat_state(1)[dummy], ed[dummy])
+    print(f"{mode} {chains} links drude_chains {drude_chains} flags {flags} amp {amp:g}: pos {ep:.2e} vel {ev:.2e} thermostat {worst:.2e} dummies kept {kept}")
+    assert ep <= 1e-10 and ev <= 1e-10 and worst <= 1e-10 and ctx.check() == 0
+    assert kept and np.array_equal(o.chain(1)[dummy], ed[dummy])
+    ctx.close()
+
+
+@pytest.mark.parametrize("amp", [800.0, 8000.0])
+@pytest.mark.parametrize("mode,chains,drude_chains,flags", DUMMY_CASES)
+def test_chain_with_a_moving_dummy_link(mode, chains, drude_chains, flags, amp):
+    """The dummy links (Cu :252, Ref :215: "will always have etaDot = 0") set to +-amp ps^-1, as set_thermostat_state or a restored
+    checkpoint can: their exp(-dtc/8 etaDot) is then a constant of the call that is not 1 -- 0.005 (inside the short polynomial) and
+    0.05 (outside it) -- on every form of the chain.  The reference honours the value and never moves it; so must the library."""
+    _moving_dummy("mixed", bool(flags & FLAG_GATHER), mode, chains, drude_chains, flags, amp)
+
+
+@pytest.mark.parametrize("amp", [800.0, 8000.0])
+@pytest.mark.parametrize("chains", [1, 3])
+def test_gather_chain_with_a_moving_dummy_link(chains, amp):
+    """The same on gather_chain_kernel, a thread per thermostat with the library exp: 42 thermostats, more than chain_kernel's 34.
+    run_tgnh<1> (chain_real_core<1>, which took its dummy's factor as 1 unread until this test) and run_tgnh<3>."""
+    _moving_dummy("groups40", True, "TGNH", chains, True, 0, amp)
 
 
 @pytest.mark.parametrize("precision", ["mixed", "double"])
