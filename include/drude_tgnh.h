@@ -1001,6 +1001,79 @@ tgnh_status tgnh_get_num_drude_force_terms(tgnh_handle h, int* rows, int* screen
 tgnh_status tgnh_compute_drude_force(tgnh_handle h, void* force, int want_energy, void* stream);    /* in the force call-out */
 tgnh_status tgnh_get_drude_energy(tgnh_handle h, void* stream, double out[2] /* springs, screened pairs */);   /* synchronises */
 
+/* THE LIBRARY'S OWN BONDED FORCES, for a host that has no OpenMM behind it (inside OpenMM the System's forces keep acting, and the glue
+ * calls none of this): OpenMM's HarmonicBondForce, HarmonicAngleForce and PeriodicTorsionForce and their energies, on the device -- the
+ * covalent half of an intramolecular force field beside the DrudeForce above.  Coulomb and Lennard-Jones forces are not here.
+ * PERIODIC IMAGES ARE NOT APPLIED: a term acts along the stored positions, and molecules are kept whole by tgnh_wrap_molecules.
+ *
+ * tgnh_set_bonded_forces: three tables.  bond_particles [nb][2] = (p1, p2) slots of the bound arrays, bond_params [nb][2] = (length nm,
+ * k kJ/mol/nm^2); angle_particles [na][3] = (p1, p2, p3), p2 the centre, angle_params [na][2] = (angle rad, k kJ/mol/rad^2);
+ * torsion_particles [nt][4] = (p1, p2, p3, p4), torsion_periodicity [nt], torsion_params [nt][2] = (phase rad, k kJ/mol).  The three
+ * replace the ones set before, together; all three counts 0 clears them.  The arrays are read before the call returns.  Every check
+ * runs before any device work, so a host-only handle gives the same answers and the same counts (tgnh_get_num_bonded_terms: out[3] =
+ * bonds, angles, torsions).  Not inside a stream capture: the tables, their inverse and the energy's scratch are uploaded and allocated
+ * here, synchronously, and never later.  cos(phase) and sin(phase) are formed here, once, in fp64.
+ * TGNH_ERR_ARG, the kind and the row's number in tgnh_last_error() ("bond 5", "angle 0", "torsion 17"): a negative count; a NULL array
+ * with a positive count; an index out of range; a particle named twice within one term; a length, angle, phase or k that is not
+ * finite; a length < 0; an angle outside [0, pi]; a periodicity < 1.  TGNH_ERR_UNSUPPORTED: a periodicity > 12; more entries
+ * (2 nb + 3 na + 4 nt) than the inverted table's 32-bit offsets take -- decided from the counts alone, before any row is read.
+ * DUPLICATE TERMS on the same particles are allowed, unlike screened pairs (force fields stack several periodicities on one dihedral),
+ * and a row with k = 0 is legal and contributes shares of exactly 0.  Refused tables leave the ones in force as they were, and so do
+ * tables whose upload fails (TGNH_ERR_HIP): the new ones are built aside and replace the old ones only when they are complete.
+ *
+ * tgnh_compute_bonded_forces(force, want_energy).  Everything in fp64 in every precision.  A position x(i) is posq, + posq_correction
+ * in mixed precision, as tgnh_get_drude_statistics defines it.  Every operation is rounded on its own, in the order written (no fused
+ * multiply-add); sqrt and the divisions are the IEEE ones.  The terms:
+ *   bond (p1, p2; r0, k):   d = x(p2) - x(p1), r = sqrt((dx^2 + dy^2) + dz^2), c = (k (r - r0)) / r;
+ *                           p1: +c d,  p2: -c d;   E = (0.5 k (r - r0)) (r - r0)
+ *   angle (p1, p2, p3; t0, k):   a = x(p1) - x(p2), b = x(p3) - x(p2), c = a x b, s = max(|c|, 1e-6) (OpenMM's floor: a collinear angle
+ *                           with t0 = pi gives exactly zero, finite shares), t = atan2(|c|, a . b) (not acos, which loses half the
+ *                           digits near 0 and pi), g = k (t - t0);
+ *                           F1 = (g / ((a . a) s)) (c x a),  F3 = (g / ((b . b) s)) (b x c),  F2 = -(F1 + F3), each component formed from
+ *                           the fp64 F1 and F3 and then converted;   p1: F1,  p2: F2,  p3: F3;   E = (0.5 g) (t - t0)
+ *   torsion (p1, p2, p3, p4; n, phi0, k):   v0 = x(p1) - x(p2), v1 = x(p3) - x(p2), v2 = x(p3) - x(p4), c0 = v0 x v1, c1 = v1 x v2,
+ *                           l = sqrt(v1 . v1), X = c0 . c1, Y = l (v0 . c1), hyp = sqrt(X^2 + Y^2), cos phi = X / hyp, sin phi = Y / hyp
+ *                           (the IUPAC sign: cis is 0, trans is pi).  No trigonometric call on the device: (C_1, S_1) = (cos phi, sin phi),
+ *                           C_(m+1) = C_m cos phi - S_m sin phi, S_(m+1) = S_m cos phi + C_m sin phi up to m = n.
+ *                           E = k (1 + (C_n cos phi0 + S_n sin phi0));   g = dE/dphi = -(k n) (S_n cos phi0 - C_n sin phi0);
+ *                           F1 = (-g l / (c0 . c0)) c0,  F4 = (g l / (c1 . c1)) c1,
+ *                           s = ((v0 . v1) / (v1 . v1)) F1 - ((v2 . v1) / (v1 . v1)) F4,  F2 = s - F1,  F3 = -s - F4;   p1..p4: F1..F4
+ * (The angle and torsion shares were checked against central finite differences of the energies above in fp80,
+ * tests/test_bonded_forces.py; they are -dE/dx.)
+ * Each component of each particle's share of each term is converted on its own, llrint(c * 4294967296.0), and added to the particle's
+ * entry as an integer (tgnh_compute_drude_force's rule): the result is a function of the inputs alone -- not of grid, order, device
+ * or step path -- and no atomic operation touches the buffer.  The bond shares are bit for bit what a numpy restatement gives.
+ * `force` is int64 [3*padded] fixed point x 2^32, planes x|y|z -- normally the bound buffer.  The call ADDS: two calls add twice.
+ * Padding and slots in no term are neither read nor written; positions, velm and posDelta are only read or not touched at all.
+ * A degenerate torsion (c0 or c1 of length 0) or a bond of length 0 stores the non-finite numbers it produces; there is no status
+ * bit for it, as for a DrudeForce axis of length 0.
+ * One launch on `stream` (one lane per receiving slot over the tables inverted at set time, bonds numbered first, then angles, then
+ * torsions; a term is recomputed by every particle that receives from it), none with empty tables (TGNH_OK).  It does not synchronise
+ * and can be captured into a hipGraph.  It is not a tgnh_state_changed, and may run at any time with respect to kicks a step still
+ * owes (tgnh_get_pending_state), as tgnh_compute_drude_force may.  TGNH_ERR_STATE: a host-only handle, buffers not bound, force is
+ * NULL.  Follows tgnh_get_status_flags' rule for sticky failures.
+ *
+ * THE ENERGY.  want_energy != 0: the same launch also leaves a row of partial sums {bonds, angles, torsions} per work-group, in scratch
+ * allocated at set time.  tgnh_get_bonded_energy enqueues the one-work-group sum of the rows, synchronises `stream` and returns
+ * out[0] = the bonds' energy, out[1] = the angles', out[2] = the torsions', kJ/mol.  Each term is counted by exactly one lane, the
+ * lane of its p1.  No floating-point atomic; the grid is a function of the number of receiving slots alone and every order of
+ * additions is fixed by it, so the same positions give the same bits from any handle over the same slots and the same tables, tiled
+ * or TGNH_FLAG_GATHER, TGNH or DUALNH, asked once or twice.
+ * TGNH_ERR_STATE: no tgnh_compute_bonded_forces with want_energy since the tables were set -- a launch that was only RECORDED into a
+ * stream capture does not count (nothing has run; the replayed graph fills the rows, and an eager want_energy launch before or after
+ * the capture opens the query) --; a host-only handle, buffers not bound.  TGNH_ERR_ARG: out is NULL.
+ * SHARDED RUNS: shards are whole molecules; every rank hands over its own terms with local indices, and a term that
+ * names a particle outside the shard is refused by the index check.  Nothing is exchanged: the forces are local and the three
+ * energies are additive over ranks. */
+tgnh_status tgnh_set_bonded_forces(tgnh_handle h,
+    int num_bonds,    const int32_t* bond_particles    /* [nb][2] */, const double* bond_params    /* [nb][2]: length nm, k kJ/mol/nm^2 */,
+    int num_angles,   const int32_t* angle_particles   /* [na][3], p2 the centre */, const double* angle_params /* [na][2]: angle rad, k kJ/mol/rad^2 */,
+    int num_torsions, const int32_t* torsion_particles /* [nt][4] */, const int32_t* torsion_periodicity /* [nt] */,
+                      const double* torsion_params     /* [nt][2]: phase rad, k kJ/mol */);
+tgnh_status tgnh_get_num_bonded_terms(tgnh_handle h, int out[3]);
+tgnh_status tgnh_compute_bonded_forces(tgnh_handle h, void* force, int want_energy, void* stream);   /* ADDS; one launch; capturable */
+tgnh_status tgnh_get_bonded_energy(tgnh_handle h, void* stream, double out[3] /* bonds, angles, torsions */);   /* synchronises */
+
 /* The call-outs of the reference's own testWater (platforms/reference/tests/TestReferenceDrudeTGNHIntegrator.cpp:111-166),
  * harness only: its force field -- NonbondedForce with reaction field, cutoff `cutoff` in a cubic box of edge `box`, +
  * DrudeForce + the M site's force spread over O, H1, H2, for slots laid out O, D, H1, H2, M per molecule -- written into

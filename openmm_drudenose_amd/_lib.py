@@ -202,6 +202,10 @@ SIGNATURES = {
     "tgnh_get_num_drude_force_terms": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "tgnh_compute_drude_force": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tgnh_get_drude_energy": (C.c_int, [C.c_void_p, C.c_void_p, c_f64p]),
+    "tgnh_set_bonded_forces": (C.c_int, [C.c_void_p, C.c_int, c_i32p, c_f64p, C.c_int, c_i32p, c_f64p, C.c_int, c_i32p, c_i32p, c_f64p]),
+    "tgnh_get_num_bonded_terms": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "tgnh_compute_bonded_forces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "tgnh_get_bonded_energy": (C.c_int, [C.c_void_p, C.c_void_p, c_f64p]),
     "tgnh_harness_water_force": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "tgnh_harness_remove_cm_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tgnh_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),

@@ -194,6 +194,28 @@ struct tgnh_context {
             d_recv_slot.reset(); d_recv_start.reset(); d_recv_term.reset(); d_recv_role.reset(); d_energy.reset();
         }
     } dforce;
+    struct BondedForces {             // tgnh_set_bonded_forces (tgnh_bonded.cpp): the three tables in the caller's order and their one inverse
+        int bonds = 0, angles = 0, torsions = 0;  // terms in force (a host-only handle keeps the counts and nothing else)
+        int receivers = 0;                // slots that receive a share of some term
+        bool energy_launched = false;     // a want_energy launch has filled d_energy's rows since the tables were set
+        tgnh::DeviceBuf<int2> d_bond_atoms;       // [bonds] (p1, p2), uploaded at set time, never inside a capture
+        tgnh::DeviceBuf<double2> d_bond_par;      // [bonds] (length, k)
+        tgnh::DeviceBuf<int4> d_angle_atoms;      // [angles] (p1, p2, p3, 0)
+        tgnh::DeviceBuf<double2> d_angle_par;     // [angles] (angle, k)
+        tgnh::DeviceBuf<int4> d_torsion_atoms;    // [torsions]
+        tgnh::DeviceBuf<int> d_torsion_n;         // [torsions]
+        tgnh::DeviceBuf<double> d_torsion_par;    // [3][torsions] cos(phase), sin(phase), k
+        tgnh::DeviceBuf<int> d_recv_slot, d_recv_start, d_recv_term;   // [receivers], [receivers + 1], [entries]: the inverse in CSR form
+        tgnh::DeviceBuf<unsigned char> d_recv_role;                    // [entries]
+        tgnh::DeviceBuf<double> d_energy; // [index_grid(receivers) + 1][4]: a row per work-group of the launch, then the totals; allocated at set time
+        bool empty() const { return bonds + angles + torsions == 0; }
+        void drop() {
+            bonds = angles = torsions = receivers = 0; energy_launched = false;
+            d_bond_atoms.reset(); d_bond_par.reset(); d_angle_atoms.reset(); d_angle_par.reset();
+            d_torsion_atoms.reset(); d_torsion_n.reset(); d_torsion_par.reset();
+            d_recv_slot.reset(); d_recv_start.reset(); d_recv_term.reset(); d_recv_role.reset(); d_energy.reset();
+        }
+    } bonded;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block
         std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction

@@ -4,8 +4,18 @@
 setters); it holds the table only.  `tables()` gives it in the form tgnh_set_drude_force takes (include/drude_tgnh.h has the
 contract and the terms); `DrudeSystem.set_drude_force` attaches it to a system, and a `HipContext` over such a system hands it to
 its handle.  Units are OpenMM's: charge e, polarizability nm^3.
+
+`HarmonicBondForce`, `HarmonicAngleForce` and `PeriodicTorsionForce` are tables of the same kind with OpenMM's method names (nm, rad,
+kJ/mol); `BondedForces` hands up to three of them to a handle (tgnh_set_bonded_forces) and is itself a force call-out:
+`ctx.force_fn = BondedForces(ctx, bonds, angles, torsions)` with `ctx.drude_force = True` runs a flexible Drude molecule on the
+library's forces alone.
 """
+import ctypes as C
+
 import numpy as np
+
+from . import _lib
+from ._abi import TgnhError, _check
 
 
 class DrudeForce:
@@ -62,3 +72,162 @@ class DrudeForce:
         if not 0 <= index < len(table):                      # ASSERT_VALID_INDEX
             raise IndexError("Index out of range")
         return int(index)
+
+
+class _TermTable:
+    """Rows of `_WIDTH` particle indices, then `_EXTRA` integers, then two floats: the common part of the three bonded tables."""
+    _WIDTH, _EXTRA = 0, 0
+
+    def __init__(self):
+        self._rows = []
+
+    def _add(self, *row):
+        self._rows.append(self._row(*row))
+        return len(self._rows) - 1
+
+    def _get(self, index):
+        return tuple(self._rows[DrudeForce._index(index, self._rows)])
+
+    def _set(self, index, *row):
+        self._rows[DrudeForce._index(index, self._rows)] = self._row(*row)
+
+    def _row(self, *row):
+        ints = self._WIDTH + self._EXTRA
+        if len(row) != ints + 2:
+            raise TypeError(f"{type(self).__name__}: {ints + 2} values a row, got {len(row)}")
+        return [int(v) for v in row[:ints]] + [float(v) for v in row[ints:]]
+
+    def tables(self):
+        """-> (particles [n, width] int32, params [n, 2] float64); a PeriodicTorsionForce: (particles [n, 4], periodicity [n] int32,
+        params [n, 2] = (phase, k))"""
+        w, x = self._WIDTH, self._EXTRA
+        particles = np.ascontiguousarray([r[:w] for r in self._rows], np.int32).reshape(-1, w)
+        params = np.ascontiguousarray([r[w + x:] for r in self._rows], np.float64).reshape(-1, 2)
+        if not x:
+            return particles, params
+        return particles, np.ascontiguousarray([r[w] for r in self._rows], np.int32).reshape(-1), params
+
+
+class HarmonicBondForce(_TermTable):
+    """OpenMM's HarmonicBondForce as a table: E = 1/2 k (r - length)^2, length in nm, k in kJ/mol/nm^2."""
+    _WIDTH = 2
+
+    def getNumBonds(self):
+        return len(self._rows)
+
+    def addBond(self, particle1, particle2, length, k):
+        return self._add(particle1, particle2, length, k)
+
+    def getBondParameters(self, index):
+        return self._get(index)
+
+    def setBondParameters(self, index, particle1, particle2, length, k):
+        self._set(index, particle1, particle2, length, k)
+
+
+class HarmonicAngleForce(_TermTable):
+    """OpenMM's HarmonicAngleForce as a table: E = 1/2 k (theta - angle)^2 about particle2, angle in rad, k in kJ/mol/rad^2."""
+    _WIDTH = 3
+
+    def getNumAngles(self):
+        return len(self._rows)
+
+    def addAngle(self, particle1, particle2, particle3, angle, k):
+        return self._add(particle1, particle2, particle3, angle, k)
+
+    def getAngleParameters(self, index):
+        return self._get(index)
+
+    def setAngleParameters(self, index, particle1, particle2, particle3, angle, k):
+        self._set(index, particle1, particle2, particle3, angle, k)
+
+
+class PeriodicTorsionForce(_TermTable):
+    """OpenMM's PeriodicTorsionForce as a table: E = k (1 + cos(periodicity phi - phase)), phase in rad, k in kJ/mol."""
+    _WIDTH, _EXTRA = 4, 1
+
+    def getNumTorsions(self):
+        return len(self._rows)
+
+    def addTorsion(self, particle1, particle2, particle3, particle4, periodicity, phase, k):
+        return self._add(particle1, particle2, particle3, particle4, periodicity, phase, k)
+
+    def getTorsionParameters(self, index):
+        return self._get(index)
+
+    def setTorsionParameters(self, index, particle1, particle2, particle3, particle4, periodicity, phase, k):
+        self._set(index, particle1, particle2, particle3, particle4, periodicity, phase, k)
+
+
+class BondedForces:
+    """The library's bonded forces on a handle (include/drude_tgnh.h: tgnh_set_bonded_forces, ...).  `owner` is a HipContext or a
+    HostTopology; bonds, angles, torsions: a HarmonicBondForce / HarmonicAngleForce / PeriodicTorsionForce, the tuple its tables()
+    gives, or None.  Construction hands the tables to the handle (they replace the ones in force); a shape that does not fit is
+    refused here, before any library call.  An instance is a force call-out: it zeroes the context's force buffer and adds the
+    bonded forces, so `ctx.force_fn = BondedForces(ctx, ...)` is all a step, the minimiser or the barostat need."""
+
+    def __init__(self, owner, bonds=None, angles=None, torsions=None):
+        self.owner = owner
+        b = self._tables("bonds", bonds, 2, False)
+        a = self._tables("angles", angles, 3, False)
+        t = self._tables("torsions", torsions, 4, True)
+        ptr = lambda v, p: v.ctypes.data_as(p) if len(v) else None                                # noqa: E731
+        _check(owner.lib.tgnh_set_bonded_forces(owner.h, len(b[0]), ptr(b[0], _lib.c_i32p), ptr(b[-1], _lib.c_f64p),
+                                                len(a[0]), ptr(a[0], _lib.c_i32p), ptr(a[-1], _lib.c_f64p),
+                                                len(t[0]), ptr(t[0], _lib.c_i32p), ptr(t[1], _lib.c_i32p), ptr(t[-1], _lib.c_f64p)))
+
+    @staticmethod
+    def _tables(name, table, width, periodic):
+        """-> the table's arrays, contiguous and typed; TgnhError(ERR_ARG) for a shape that is not [n, width] beside [n, 2] (and [n])"""
+        if table is None:
+            table = (np.zeros((0, width), np.int32),) + ((np.zeros(0, np.int32),) if periodic else ()) + (np.zeros((0, 2)),)
+        elif hasattr(table, "tables"):
+            table = table.tables()
+        if len(table) != (3 if periodic else 2):
+            raise TgnhError(_lib.ERR_ARG, f"set_bonded_forces: {name}: {3 if periodic else 2} arrays, got {len(table)}")
+        arrays = [np.ascontiguousarray(v, np.float64 if m == len(table) - 1 else np.int32) for m, v in enumerate(table)]
+        n = len(arrays[0])
+        if arrays[0].ndim != 2 or arrays[0].shape[1] != width:
+            raise TgnhError(_lib.ERR_ARG, f"set_bonded_forces: {name}: particles of shape {arrays[0].shape}, not [n, {width}]")
+        if arrays[-1].shape != (n, 2):
+            raise TgnhError(_lib.ERR_ARG, f"set_bonded_forces: {name}: parameters of shape {arrays[-1].shape} for {n} rows of particles, not [{n}, 2]")
+        if periodic and arrays[1].shape != (n,):
+            raise TgnhError(_lib.ERR_ARG, f"set_bonded_forces: {name}: periodicities of shape {arrays[1].shape} for {n} rows of particles, not [{n}]")
+        return arrays
+
+    @property
+    def num_terms(self):
+        """tgnh_get_num_bonded_terms: (bonds, angles, torsions) of the tables in force"""
+        out = (C.c_int * 3)()
+        _check(self.owner.lib.tgnh_get_num_bonded_terms(self.owner.h, out))
+        return tuple(out)
+
+    def compute(self, energy=False):
+        """tgnh_compute_bonded_forces on the owner's force buffer: the terms are ADDED to what it holds (empty tables: no launch).
+        energy=True: the same launch leaves the partial sums energy() adds.  No synchronisation."""
+        o = self.owner
+        force = getattr(o, "force", None)
+        _check(o.lib.tgnh_compute_bonded_forces(o.h, None if force is None else force.data_ptr(), 1 if energy else 0, o._stream()))
+
+    def energy(self):
+        """tgnh_get_bonded_energy: (bonds, angles, torsions) in kJ/mol, of the positions the last compute(energy=True) read.
+        Synchronises."""
+        out = (C.c_double * 3)()
+        _check(self.owner.lib.tgnh_get_bonded_energy(self.owner.h, self.owner._stream(), out))
+        return tuple(float(e) for e in out)
+
+    def clear(self):
+        """all three counts 0: the tables are gone, compute() launches nothing"""
+        _check(self.owner.lib.tgnh_set_bonded_forces(self.owner.h, 0, None, None, 0, None, None, 0, None, None, None))
+
+    def __call__(self, ctx):
+        """the form HipContext.force_fn takes"""
+        ctx.force.zero_()
+        self.compute()
+
+    def then(self, fn):
+        """-> a call-out that runs this one and then fn(ctx): for a caller who adds a nonbonded force of their own"""
+        def both(ctx):
+            self(ctx)
+            fn(ctx)
+        return both
