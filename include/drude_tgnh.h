@@ -931,7 +931,7 @@ tgnh_status tgnh_distribute_virtual_site_forces(tgnh_handle h, void* force, void
 /* THE LIBRARY'S OWN DRUDEFORCE, for a host that has no OpenMM behind it (inside OpenMM the System's DrudeForce keeps acting, and the
  * glue calls none of this): the springs that hold the Drude particles, their anisotropy, the Thole-screened pairs and the energy, on
  * the device.  It stands beside the harness forces (tgnh_harness_force: a bench workload with a tether; tgnh_harness_water_force:
- * testWater's one isotropic spring per molecule) and replaces neither.  Coulomb and Lennard-Jones forces are not here.
+ * testWater's one isotropic spring per molecule) and replaces neither.  Coulomb and Lennard-Jones forces are not here: THE LIBRARY'S OWN NONBONDED FORCE below has them.
  *
  * tgnh_set_drude_force: OpenMM's DrudeForce::addParticle / addScreenedPair as a table.  particles [n][5] = (p, p1, p2, p3, p4) slots
  * of the bound arrays, -1 = none for p2..p4; params [n][4] = (charge e, polarizability nm^3, aniso12, aniso34); screened
@@ -1073,6 +1073,108 @@ tgnh_status tgnh_set_bonded_forces(tgnh_handle h,
 tgnh_status tgnh_get_num_bonded_terms(tgnh_handle h, int out[3]);
 tgnh_status tgnh_compute_bonded_forces(tgnh_handle h, void* force, int want_energy, void* stream);   /* ADDS; one launch; capturable */
 tgnh_status tgnh_get_bonded_energy(tgnh_handle h, void* stream, double out[3] /* bonds, angles, torsions */);   /* synchronises */
+
+/* THE LIBRARY'S OWN NONBONDED FORCE, for a host that has no OpenMM behind it (inside OpenMM the System's NonbondedForce keeps acting, and
+ * the glue calls none of this): Coulomb with a reaction field and Lennard-Jones between all particles inside a cutoff of a rectangular
+ * periodic box, and OpenMM's exceptions -- the intermolecular half of a force field beside the DrudeForce and the bonded forces above.
+ * The definitions are OpenMM's NonbondedForce with CutoffPeriodic, recalled from its published documentation, as oracle/water_ff.c
+ * restates them; OpenMM was not at hand to check against.  NOT BUILT: Ewald and PME, the switching function, the long-range dispersion
+ * correction, triclinic cells, a Verlet list with a skin (the cells are rebuilt by every call, so the call stays stateless).
+ *
+ * tgnh_set_nonbonded_force.  desc->particles [n][3] = (charge e, sigma nm, epsilon kJ/mol), one row per slot of the bound arrays:
+ * charges come from this table, posq.w is neither read nor written.  exception_particles [ne][2] = (p1, p2), exception_params [ne][3] =
+ * (chargeProd e^2, sigma nm, epsilon kJ/mol).  The table replaces the one set before; desc == NULL or num_particles == 0 clears it.  The
+ * arrays are read before the call returns.  Every check runs before any device work, so a host-only handle gives the same answers and
+ * the same counts (tgnh_get_num_nonbonded_terms: out[3] = particles, exceptions, of which evaluated).  Not inside a stream capture: the
+ * tables, the exclusion list of every slot (ascending), the inverse of the evaluated exceptions and every per-slot buffer are uploaded
+ * and allocated here, synchronously.  krf and crf are formed here, once, in fp64, each operation rounded on its own:
+ *   krf = ((1 / ((rc rc) rc)) (eps - 1)) / (2 eps + 1)        crf = ((1 / rc) (3 eps)) / (2 eps + 1)
+ * TGNH_ERR_ARG, with "particle 7" or "exception 3" in tgnh_last_error(): a struct_size that is not sizeof(tgnh_nonbonded_desc);
+ * num_particles that is not the handle's slot count; a negative count; a NULL array with a positive count; a parameter that is not
+ * finite; sigma < 0 or epsilon < 0; a cutoff that is not finite or <= 0; a dielectric that is not finite or < 1; an exception index out
+ * of range; an exception with p1 == p2; the same pair in two exception rows (the later row is named).  TGNH_ERR_UNSUPPORTED: any method
+ * but TGNH_NB_CUTOFF_PERIODIC; a handle that is one shard of several (a hook, RCCL or the mailboxes are attached): pairs cross shards
+ * and nothing is exchanged here; 2 ne beyond 32-bit offsets (decided from the count alone).  A refused table leaves the one in force as
+ * it was, and so does one whose upload fails (TGNH_ERR_HIP): the new one is built aside and swapped in when it is complete.
+ *
+ * tgnh_compute_nonbonded_force(force, want_energy).  Everything in fp64 in every precision.  x(i) is posq, + posq_correction in mixed
+ * precision, as tgnh_get_drude_statistics defines it.  Every operation is rounded on its own, in the order written (no fused
+ * multiply-add); sqrt and the divisions are the IEEE ones; rint rounds to nearest, ties to even.  K = 138.935456.  L is the box's edge
+ * along the component, rc the cutoff.
+ * PAIRS.  Every unordered pair {a, b} of slots that no exception row names gets a term.  For the share of particle a, b the other
+ * one, per component k:
+ *   d_k  = x_k(a) - x_k(b)
+ *   t_k  = d_k / L_k
+ *   t_k  = rint(t_k)                       (not floor(t + 0.5): rint is odd, so the pair's two lanes hold exactly negated d)
+ *   t_k  = L_k t_k
+ *   d_k  = d_k - t_k
+ * (The device skips the division where the result of these four lines is known exactly: |d_k| <= 0.49 L_k leaves d_k as it is, since
+ * rint gives 0; 0.51 L_k <= |d_k| <= 1.49 L_k gives d_k - copysign(L_k, d_k), since rint gives +-1 and L (+-1) is +-L.  The margins
+ * of 0.01 keep the rounded quotient off the ties at 0.5 and 1.5.  Everything else, a NaN included, takes the four lines: same bits.)
+ * then
+ *   r2   = (dx dx + dy dy) + dz dz         the pair is skipped unless r2 < rc rc
+ *   r    = sqrt(r2)
+ *   inv  = 1 / r
+ *   qq   = K (q_a q_b)                     (the charges' product first: it commutes, so both lanes hold the same bits, and a
+ *                                           permutation of the slots permutes the result; (K q_a) q_b would do neither)
+ *   sig  = 0.5 (sigma_a + sigma_b)
+ *   e4   = 4 sqrt(epsilon_a epsilon_b)
+ *   s2   = (sig sig) / r2
+ *   s6   = (s2 s2) s2
+ *   s12  = s6 s6
+ *   dc   = qq ((2 krf) r - inv inv)        the Coulomb part of dE/dr
+ *   dl   = (e4 (6 s6 - 12 s12)) inv        the Lennard-Jones part
+ *   c    = -((dc + dl) inv)
+ *   particle a receives llrint((c d_k) 4294967296.0) per component, added as an integer
+ *   E_C  = qq ((inv + krf r2) - crf)       E_LJ = e4 (s12 - s6)
+ * EXCEPTIONS.  Every pair an exception row names is left out of the above.  A row with chargeProd != 0 or epsilon != 0 is evaluated on
+ * its own, with no cutoff, no reaction field and NO PERIODIC IMAGE (molecules are whole: the bonded section's rule); any other row is a
+ * pure exclusion.  For the share of particle a of the row, b the other one:
+ *   d_k  = x_k(a) - x_k(b);   r2, r, inv as above;   qq = K chargeProd;   e4 = 4 epsilon;   s2 = (sigma sigma) / r2;   s6, s12 as above
+ *   dc   = qq (-(inv inv));   dl = (e4 (6 s6 - 12 s12)) inv;   c = -((dc + dl) inv);   llrint((c d_k) 4294967296.0) as above
+ *   E_C  = qq inv             E_LJ = e4 (s12 - s6)
+ * Every contribution is converted on its own and added as an integer, so the change of the force buffer is a function of positions,
+ * box and tables alone -- not of cell order, grid or path --, a numpy restatement gives it bit for bit (tests/test_nonbonded.py), and a
+ * pair's two shares cancel exactly.  `force` is int64 [3*padded] fixed point x 2^32, planes x|y|z -- normally the bound buffer.  The
+ * call ADDS: two calls add twice.  No atomic operation touches the buffer.  Padding is neither read nor written; positions, velm and
+ * posDelta are only read or not touched at all.  Two particles that no exception names at r = 0 store the non-finite numbers that come
+ * out; there is no status bit for it.
+ * THE CELLS.  nc_k = max(1, floor(L_k / (1.001 rc))) cells per edge (the 1.001 keeps a one-ulp misassignment at a cell face from hiding
+ * a pair inside the cutoff); a slot's cell per component is s = x / L, s = s - floor(s), min((int)(s nc), nc - 1): positions far outside
+ * the box and negative ones are legal.  More than 2^24 cells: TGNH_ERR_UNSUPPORTED.  LAUNCHES: one memset and five kernels a call --
+ * cell, scan, place, rank, pairs -- and a sixth when some exception is evaluated; the numbers do not depend on n.  None with no table
+ * set (TGNH_OK).  The call does not synchronise and can be captured into a hipGraph; a graph bakes in the box it was recorded with.
+ * The per-cell buffers grow at the first call whose box needs more cells than they hold: on a capturing stream that call returns
+ * TGNH_ERR_STATE and asks for one call outside the capture (the frame rule); growing them invalidates graphs recorded before.
+ * TGNH_ERR_STATE: a host-only handle, buffers not bound, force is NULL, no box set.  TGNH_ERR_UNSUPPORTED: a box with a non-zero
+ * off-diagonal component; a cutoff above half the shortest edge; a sharded handle.  Follows tgnh_get_status_flags' rule for sticky
+ * failures.  It is not a tgnh_state_changed.
+ *
+ * THE ENERGY.  want_energy != 0: the pair launch also leaves a row {E_C, E_LJ} per work-group -- a lane counts a pair only when the
+ * other slot is larger than its own, and adds in traversal order: neighbour cells z, then y, then x from c - 1 upwards, members in
+ * (cell, slot) order -- and the exception launch a row per work-group, the lane of a row's p1 counting it.  tgnh_get_nonbonded_energy
+ * enqueues the one-work-group sum, synchronises `stream` and returns out[0] = the pairs' Coulomb energy with the reaction field,
+ * out[1] = the pairs' Lennard-Jones energy, out[2], out[3] = the evaluated exceptions' Coulomb and Lennard-Jones energy, kJ/mol.  No
+ * floating-point atomic: the same positions, box and tables give the same bits from any handle over the same slots, tiled or
+ * TGNH_FLAG_GATHER, TGNH or DUALNH, asked once or twice.  TGNH_ERR_STATE: no tgnh_compute_nonbonded_force with want_energy since the
+ * table was set or since the per-cell buffers last grew (a launch that was only recorded into a stream capture does not count); a host-only handle, buffers not bound.
+ * TGNH_ERR_ARG: out is NULL. */
+enum { TGNH_NB_NO_CUTOFF = 0, TGNH_NB_CUTOFF_NONPERIODIC = 1, TGNH_NB_CUTOFF_PERIODIC = 2 };   /* OpenMM's numbering */
+typedef struct tgnh_nonbonded_desc {
+    uint32_t struct_size;             /* sizeof(tgnh_nonbonded_desc); anything else: TGNH_ERR_ARG */
+    int32_t method;                   /* only TGNH_NB_CUTOFF_PERIODIC is taken */
+    double cutoff;                    /* nm */
+    double reaction_field_dielectric; /* OpenMM's default 78.3 */
+    int32_t num_particles;
+    const double* particles;          /* [n][3] charge e, sigma nm, epsilon kJ/mol: one row per slot of the bound arrays */
+    int32_t num_exceptions;
+    const int32_t* exception_particles;   /* [ne][2] */
+    const double* exception_params;   /* [ne][3] chargeProd, sigma, epsilon */
+} tgnh_nonbonded_desc;
+tgnh_status tgnh_set_nonbonded_force(tgnh_handle h, const tgnh_nonbonded_desc* d);      /* d == NULL or num_particles == 0 clears */
+tgnh_status tgnh_get_num_nonbonded_terms(tgnh_handle h, int out[3]);                    /* particles, exceptions, of which evaluated */
+tgnh_status tgnh_compute_nonbonded_force(tgnh_handle h, void* force, int want_energy, void* stream);   /* ADDS; capturable */
+tgnh_status tgnh_get_nonbonded_energy(tgnh_handle h, void* stream, double out[4]);      /* pair Coulomb (with reaction field), pair LJ, exception Coulomb, exception LJ; synchronises */
 
 /* The call-outs of the reference's own testWater (platforms/reference/tests/TestReferenceDrudeTGNHIntegrator.cpp:111-166),
  * harness only: its force field -- NonbondedForce with reaction field, cutoff `cutoff` in a cubic box of edge `box`, +

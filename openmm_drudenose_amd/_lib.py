@@ -206,6 +206,10 @@ SIGNATURES = {
     "tgnh_get_num_bonded_terms": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "tgnh_compute_bonded_forces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tgnh_get_bonded_energy": (C.c_int, [C.c_void_p, C.c_void_p, c_f64p]),
+    "tgnh_set_nonbonded_force": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tgnh_get_num_nonbonded_terms": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "tgnh_compute_nonbonded_force": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "tgnh_get_nonbonded_energy": (C.c_int, [C.c_void_p, C.c_void_p, c_f64p]),
     "tgnh_harness_water_force": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "tgnh_harness_remove_cm_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tgnh_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),

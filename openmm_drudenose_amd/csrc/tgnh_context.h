@@ -216,6 +216,29 @@ struct tgnh_context {
             d_recv_slot.reset(); d_recv_start.reset(); d_recv_term.reset(); d_recv_role.reset(); d_energy.reset();
         }
     } bonded;
+    struct Nonbonded {                // tgnh_set_nonbonded_force (tgnh_nonbonded.cpp): the particle table, the exclusion lists, the evaluated exceptions' inverse
+        int particles = 0, exceptions = 0, evaluated = 0;   // in force (a host-only handle keeps these, the scalars below, and nothing else)
+        double cutoff = 0, dielectric = 0, krf = 0, crf = 0;
+        int receivers = 0;                // slots that receive a share of some evaluated exception
+        bool energy_launched = false;     // a want_energy call has filled the rows since the tables were set
+        int energy_rows = 0;              // ... and the pair launch of the last such call wrote this many
+        int cells_allocated = 0;          // what the per-cell buffers below hold; they grow at the first call that needs more, never inside a capture
+        tgnh::DeviceBuf<double> d_par;            // [particles][3] charge, sigma, epsilon; uploaded at set time, as everything down to d_totals
+        tgnh::DeviceBuf<int> d_excl_start, d_excl;        // [particles + 1], [2 exceptions]: a slot's excluded partners, ascending
+        tgnh::DeviceBuf<int2> d_excl_range;       // [particles] (lowest, highest) excluded partner, (1, 0): none
+        tgnh::DeviceBuf<int2> d_exc_atoms;        // [evaluated] (p1, p2)
+        tgnh::DeviceBuf<double> d_exc_par;        // [evaluated][3] chargeProd, sigma, epsilon
+        tgnh::DeviceBuf<int> d_recv_slot, d_recv_start, d_recv_term;   // [receivers], [receivers + 1], [entries]: the inverse in CSR form
+        tgnh::DeviceBuf<unsigned char> d_recv_role;                    // [entries]
+        tgnh::DeviceBuf<double> d_exc_rows;       // [index_grid(receivers)][4]
+        tgnh::DeviceBuf<int> d_cell_of, d_placed, d_sorted_slot, d_n_chunks;   // [particles] x 3, [1]: the cell build's per-slot scratch
+        tgnh::DeviceBuf<double> d_sorted;         // [6][particles]
+        tgnh::DeviceBuf<int2> d_sorted_range;     // [particles]
+        tgnh::DeviceBuf<double> d_totals;         // [4] where the energy's sum lands
+        tgnh::DeviceBuf<int> d_count, d_cell_start;       // [2 cells_allocated], [cells_allocated + 1]
+        tgnh::DeviceBuf<int2> d_chunks;           // [cells_allocated + ceil(particles / 64)]
+        tgnh::DeviceBuf<double> d_pair_rows;      // [pair grid of cells_allocated][4]
+    } nonbonded;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block
         std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction

@@ -9,6 +9,10 @@ its handle.  Units are OpenMM's: charge e, polarizability nm^3.
 kJ/mol); `BondedForces` hands up to three of them to a handle (tgnh_set_bonded_forces) and is itself a force call-out:
 `ctx.force_fn = BondedForces(ctx, bonds, angles, torsions)` with `ctx.drude_force = True` runs a flexible Drude molecule on the
 library's forces alone.
+
+`NonbondedForce` is OpenMM's table of charges, Lennard-Jones parameters and exceptions with its method names; `NonbondedForces` hands
+it to a handle (tgnh_set_nonbonded_force: CutoffPeriodic with a reaction field, over cell lists) and is a force call-out too:
+`BondedForces(ctx, ...).then(lambda c: nb.compute())`.
 """
 import ctypes as C
 
@@ -227,6 +231,194 @@ class BondedForces:
 
     def then(self, fn):
         """-> a call-out that runs this one and then fn(ctx): for a caller who adds a nonbonded force of their own"""
+        def both(ctx):
+            self(ctx)
+            fn(ctx)
+        return both
+
+
+class _NonbondedDesc(C.Structure):
+    """tgnh_nonbonded_desc (tgnh_set_nonbonded_force)"""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("method", C.c_int32), ("cutoff", C.c_double), ("reaction_field_dielectric", C.c_double),
+        ("num_particles", C.c_int32), ("particles", C.c_void_p), ("num_exceptions", C.c_int32), ("exception_particles", C.c_void_p),
+        ("exception_params", C.c_void_p),
+    ]
+
+
+class NonbondedForce:
+    """OpenMM's NonbondedForce as a table: per particle (charge e, sigma nm, epsilon kJ/mol), exceptions (p1, p2, chargeProd, sigma,
+    epsilon), the method, the cutoff and the reaction field's dielectric.  The library takes CutoffPeriodic only (the other
+    methods are refused by tgnh_set_nonbonded_force, not here)."""
+    NoCutoff, CutoffNonPeriodic, CutoffPeriodic = 0, 1, 2        # OpenMM's numbering
+
+    def __init__(self):
+        self._particles = []         # [charge, sigma, epsilon]
+        self._exceptions = []        # [p1, p2, chargeProd, sigma, epsilon]
+        self._pair_index = {}        # (lo, hi) -> row of _exceptions
+        self._method = self.NoCutoff                             # OpenMM's defaults
+        self._cutoff = 1.0
+        self._dielectric = 78.3
+
+    # --- particles ---
+    def getNumParticles(self):
+        return len(self._particles)
+
+    def addParticle(self, charge, sigma, epsilon):
+        self._particles.append([float(charge), float(sigma), float(epsilon)])
+        return len(self._particles) - 1
+
+    def getParticleParameters(self, index):
+        return tuple(self._particles[DrudeForce._index(index, self._particles)])
+
+    def setParticleParameters(self, index, charge, sigma, epsilon):
+        self._particles[DrudeForce._index(index, self._particles)] = [float(charge), float(sigma), float(epsilon)]
+
+    # --- exceptions ---
+    def getNumExceptions(self):
+        return len(self._exceptions)
+
+    def addException(self, particle1, particle2, chargeProd, sigma, epsilon, replace=False):
+        """A pair left out of the nonbonded loop and, unless chargeProd and epsilon are both 0, evaluated with these parameters.  A
+        pair that already has an exception: ValueError, or with replace=True its row is overwritten.  Returns the row's index."""
+        p1, p2 = int(particle1), int(particle2)
+        key = (min(p1, p2), max(p1, p2))
+        row = [p1, p2, float(chargeProd), float(sigma), float(epsilon)]
+        if key in self._pair_index:
+            if not replace:
+                raise ValueError(f"NonbondedForce: There is already an exception for particles {p1} and {p2}")
+            self._exceptions[self._pair_index[key]] = row
+            return self._pair_index[key]
+        self._exceptions.append(row)
+        self._pair_index[key] = len(self._exceptions) - 1
+        return len(self._exceptions) - 1
+
+    def getExceptionParameters(self, index):
+        return tuple(self._exceptions[DrudeForce._index(index, self._exceptions)])
+
+    def setExceptionParameters(self, index, particle1, particle2, chargeProd, sigma, epsilon):
+        index = DrudeForce._index(index, self._exceptions)
+        old = self._exceptions[index]
+        p1, p2 = int(particle1), int(particle2)
+        key = (min(p1, p2), max(p1, p2))
+        if self._pair_index.get(key, index) != index:
+            raise ValueError(f"NonbondedForce: There is already an exception for particles {p1} and {p2}")
+        del self._pair_index[(min(old[0], old[1]), max(old[0], old[1]))]
+        self._pair_index[key] = index
+        self._exceptions[index] = [p1, p2, float(chargeProd), float(sigma), float(epsilon)]
+
+    def createExceptionsFromBonds(self, bonds, coulomb14Scale, lj14Scale):
+        """OpenMM's rule: particles one or two bonds apart become pure exclusions; particles three bonds apart (and no closer by
+        another path) get chargeProd = coulomb14Scale q_i q_j, the mean sigma and epsilon = lj14Scale sqrt(eps_i eps_j).  Pairs that
+        already have an exception keep it."""
+        n = len(self._particles)
+        near = [set() for _ in range(n)]
+        for a, b in bonds:
+            a, b = int(a), int(b)
+            if not (0 <= a < n and 0 <= b < n):
+                raise IndexError("createExceptionsFromBonds: Illegal particle index in list of bonds")
+            near[a].add(b); near[b].add(a)
+        for i in range(n):
+            one = near[i]
+            two = set().union(*(near[j] for j in one)) - one - {i} if one else set()
+            three = (set().union(*(near[j] for j in two)) if two else set()) - two - one - {i}
+            for j in sorted(one | two):
+                if j > i and (i, j) not in self._pair_index:
+                    self.addException(i, j, 0.0, 1.0, 0.0)
+            for j in sorted(three):
+                if j > i and (i, j) not in self._pair_index:
+                    (qi, si, ei), (qj, sj, ej) = self._particles[i], self._particles[j]
+                    self.addException(i, j, coulomb14Scale * qi * qj, 0.5 * (si + sj), lj14Scale * (ei * ej) ** 0.5)
+
+    # --- the method and its parameters ---
+    def getNonbondedMethod(self):
+        return self._method
+
+    def setNonbondedMethod(self, method):
+        if method not in (self.NoCutoff, self.CutoffNonPeriodic, self.CutoffPeriodic):
+            raise ValueError("NonbondedForce: Illegal value for nonbonded method")
+        self._method = int(method)
+
+    def getCutoffDistance(self):
+        return self._cutoff
+
+    def setCutoffDistance(self, distance):
+        self._cutoff = float(distance)
+
+    def getReactionFieldDielectric(self):
+        return self._dielectric
+
+    def setReactionFieldDielectric(self, dielectric):
+        self._dielectric = float(dielectric)
+
+    # --- the table as tgnh_set_nonbonded_force takes it ---
+    def tables(self):
+        """-> (method, cutoff, dielectric, particles [n, 3] float64, exception_particles [ne, 2] int32, exception_params [ne, 3] float64)"""
+        exc = np.array(self._exceptions, np.float64).reshape(-1, 5)
+        return (self._method, self._cutoff, self._dielectric, np.array(self._particles, np.float64).reshape(-1, 3),
+                np.ascontiguousarray(exc[:, :2], np.int32), np.ascontiguousarray(exc[:, 2:]))
+
+
+class NonbondedForces:
+    """The library's NonbondedForce on a handle (include/drude_tgnh.h: tgnh_set_nonbonded_force, ...).  `owner` is a HipContext or a
+    HostTopology; `force` a NonbondedForce, the tuple its tables() gives, or None (nothing set).  Construction hands the table to
+    the handle (it replaces the one in force); a shape that does not fit is refused here, before any library call.  The box is the
+    handle's (setPeriodicBoxVectors).  An instance is a force call-out, and `BondedForces(ctx, ...).then(lambda c: nb.compute())`
+    adds it behind the bonded forces."""
+
+    def __init__(self, owner, force=None):
+        self.owner = owner
+        if force is None:
+            self.clear()
+            return
+        table = force.tables() if hasattr(force, "tables") else force
+        if len(table) != 6:
+            raise TgnhError(_lib.ERR_ARG, f"set_nonbonded_force: a method, a cutoff, a dielectric and three arrays, got {len(table)} values")
+        method, cutoff, dielectric = int(table[0]), float(table[1]), float(table[2])
+        par, ep, ex = (np.ascontiguousarray(v, t) for v, t in zip(table[3:], (np.float64, np.int32, np.float64)))
+        if par.ndim != 2 or par.shape[1] != 3:
+            raise TgnhError(_lib.ERR_ARG, f"set_nonbonded_force: particles of shape {par.shape}, not [n, 3]")
+        ne = len(ep)
+        if ep.shape != (ne, 2):
+            raise TgnhError(_lib.ERR_ARG, f"set_nonbonded_force: exception particles of shape {ep.shape}, not [ne, 2]")
+        if ex.shape != (ne, 3):
+            raise TgnhError(_lib.ERR_ARG, f"set_nonbonded_force: exception parameters of shape {ex.shape} for {ne} rows of particles, not [{ne}, 3]")
+        d = _NonbondedDesc(C.sizeof(_NonbondedDesc), method, cutoff, dielectric, len(par), par.ctypes.data if len(par) else None,
+                           ne, ep.ctypes.data if ne else None, ex.ctypes.data if ne else None)
+        _check(owner.lib.tgnh_set_nonbonded_force(owner.h, C.byref(d)))
+
+    @property
+    def num_terms(self):
+        """tgnh_get_num_nonbonded_terms: (particles, exceptions, of which evaluated) of the table in force"""
+        out = (C.c_int * 3)()
+        _check(self.owner.lib.tgnh_get_num_nonbonded_terms(self.owner.h, out))
+        return tuple(out)
+
+    def compute(self, energy=False):
+        """tgnh_compute_nonbonded_force on the owner's force buffer: the terms are ADDED to what it holds (no table: no launch).
+        energy=True: the same launches leave the partial sums energy() adds.  No synchronisation."""
+        o = self.owner
+        force = getattr(o, "force", None)
+        _check(o.lib.tgnh_compute_nonbonded_force(o.h, None if force is None else force.data_ptr(), 1 if energy else 0, o._stream()))
+
+    def energy(self):
+        """tgnh_get_nonbonded_energy: (pair Coulomb with the reaction field, pair Lennard-Jones, exception Coulomb, exception
+        Lennard-Jones) in kJ/mol, of the positions the last compute(energy=True) read.  Synchronises."""
+        out = (C.c_double * 4)()
+        _check(self.owner.lib.tgnh_get_nonbonded_energy(self.owner.h, self.owner._stream(), out))
+        return tuple(float(e) for e in out)
+
+    def clear(self):
+        """the table is gone, compute() launches nothing"""
+        _check(self.owner.lib.tgnh_set_nonbonded_force(self.owner.h, None))
+
+    def __call__(self, ctx):
+        """the form HipContext.force_fn takes"""
+        ctx.force.zero_()
+        self.compute()
+
+    def then(self, fn):
+        """-> a call-out that runs this one and then fn(ctx)"""
         def both(ctx):
             self(ctx)
             fn(ctx)

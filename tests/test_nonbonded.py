@@ -1,0 +1,669 @@
+"""The library's NonbondedForce without a GPU (csrc/tgnh_nonbonded.*; include/drude_tgnh.h has the contract): an fp80 O(N^2)
+reference, an fp64 numpy TWIN that follows the header's sequence of operations line for line -- all ordered pairs, no cells --, the
+two systems the GPU tests run (tests/test_nonbonded_gpu.py), and the checks that need no device.
+
+ * the reference's forces are -dE/dx of its own energies by central differences in fp80, per term kind, within 1e-8 of the kind's
+   largest force (the bonded test's method: h = 1e-6 nm, the truncation term h^2 f''' / 6 is below 1e-9 of f for a Lennard-Jones
+   pair at 0.3 nm, and fp80's rounding of E over h is 1e-13);
+ * on the reference's testWater, perturbed, reference nonbonded + Drude spring + M-site spread equals oracle/water_ff.c within that
+   test's 1e-9 max|f|, and the energy within 1e-9 of the sum of the terms' magnitudes: an independent statement of the same physics;
+ * MEASURED_MARGIN: the largest |c_twin - c_reference| r over a pair's uncancelled |dE/dr| = |qq| (1/r^2 + 2 krf r) + e4 (12 s12 +
+   6 s6) / r, over every pair of every state below (1.2e-13: see MEASURED_MARGIN); GATE = 16 x that (the project's convention);
+ * a pair's two shares in the twin are exact negatives of each other, so the twin's integers add up to zero per plane;
+ * every refusal with its text on a host-only handle, the table in force unchanged; the table class; createExceptionsFromBonds on a
+   branched chain; shape refusals against a recording stand-in.
+
+CONDITION on every state the GPU tests use, asserted here: no pair with |r2 - rc^2| < 1e-9 rc^2, so twin and reference agree on who
+is inside (the two constructed pairs of system B sit at rc (1 -+ 1e-6), 2000 times further from the cutoff than that)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from openmm_drudenose_amd import _lib
+from openmm_drudenose_amd.drudetgnhplugin import DrudeTGNHIntegrator, HostTopology, TgnhError
+from openmm_drudenose_amd.forces import NonbondedForce, NonbondedForces
+from openmm_drudenose_amd.system import DrudeSystem
+from oracle.binding import water_forces
+import water_test_system as wts
+from test_bonded_forces import CHAIN, CHAIN_BONDS, CHAIN_DRUDES, CHAIN_SLOT, _Owner
+
+PRECISIONS = ("double", "mixed", "single")
+FIXED = 4294967296.0
+K = 138.935456
+# test_the_margin_between_twin_and_reference prints the figure: 1.11e-13 when this was written.  It is the twin's d = x(a) - x(b), rounded
+# to fp64 where system B keeps molecules two box lengths outside the cell: half an ulp of a 9 nm difference, 9e-16 nm, is 9e-15 of
+# r = 0.1 nm, and the r^-13 of a Lennard-Jones force multiplies that by 13.
+MEASURED_MARGIN = 1.2e-13
+GATE = 16 * MEASURED_MARGIN
+L = np.longdouble
+CUTOFF, DIELECTRIC = 1.0, 78.3
+_cache = {}
+
+
+def rf_constants(rc, eps, dtype):
+    """krf and crf as tgnh_set_nonbonded_force forms them"""
+    rc, eps, one, two, three = (dtype(v) for v in (rc, eps, 1.0, 2.0, 3.0))
+    return ((one / ((rc * rc) * rc)) * (eps - one)) / (two * eps + one), ((one / rc) * (three * eps)) / (two * eps + one)
+
+
+def excluded_matrix(n, exc_particles):
+    m = np.zeros((n, n), bool)
+    m[exc_particles[:, 0], exc_particles[:, 1]] = True
+    m[exc_particles[:, 1], exc_particles[:, 0]] = True
+    np.fill_diagonal(m, True)
+    return m
+
+
+def pair_terms(x, table, box, dtype):
+    """The header's PAIRS, for every ORDERED pair (a, b) the loop takes and that is inside the cutoff -> dict of arrays: a, b (slots),
+    d [m, 3], c, e_c, e_lj, scale (the uncancelled |dE/dr|).  dtype float64: the twin, operation for operation; longdouble: the
+    reference."""
+    method, rc, eps_rf, par, ep, ex = table
+    n = len(x)
+    krf, crf = rf_constants(rc, eps_rf, dtype)
+    a, b = np.nonzero(~excluded_matrix(n, ep))
+    xs, box = x.astype(dtype), np.asarray(box, dtype)
+    d = xs[a] - xs[b]
+    t = d / box
+    t = np.rint(t)
+    t = box * t
+    d = d - t
+    r2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    keep = r2 < dtype(rc) * dtype(rc)
+    a, b, d, r2 = a[keep], b[keep], d[keep], r2[keep]
+    q, sg, ep_ = (par[:, m].astype(dtype) for m in range(3))
+    r = np.sqrt(r2)
+    inv = dtype(1.0) / r
+    qq = dtype(K) * (q[a] * q[b])
+    sig = dtype(0.5) * (sg[a] + sg[b])
+    e4 = dtype(4.0) * np.sqrt(ep_[a] * ep_[b])
+    s2 = (sig * sig) / r2
+    s6 = (s2 * s2) * s2
+    s12 = s6 * s6
+    dc = qq * ((dtype(2.0) * krf) * r - inv * inv)
+    dl = (e4 * (dtype(6.0) * s6 - dtype(12.0) * s12)) * inv
+    c = -((dc + dl) * inv)
+    return dict(a=a, b=b, d=d, c=c, r=r, e_c=qq * ((inv + krf * r2) - crf), e_lj=e4 * (s12 - s6),
+                scale=np.abs(qq) * (inv * inv + (dtype(2.0) * krf) * r) + (e4 * (dtype(6.0) * s6 + dtype(12.0) * s12)) * inv)
+
+
+def exception_terms(x, table, dtype):
+    """The header's EXCEPTIONS, for both receivers of every evaluated row: role 0 is the row's p1"""
+    ep, ex = table[4], table[5]
+    rows = np.nonzero((ex[:, 0] != 0.0) | (ex[:, 2] != 0.0))[0]
+    a = np.concatenate([ep[rows, 0], ep[rows, 1]])
+    b = np.concatenate([ep[rows, 1], ep[rows, 0]])
+    role = np.repeat([0, 1], len(rows))
+    p = np.concatenate([ex[rows], ex[rows]]).astype(dtype)
+    xs = x.astype(dtype)
+    d = xs[a] - xs[b]
+    r2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    r = np.sqrt(r2)
+    inv = dtype(1.0) / r
+    qq = dtype(K) * p[:, 0]
+    e4 = dtype(4.0) * p[:, 2]
+    s2 = (p[:, 1] * p[:, 1]) / r2
+    s6 = (s2 * s2) * s2
+    s12 = s6 * s6
+    dc = qq * (-(inv * inv))
+    dl = (e4 * (dtype(6.0) * s6 - dtype(12.0) * s12)) * inv
+    c = -((dc + dl) * inv)
+    return dict(a=a, b=b, d=d, c=c, r=r, role=role, e_c=qq * inv, e_lj=e4 * (s12 - s6),
+                scale=np.abs(qq) * (inv * inv) + (e4 * (dtype(6.0) * s6 + dtype(12.0) * s12)) * inv)
+
+
+def twin_integers(x, table, box):
+    """-> [n, 3] int64: what tgnh_compute_nonbonded_force adds to the buffer, bit for bit"""
+    out = np.zeros((len(x), 3), np.int64)
+    for t in (pair_terms(x, table, box, np.float64), exception_terms(x, table, np.float64)):
+        np.add.at(out, t["a"], np.rint((t["c"][:, None] * t["d"]) * FIXED).astype(np.int64))
+    return out
+
+
+def reference_forces(x, table, box):
+    """-> [n, 3] fp80 forces, and the four energies (pair Coulomb, pair LJ, exception Coulomb, exception LJ) with the sums of their
+    terms' magnitudes"""
+    f = np.zeros((len(x), 3), L)
+    p, e = pair_terms(x, table, box, L), exception_terms(x, table, L)
+    np.add.at(f, p["a"], p["c"][:, None] * p["d"])
+    np.add.at(f, e["a"], e["c"][:, None] * e["d"])
+    once, first = p["a"] < p["b"], e["role"] == 0
+    terms = (p["e_c"][once], p["e_lj"][once], e["e_c"][first], e["e_lj"][first])
+    return f, [t.sum() for t in terms], [np.abs(t).sum() for t in terms]
+
+
+def stored(x, precision):
+    """The stored arrays of positions x in a precision and their fp64 reading -> dict posq, corr (float32 or None), x"""
+    real = np.float64 if precision == "double" else np.float32
+    posq = x.astype(real)
+    corr = (x - posq.astype(np.float64)).astype(np.float32) if precision == "mixed" else None
+    return dict(posq=posq, corr=corr, x=posq.astype(np.float64) + (corr.astype(np.float64) if corr is not None else 0.0))
+
+
+def integrator():
+    return DrudeTGNHIntegrator(300.0, 0.1, 1.0, 0.005, 0.0005, 20, 1, True, True)
+
+
+# ---------------------------------------------------------------------------
+# system A: the reference's water box, every intramolecular pair a pure exclusion
+# ---------------------------------------------------------------------------
+WATER_Q = (1.71636, -1.71636, 0.55733, 0.55733, -1.11466)
+WATER_SIGMA, WATER_EPS = 0.318395, 0.21094 * 4.184
+BOX_A = (wts.BOX, wts.BOX, wts.BOX)
+
+
+def water_table(n_mol):
+    f = NonbondedForce()
+    for _ in range(n_mol):
+        for m, q in enumerate(WATER_Q):
+            f.addParticle(q, WATER_SIGMA if m == 0 else 0.0, WATER_EPS if m == 0 else 0.0)
+    for mol in range(n_mol):
+        for i in range(5):
+            for j in range(i + 1, 5):
+                f.addException(5 * mol + i, 5 * mol + j, 0.0, 1.0, 0.0)
+    f.setNonbondedMethod(NonbondedForce.CutoffPeriodic)
+    f.setCutoffDistance(CUTOFF)
+    return f
+
+
+def system_a():
+    if "a" not in _cache:
+        s = wts.build()
+        _cache["a"] = (s, water_table(s.num_particles // 5).tables())
+    return _cache["a"]
+
+
+def perturbed_water():
+    """test_harness_call_outs_equal_their_statements' state"""
+    s = wts.build()
+    return s.positions + np.random.default_rng(1).normal(0, 0.01, s.positions.shape)
+
+
+# ---------------------------------------------------------------------------
+# system B: a hub, branched chains with Drude particles, waters, ions, a crowded cell, and the constructed slots
+# ---------------------------------------------------------------------------
+BOX_B = (2.1, 3.2, 4.5)          # 2, 3 and 4 cells of at least 1.001 nm
+BOX_B_FOUR = (2.1, 3.2, 4.0)     # an edge of exactly 4 cutoffs: 3 cells, not 4
+BOX_B_MORE = (2.1, 3.2, 5.625)   # 5 cells along z: more cells than BOX_B
+HUB_ARMS = 12
+
+
+def cells_per_edge(box, rc=CUTOFF):
+    return tuple(max(1, int(np.floor(e / (1.001 * rc)))) for e in box)
+
+
+def cell_of(x, box, rc=CUTOFF):
+    nc = np.array(cells_per_edge(box, rc))
+    s = x / np.asarray(box)
+    s = s - np.floor(s)
+    c = np.minimum((s * nc).astype(np.int64), nc - 1)
+    return (c[:, 2] * nc[1] + c[:, 1]) * nc[0] + c[:, 0]
+
+
+def system_b():
+    """-> (DrudeSystem, table, info).  Everything but one lonely ion lives at 0 <= z <= 2.3 (or whole box lengths from there)."""
+    if "b" in _cache:
+        return _cache["b"]
+    rng = np.random.default_rng(11)
+    pos, mass, resid, bonds, drude, parent = [], [], [], [], [], []
+    f = NonbondedForce()
+    info = {}
+
+    def add(x, m, q, sigma, eps, mol):
+        pos.append(np.asarray(x, np.float64)); mass.append(m); resid.append(mol)
+        return f.addParticle(q, sigma, eps)
+
+    def add_drude(of, mol):
+        i = add(pos[of] + rng.normal(0, 0.006, 3), 0.4, -1.0, 0.0, 0.0, mol)
+        drude.append(i); parent.append(of); bonds.append((of, i))
+        return i
+
+    placed = []                                                  # (centre, radius) of what stands already
+
+    def place(radius, lo=(0.0, 0.0, 0.1), hi=(2.1, 3.2, 2.2)):
+        while True:
+            c = rng.uniform(np.array(lo) + radius * np.array([0, 0, 1]), np.array(hi) - radius * np.array([0, 0, 1]))
+            d = [np.abs((c - p + np.array(BOX_B) / 2) % np.array(BOX_B) - np.array(BOX_B) / 2) for p, _ in placed]
+            if all(np.linalg.norm(v) >= radius + r + 0.22 for v, (_, r) in zip(d, placed)):
+                placed.append((c, radius))
+                return c
+
+    mol = 0
+    # the crowded cell: 5 x 5 x 3 = 75 atoms 0.2 nm apart inside cell (0, 0, 0), which is 1.05 x 1.0667 x 1.125
+    info["cluster"] = []
+    for i in range(5):
+        for j in range(5):
+            for k in range(3):
+                at = np.array([0.1 + 0.2 * i, 0.1 + 0.2 * j, 0.12 + 0.2 * k]) + rng.uniform(-0.01, 0.01, 3)      # (off the lattice: 0.6, 0.8, 0 is a cutoff)
+                info["cluster"].append(add(at, 20.0, 0.1 * (-1) ** (i + j + k), 0.17, 0.3, mol))
+                mol += 1
+    placed.append((np.array([0.5, 0.5, 0.32]), 0.62))
+    # the constructed slots, placed first so that the random ones keep their distance
+    rc = CUTOFF
+    info["inside"] = (add([1.6, 0.3, 0.725], 20.0, 0.5, 0.3, 0.5, mol), add([1.6, 0.3, 0.725 + rc * (1 - 1e-6)], 20.0, -0.5, 0.3, 0.5, mol + 1))
+    info["outside"] = (add([1.6, 1.5, 0.725], 20.0, 0.5, 0.3, 0.5, mol + 2), add([1.6, 1.5, 0.725 + rc * (1 + 1e-6)], 20.0, -0.5, 0.3, 0.5, mol + 3))
+    info["cell_face"] = add([1.3, 2.6, 1.125], 20.0, 1.0, 0.25, 0.4, mol + 4)          # z = 4.5 / 4 exactly, in every precision
+    info["box_face"] = add([0.0, 2.0, 4.5], 20.0, -1.0, 0.25, 0.4, mol + 5)            # x = 0 and z = L_z exactly
+    info["lonely"] = add([1.0, 1.6, 3.4], 20.0, 1.0, 0.3, 0.5, mol + 6)                # nothing within 1 nm: the rest ends at z = 2.3
+    mol += 7
+    for i in info["inside"] + info["outside"] + (info["cell_face"],):
+        placed.append((pos[i], 0.0))
+    placed.append((np.array([0.0, 2.0, 0.0]), 0.0))
+    # the hub: a centre with 12 arms, an atom and its Drude particle each -- 24 exclusions on the centre
+    c = place(0.2)
+    hub = add(c, 12.0, 0.4, 0.3, 0.4, mol)
+    info["hub"] = hub
+    dirs = rng.normal(size=(HUB_ARMS * 40, 3))
+    dirs /= np.linalg.norm(dirs, axis=1)[:, None]
+    arms = [dirs[0]]
+    for v in dirs[1:]:
+        if len(arms) < HUB_ARMS and all(np.linalg.norm(v - w) > 0.75 for w in arms):
+            arms.append(v)
+    assert len(arms) == HUB_ARMS
+    for v in arms:
+        a = add(c + 0.17 * v, 12.0, 0.9, 0.2, 0.2, mol)
+        bonds.append((hub, a))
+        add_drude(a, mol)
+    mol += 1
+    # branched chains of test_bonded_forces.py's shape: 8 atoms, 3 of them with a Drude particle
+    extent = np.abs(CHAIN - CHAIN.mean(0)).max() * np.sqrt(3)
+    info["chains"] = []
+    for _ in range(6):
+        c = place(extent)
+        first = len(pos)
+        info["chains"].append(first)
+        q = rng.uniform(-0.4, 0.4, 8)
+        atoms = {}
+        for at in range(8):
+            atoms[at] = add(c + CHAIN[at] - CHAIN.mean(0), 12.0, q[at] + (1.0 if at in CHAIN_DRUDES else 0.0), 0.3, 0.35, mol)
+            assert atoms[at] - first == CHAIN_SLOT[at]
+            if at in CHAIN_DRUDES:
+                add_drude(atoms[at], mol)
+        bonds.extend((atoms[i], atoms[j]) for i, j in CHAIN_BONDS)
+        mol += 1
+    # waters, two of them whole box lengths outside the cell: one at negative coordinates, one beyond
+    info["waters"] = []
+    geom = wts.build().positions[:5] - wts.build().positions[0]
+    for w in range(36):
+        c = place(0.1)
+        shift = {0: np.array([-2 * BOX_B[0], 0.0, -BOX_B[2]]), 1: np.array([0.0, 2 * BOX_B[1], BOX_B[2]])}.get(w, np.zeros(3))
+        o = len(pos)
+        info["waters"].append(o)
+        for m in range(5):
+            add(c + geom[m] + shift + (rng.normal(0, 0.004, 3) if m == 1 else 0.0), (15.6, 0.4, 1.0, 1.0, 1.0)[m], WATER_Q[m],
+                WATER_SIGMA if m == 0 else 0.0, WATER_EPS if m == 0 else 0.0, mol)
+        drude.append(o + 1); parent.append(o)
+        bonds.extend([(o, o + 1), (o, o + 2), (o, o + 3), (o, o + 4), (o + 2, o + 3)])
+        mol += 1
+    info["far"] = (info["waters"][0], info["waters"][1])
+    # ions
+    for k in range(22):
+        add(place(0.0), 23.0, 1.0 if k % 2 else -1.0, 0.25, 0.4, mol)
+        mol += 1
+    f.createExceptionsFromBonds(bonds, 1.0 / 1.2, 0.5)
+    f.setNonbondedMethod(NonbondedForce.CutoffPeriodic)
+    f.setCutoffDistance(CUTOFF)
+    x = np.array(pos)
+    s = DrudeSystem(mass=np.array(mass), pair_drude=np.array(drude), pair_parent=np.array(parent), resid=np.array(resid), positions=x,
+                    velocities=np.zeros_like(x), name="nonbonded system B")
+    info["bonds"] = bonds
+    _cache["b"] = (s, f.tables(), info)
+    return _cache["b"]
+
+
+def states():
+    """every (name, precision) -> (x as the device reads it, table, box) the GPU tests use"""
+    if "states" not in _cache:
+        out = {}
+        sa, ta = system_a()
+        sb, tb, _ = system_b()
+        for p in PRECISIONS:
+            out["A", p] = (stored(sa.positions, p)["x"], ta, BOX_A)
+            out["A perturbed", p] = (stored(perturbed_water(), p)["x"], ta, BOX_A)
+            out["B", p] = (stored(sb.positions, p)["x"], tb, BOX_B)
+            out["B four", p] = (stored(sb.positions, p)["x"], tb, BOX_B_FOUR)
+            out["B more", p] = (stored(sb.positions, p)["x"], tb, BOX_B_MORE)
+        _cache["states"] = out
+    return _cache["states"]
+
+
+def evaluated(name, precision, dtype):
+    key = ("eval", name, precision, np.dtype(dtype).name)
+    if key not in _cache:
+        x, table, box = states()[name, precision]
+        _cache[key] = (pair_terms(x, table, box, dtype), exception_terms(x, table, dtype))
+    return _cache[key]
+
+
+# ---------------------------------------------------------------------------
+# the systems have the shapes the kernels can go wrong at
+# ---------------------------------------------------------------------------
+def test_system_a_is_the_water_box_with_drude_on_oxygen():
+    s, table = system_a()
+    assert s.num_particles == 1080 and cells_per_edge(BOX_A) == (4, 4, 4)
+    assert np.array_equal(s.positions[0::5], s.positions[1::5])                  # r = 0 between D and O: excluded, never evaluated
+    assert len(table[4]) == 216 * 10 and not np.any(table[5][:, 0]) and not np.any(table[5][:, 2])
+
+
+def test_system_b_has_the_shapes_the_kernels_can_go_wrong_at():
+    s, table, info = system_b()
+    n = s.num_particles
+    x = s.positions
+    assert n <= 800 and n % 64 != 0
+    assert cells_per_edge(BOX_B) == (2, 3, 4) and cells_per_edge(BOX_B_FOUR) == (2, 3, 3) and cells_per_edge(BOX_B_MORE) == (2, 3, 5)
+    assert BOX_B_FOUR[2] == 4 * CUTOFF
+    for p in PRECISIONS:
+        xs = stored(x, p)["x"]
+        cells = cell_of(xs, BOX_B)
+        count = np.bincount(cells, minlength=24)
+        assert (count == 0).any() and count.max() > 64                           # an empty cell; one that needs the chunk loop
+        assert np.all(cells[info["cluster"]] == 0) and count[0] >= 75
+        # on a cell face and on a box face, exactly
+        assert xs[info["cell_face"], 2] / BOX_B[2] * 4 == 1.0 and xs[info["box_face"], 2] == BOX_B[2] and xs[info["box_face"], 0] == 0.0
+        assert cells[info["cell_face"]] // 6 == 1 and cells[info["box_face"]] // 6 == 0
+        # more than a box length outside, and negative coordinates
+        far = xs[list(info["far"])]
+        assert far[0, 0] < -BOX_B[0] and far[0, 2] < 0 and far[1, 1] > 2 * BOX_B[1]
+        pt = evaluated("B", p, np.float64)[0]
+        # the constructed pairs straddle the cell face z = 1.125: one inside the cutoff, one outside
+        i, j = info["inside"]
+        k, m = info["outside"]
+        assert cells[i] // 6 == 0 and cells[j] // 6 == 1 and cells[k] // 6 == 0 and cells[m] // 6 == 1
+        assert np.any((pt["a"] == i) & (pt["b"] == j)) and not np.any((pt["a"] == k) & (pt["b"] == m))
+        r_in, r_out = np.linalg.norm(xs[i] - xs[j]), np.linalg.norm(xs[k] - xs[m])
+        assert 0.5e-6 < 1 - r_in < 1.5e-6 and 0.5e-6 < r_out - 1 < 1.5e-6
+        # nobody near the lonely ion; no pair closer than 0.1 nm that is not excluded
+        assert not np.any(pt["a"] == info["lonely"]) and not np.any(pt["b"] == info["lonely"])
+        assert pt["r"].min() > 0.1
+    nex = np.bincount(table[4].ravel(), minlength=n)
+    assert nex[info["hub"]] == 2 * HUB_ARMS >= 20
+    assert np.any((table[5][:, 0] != 0) & (table[5][:, 2] != 0)) and np.any((table[5][:, 0] == 0) & (table[5][:, 2] == 0))
+
+
+def test_no_state_has_a_pair_at_the_cutoff():
+    """the CONDITION of the docstring, on every state the GPU tests use; twin and reference then take the same pairs"""
+    for (name, p), (x, table, box) in states().items():
+        n = len(x)
+        d = x[:, None, :] - x[None, :, :]
+        d -= np.asarray(box) * np.rint(d / np.asarray(box))
+        r2 = (d * d).sum(-1)[~excluded_matrix(n, table[4])]
+        gap = np.abs(r2 - CUTOFF ** 2).min()
+        assert gap >= 1e-9 * CUTOFF ** 2, (name, p, gap)
+        t, r = evaluated(name, p, np.float64)[0], evaluated(name, p, L)[0]
+        assert np.array_equal(t["a"], r["a"]) and np.array_equal(t["b"], r["b"])
+
+
+# ---------------------------------------------------------------------------
+# the reference against finite differences of its own energy, and against the oracle's water force field
+# ---------------------------------------------------------------------------
+def small_system():
+    rng = np.random.default_rng(3)
+    n = 14
+    while True:
+        x = rng.uniform(-1.0, 4.0, (n, 3))
+        f = NonbondedForce()
+        for i in range(n):
+            f.addParticle(rng.uniform(-1, 1), rng.uniform(0.2, 0.35), rng.uniform(0.1, 0.9))
+        f.addException(0, 1, 0.3, 0.28, 0.5)
+        f.addException(2, 3, -0.2, 0.3, 0.0)
+        f.addException(4, 5, 0.0, 0.31, 0.7)
+        f.addException(6, 7, 0.0, 1.0, 0.0)
+        f.setNonbondedMethod(f.CutoffPeriodic)
+        box = (2.2, 2.6, 3.1)
+        t = pair_terms(x, f.tables(), box, L)
+        if t["r"].min() > 0.22 and np.abs(t["r"] - 1.0).min() > 1e-3 and len(t["a"]) > 40:
+            return x, f, box
+
+
+@pytest.mark.parametrize("kind", ("pair coulomb", "pair lj", "exception"))
+def test_forces_against_finite_differences_of_the_energy(kind):
+    x, f, box = small_system()
+    method, rc, eps, par, ep, ex = f.tables()
+    par, ex = par.copy(), ex.copy()
+    if kind == "pair coulomb":
+        par[:, 2] = 0
+        ex[:, 0] = ex[:, 2] = 0
+    elif kind == "pair lj":
+        par[:, 0] = 0
+        ex[:, 0] = ex[:, 2] = 0
+    else:
+        par[:, 0] = par[:, 2] = 0
+    table = (method, rc, eps, par, ep, ex)
+    force, _, _ = reference_forces(x, table, box)
+    assert np.abs(force).max() > 1.0
+    h = L(1e-6)
+    worst = L(0)
+    for i in range(len(x)):
+        for k in range(3):
+            e = []
+            for sign in (1, -1):
+                y = x.astype(L)
+                y[i, k] += sign * h
+                e.append(sum(reference_forces(y, table, box)[1]))
+            worst = max(worst, abs(-(e[0] - e[1]) / (2 * h) - force[i, k]))
+    print(f"{kind}: forces off the central differences by at most {float(worst / np.abs(force).max()):.2e} of the largest")
+    assert worst <= 1e-8 * np.abs(force).max()
+
+
+def test_the_reference_is_the_oracles_water_force_field():
+    s, table = system_a()
+    x = perturbed_water()
+    f, e, mag = reference_forces(x, table, BOX_A)
+    kd = L(100000.0 * 4.184)
+    o, d, h1, h2, m = (np.arange(i, len(x), 5) for i in range(5))
+    spring = kd * (x[d].astype(L) - x[o].astype(L))
+    f[d] -= spring
+    f[o] += spring
+    for w, to in zip(wts.W, (o, h1, h2)):
+        f[to] += L(w) * f[m]
+    f[m] = 0
+    e_total = sum(e) + (L(0.5) * kd * ((x[d].astype(L) - x[o].astype(L)) ** 2).sum())
+    f_oracle, e_oracle = water_forces(x, wts.BOX)
+    off = np.abs(f - f_oracle).max() / np.abs(f_oracle).max()
+    print(f"reference against oracle/water_ff.c: forces {float(off):.2e} of the largest, energy {float(e_total):.6f} against {e_oracle:.6f}")
+    assert off <= 1e-9
+    assert abs(e_total - e_oracle) <= 1e-9 * float(sum(mag))
+
+
+# ---------------------------------------------------------------------------
+# twin against reference
+# ---------------------------------------------------------------------------
+def margins():
+    if "margins" not in _cache:
+        worst = 0.0
+        for (name, p) in states():
+            for t, r in zip(evaluated(name, p, np.float64), evaluated(name, p, L)):
+                if len(t["c"]):
+                    worst = max(worst, float((np.abs(t["c"].astype(L) - r["c"]) * r["r"] / r["scale"]).max()))
+        _cache["margins"] = worst
+    return _cache["margins"]
+
+
+def test_the_margin_between_twin_and_reference():
+    m = margins()
+    print(f"twin against reference: {m:.3e} of a pair's uncancelled |dE/dr|; MEASURED_MARGIN {MEASURED_MARGIN:.1e}, GATE {GATE:.1e}")
+    assert MEASURED_MARGIN / 4 < m <= MEASURED_MARGIN
+
+
+@pytest.mark.parametrize("name", ("A", "B"))
+def test_a_pairs_two_shares_cancel_exactly_in_the_twin(name):
+    x, table, box = states()[name, "mixed"]
+    for t in (pair_terms(x, table, box, np.float64), exception_terms(x, table, np.float64)):
+        share = np.rint((t["c"][:, None] * t["d"]) * FIXED).astype(np.int64)
+        order = np.lexsort((t["b"], t["a"])), np.lexsort((t["a"], t["b"]))
+        assert np.array_equal(t["a"][order[0]], t["b"][order[1]]) and np.array_equal(share[order[0]], -share[order[1]])
+    total = twin_integers(x, table, box)
+    assert np.array_equal(total.sum(0), np.zeros(3, np.int64)) and np.any(total != 0)
+
+
+# ---------------------------------------------------------------------------
+# tgnh_set_nonbonded_force on a host-only handle
+# ---------------------------------------------------------------------------
+def counts(top):
+    out = (C.c_int * 3)()
+    assert top.lib.tgnh_get_num_nonbonded_terms(top.h, out) == _lib.TGNH_OK
+    return tuple(out)
+
+
+def refused(top, table, match, status=_lib.ERR_ARG):
+    before = counts(top)
+    with pytest.raises(TgnhError, match=match) as e:
+        NonbondedForces(top, table)
+    assert e.value.status == status
+    assert counts(top) == before                                 # a refused table changes nothing
+
+
+def test_accepted_tables_and_the_counts():
+    s, table, info = system_b()
+    top = HostTopology(s, integrator())
+    assert counts(top) == (0, 0, 0)
+    f = NonbondedForces(top, table)
+    ne = len(table[4])
+    ev = int(((table[5][:, 0] != 0) | (table[5][:, 2] != 0)).sum())
+    assert f.num_terms == (s.num_particles, ne, ev) == counts(top) and 0 < ev < ne
+    NonbondedForces(top, table[:4] + (table[4][:5], table[5][:5]))               # a second table replaces the first
+    assert counts(top)[:2] == (s.num_particles, 5)
+    f.clear()
+    assert counts(top) == (0, 0, 0)
+    f = NonbondedForces(top, table)
+    NonbondedForces(top)                                         # nothing at all clears too
+    assert counts(top) == (0, 0, 0)
+    f = NonbondedForces(top, table)
+    for call in (f.compute, lambda: f.compute(energy=True), f.energy):
+        with pytest.raises(TgnhError, match="host-only") as e:
+            call()
+        assert e.value.status == _lib.ERR_STATE
+    assert top.lib.tgnh_get_nonbonded_energy(top.h, None, None) == _lib.ERR_ARG
+    assert top.lib.tgnh_get_num_nonbonded_terms(top.h, None) == _lib.ERR_ARG
+    assert top.lib.tgnh_set_nonbonded_force(None, None) == _lib.ERR_ARG
+    top.close()
+
+
+def test_refusals():
+    s, table, info = system_b()
+    method, rc, eps, par, ep, ex = table
+    n = s.num_particles
+    top = HostTopology(s, integrator())
+    NonbondedForces(top, table)
+
+    def changed(which, index, value):
+        arrays = [par.copy(), ep.copy(), ex.copy()]
+        arrays[which][index] = value
+        return (method, rc, eps) + tuple(arrays)
+
+    refused(top, changed(0, (7, 0), np.nan), "particle 7: a parameter is not finite")
+    refused(top, changed(0, (7, 1), np.inf), "particle 7: a parameter is not finite")
+    refused(top, changed(0, (7, 1), -0.1), "particle 7: sigma is negative")
+    refused(top, changed(0, (9, 2), -1e-3), "particle 9: epsilon is negative")
+    refused(top, changed(2, (3, 0), np.nan), "exception 3: a parameter is not finite")
+    refused(top, changed(2, (3, 1), -1.0), "exception 3: sigma is negative")
+    refused(top, changed(2, (3, 2), -1.0), "exception 3: epsilon is negative")
+    refused(top, changed(1, (3, 1), n), f"exception 3: index {n} out of range")
+    refused(top, changed(1, (3, 0), -1), "exception 3: index -1 out of range")
+    refused(top, changed(1, 3, (ep[3, 0], ep[3, 0])), f"exception 3 names particle {ep[3, 0]} twice")
+    refused(top, changed(1, 12, ep[5][::-1]), "exception 12 names the pair of exception 5 again")
+    refused(top, (method, rc, eps, par[:-1], ep, ex), f"{n - 1} particles for a handle of {n} slots")
+    for bad in (0.0, -1.0, np.nan, np.inf):
+        refused(top, (method, bad, eps, par, ep, ex), "the cutoff is not finite or not positive")
+    for bad in (0.5, np.nan, np.inf):
+        refused(top, (method, rc, bad, par, ep, ex), "dielectric is not finite or below 1")
+    for bad in (NonbondedForce.NoCutoff, NonbondedForce.CutoffNonPeriodic, 3, 4, 5):
+        refused(top, (bad, rc, eps, par, ep, ex), "only TGNH_NB_CUTOFF_PERIODIC", _lib.ERR_UNSUPPORTED)
+    # the descriptor itself: a wrong struct_size, NULL arrays with positive counts, a negative count
+    from openmm_drudenose_amd.forces import _NonbondedDesc
+    before = counts(top)
+    good = dict(struct_size=C.sizeof(_NonbondedDesc), method=2, cutoff=1.0, reaction_field_dielectric=78.3, num_particles=n,
+                particles=par.ctypes.data, num_exceptions=len(ep), exception_particles=ep.ctypes.data, exception_params=ex.ctypes.data)
+    for change, text in ((dict(struct_size=8), "struct_size 8"), (dict(particles=None), "null array"), (dict(exception_params=None), "null array"),
+                         (dict(exception_particles=None), "null array"), (dict(num_exceptions=-1), "negative count")):
+        d = _NonbondedDesc(**{**good, **change})
+        assert top.lib.tgnh_set_nonbonded_force(top.h, C.byref(d)) == _lib.ERR_ARG
+        assert text in top.lib.tgnh_last_error().decode() and counts(top) == before
+    # more exceptions than 32-bit offsets take: decided from the count alone, before any row is read (the arrays are the small ones)
+    d = _NonbondedDesc(**{**good, "num_exceptions": 2 ** 30 + 1})
+    assert top.lib.tgnh_set_nonbonded_force(top.h, C.byref(d)) == _lib.ERR_UNSUPPORTED
+    assert "32-bit offsets" in top.lib.tgnh_last_error().decode() and counts(top) == before
+    d = _NonbondedDesc(**{**good, "num_exceptions": 2 ** 30 - 1, "cutoff": -1.0})                 # (under the limit: the next check answers)
+    assert top.lib.tgnh_set_nonbonded_force(top.h, C.byref(d)) == _lib.ERR_ARG and counts(top) == before
+    # a handle that is one shard of several: an all-reduce hook is attached
+    hook = _lib.ALLREDUCE_FN(lambda user, count, data, stream: 0)
+    assert top.lib.tgnh_set_allreduce(top.h, hook, None) == _lib.TGNH_OK
+    refused(top, table, "one shard of several", _lib.ERR_UNSUPPORTED)
+    assert top.lib.tgnh_set_allreduce(top.h, _lib.ALLREDUCE_FN(), None) == _lib.TGNH_OK           # detached: the same table is taken
+    assert top.lib.tgnh_set_nonbonded_force(top.h, C.byref(_NonbondedDesc(**good))) == _lib.TGNH_OK
+    top.close()
+
+
+def test_the_table_class_round_trips_its_parameters():
+    f = NonbondedForce()
+    assert (f.NoCutoff, f.CutoffNonPeriodic, f.CutoffPeriodic) == (0, 1, 2)
+    assert f.getNonbondedMethod() == f.NoCutoff and f.getCutoffDistance() == 1.0 and f.getReactionFieldDielectric() == 78.3
+    assert [f.addParticle(0.1 * i, 0.3, 0.5) for i in range(4)] == [0, 1, 2, 3] and f.getNumParticles() == 4
+    f.setParticleParameters(2, -0.5, 0.25, 0.75)
+    assert f.getParticleParameters(2) == (-0.5, 0.25, 0.75) and f.getParticleParameters(1) == (0.1, 0.3, 0.5)
+    assert f.addException(0, 1, 0.0, 1.0, 0.0) == 0 and f.addException(3, 2, 0.25, 0.3, 0.1) == 1 and f.getNumExceptions() == 2
+    with pytest.raises(ValueError, match="already an exception"):
+        f.addException(1, 0, 0.5, 0.3, 0.2)
+    assert f.addException(1, 0, 0.5, 0.3, 0.2, replace=True) == 0 and f.getExceptionParameters(0) == (1, 0, 0.5, 0.3, 0.2)
+    f.setExceptionParameters(1, 1, 3, 0.0, 0.2, 0.9)
+    assert f.getExceptionParameters(1) == (1, 3, 0.0, 0.2, 0.9)
+    with pytest.raises(ValueError, match="already an exception"):
+        f.setExceptionParameters(1, 0, 1, 0.0, 0.2, 0.9)
+    assert f.addException(2, 3, 0.0, 1.0, 0.0) == 2                              # the pair row 1 left is free again
+    for bad in (lambda: f.getParticleParameters(4), lambda: f.getExceptionParameters(-1), lambda: f.setParticleParameters(9, 0, 0, 0)):
+        with pytest.raises(IndexError):
+            bad()
+    f.setNonbondedMethod(f.CutoffPeriodic); f.setCutoffDistance(0.9); f.setReactionFieldDielectric(60.0)
+    with pytest.raises(ValueError):
+        f.setNonbondedMethod(7)
+    method, rc, eps, par, ep, ex = f.tables()
+    assert (method, rc, eps) == (2, 0.9, 60.0) and par.shape == (4, 3) and ep.dtype == np.int32 and ep.tolist() == [[1, 0], [1, 3], [2, 3]]
+    assert ex.shape == (3, 3) and par.dtype == ex.dtype == np.float64
+    assert [a.shape for a in NonbondedForce().tables()[3:]] == [(0, 3), (0, 2), (0, 3)]
+
+
+def test_create_exceptions_from_bonds_on_a_branched_chain():
+    """test_bonded_forces.py's chain: 0-1-2-3-4-5 with 6 and 7 on atom 2"""
+    f = NonbondedForce()
+    rng = np.random.default_rng(0)
+    for i in range(9):                                           # (atom 8 is in no bond)
+        f.addParticle(rng.uniform(-1, 1), 0.2 + 0.01 * i, 0.1 * (i + 1))
+    f.addException(0, 3, 9.0, 9.0, 9.0)                          # a 1-4 pair that has an exception already keeps it
+    f.createExceptionsFromBonds(CHAIN_BONDS, 0.5, 0.25)
+    got = {(min(r[0], r[1]), max(r[0], r[1])): r[2:] for r in (f.getExceptionParameters(k) for k in range(f.getNumExceptions()))}
+    one = {(min(a, b), max(a, b)) for a, b in CHAIN_BONDS}
+    two = {(0, 2), (1, 3), (1, 6), (1, 7), (3, 6), (3, 7), (6, 7), (2, 4), (3, 5)}
+    three = {(0, 3), (0, 6), (0, 7), (1, 4), (2, 5), (4, 6), (4, 7)}
+    assert set(got) == one | two | three
+    for pair in one | two:
+        assert got[pair] == (0.0, 1.0, 0.0)
+    assert got[0, 3] == (9.0, 9.0, 9.0)
+    for i, j in three - {(0, 3)}:
+        (qi, si, ei), (qj, sj, ej) = f.getParticleParameters(i), f.getParticleParameters(j)
+        assert got[i, j] == (0.5 * qi * qj, 0.5 * (si + sj), 0.25 * (ei * ej) ** 0.5)
+    with pytest.raises(IndexError):
+        f.createExceptionsFromBonds([(0, 9)], 1.0, 1.0)
+
+
+def test_shape_refusals_make_no_library_call():
+    s, table, info = system_b()
+    method, rc, eps, par, ep, ex = table
+    bad = [(method, rc, eps, par[:, :2], ep, ex), (method, rc, eps, par.ravel(), ep, ex), (method, rc, eps, par, ep[:, :1], ex),
+           (method, rc, eps, par, ep, ex[:5]), (method, rc, eps, par, ep, ex[:, :2]), (method, rc, eps, par, ep.ravel(), ex),
+           (method, rc, eps, par, ep), (par, ep, ex)]
+    for t in bad:
+        owner = _Owner()
+        with pytest.raises(TgnhError, match="set_nonbonded_force: ") as e:
+            NonbondedForces(owner, t)
+        assert e.value.status == _lib.ERR_ARG and owner.lib.calls == []
+    owner = _Owner()                                             # and what fits makes exactly one
+    f = NonbondedForces(owner, table)
+    assert [c[0] for c in owner.lib.calls] == ["tgnh_set_nonbonded_force"]
+    f.clear()
+    assert owner.lib.calls[1] == ("tgnh_set_nonbonded_force", (owner.h, None))
+    seen = []
+    owner.force = type("F", (), {"zero_": lambda self: seen.append("zero"), "data_ptr": lambda self: 64})()
+    both = f.then(lambda ctx: seen.append("then"))
+    both(owner)
+    assert seen == ["zero", "then"] and owner.lib.calls[2] == ("tgnh_compute_nonbonded_force", (owner.h, 64, 0, None))
