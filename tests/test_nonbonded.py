@@ -55,14 +55,15 @@ def excluded_matrix(n, exc_particles):
     return m
 
 
-def pair_terms(x, table, box, dtype):
+def pair_terms(x, table, box, dtype, pairs=None):
     """The header's PAIRS, for every ORDERED pair (a, b) the loop takes and that is inside the cutoff -> dict of arrays: a, b (slots),
     d [m, 3], c, e_c, e_lj, scale (the uncancelled |dE/dr|).  dtype float64: the twin, operation for operation; longdouble: the
-    reference."""
+    reference.  pairs = (a, b): only these ordered pairs, none of them excluded, go through the same lines (candidate_pairs and
+    without_excluded below give them where n x n is too many)."""
     method, rc, eps_rf, par, ep, ex = table
     n = len(x)
     krf, crf = rf_constants(rc, eps_rf, dtype)
-    a, b = np.nonzero(~excluded_matrix(n, ep))
+    a, b = np.nonzero(~excluded_matrix(n, ep)) if pairs is None else pairs
     xs, box = x.astype(dtype), np.asarray(box, dtype)
     d = xs[a] - xs[b]
     t = d / box
@@ -113,10 +114,10 @@ def exception_terms(x, table, dtype):
                 scale=np.abs(qq) * (inv * inv) + (e4 * (dtype(6.0) * s6 + dtype(12.0) * s12)) * inv)
 
 
-def twin_integers(x, table, box):
+def twin_integers(x, table, box, pairs=None):
     """-> [n, 3] int64: what tgnh_compute_nonbonded_force adds to the buffer, bit for bit"""
     out = np.zeros((len(x), 3), np.int64)
-    for t in (pair_terms(x, table, box, np.float64), exception_terms(x, table, np.float64)):
+    for t in (pair_terms(x, table, box, np.float64, pairs), exception_terms(x, table, np.float64)):
         np.add.at(out, t["a"], np.rint((t["c"][:, None] * t["d"]) * FIXED).astype(np.int64))
     return out
 
@@ -131,6 +132,78 @@ def reference_forces(x, table, box):
     once, first = p["a"] < p["b"], e["role"] == 0
     terms = (p["e_c"][once], p["e_lj"][once], e["e_c"][first], e["e_lj"][first])
     return f, [t.sum() for t in terms], [np.abs(t).sum() for t in terms]
+
+
+# ---------------------------------------------------------------------------
+# a pair search of the tests' own, for systems the n x n matrix does not reach
+# ---------------------------------------------------------------------------
+SEARCH_SLACK = 1e-6              # candidates up to rc^2 (1 + this): pair_terms decides who is inside, by its own lines
+
+
+def candidate_pairs(x, box, rc):
+    """Every ORDERED pair (a, b), a != b, whose minimum-image distance is below the cutoff, and a few just beyond it
+    (r2 < rc^2 (1 + SEARCH_SLACK)): pair_terms makes the cut itself -> a, b in lexicographic order, r2 in fp64.  A grid of
+    floor(L / rc) cells per edge -- a cell is at least one cutoff wide, so a pair inside the cutoff lies in the same or in adjacent
+    cells --, one cell offset at a time, the neighbour cell's members expanded with np.repeat: memory stays at n x the largest
+    cell.  Nothing here is the kernel's: not its 1.001 rc, not cell_of, not its min_image."""
+    x, box = np.asarray(x, np.float64), np.asarray(box, np.float64)
+    n = len(x)
+    ng = np.maximum(1, np.floor(box / rc).astype(np.int64))
+    s = x / box
+    s = s - np.floor(s)
+    c3 = np.minimum((s * ng).astype(np.int64), ng - 1)
+    flat = (c3[:, 0] * ng[1] + c3[:, 1]) * ng[2] + c3[:, 2]
+    order = np.argsort(flat, kind="stable")
+    count = np.bincount(flat, minlength=int(ng.prod()))
+    first = np.concatenate([[0], np.cumsum(count)])
+    out_a, out_b, out_r2 = [], [], []
+    offsets = [sorted({(o % int(g)) for o in (-1, 0, 1)}) for g in ng]          # 1, 2 or 3 distinct cells per edge
+    for ox in offsets[0]:
+        for oy in offsets[1]:
+            for oz in offsets[2]:
+                other = (((c3[:, 0] + ox) % ng[0]) * ng[1] + (c3[:, 1] + oy) % ng[1]) * ng[2] + (c3[:, 2] + oz) % ng[2]
+                m = count[other]
+                a = np.repeat(np.arange(n), m)
+                within = np.arange(m.sum()) - np.repeat(np.cumsum(m) - m, m)
+                b = order[np.repeat(first[other], m) + within]
+                d = x[a] - x[b]
+                d -= box * np.rint(d / box)
+                r2 = (d * d).sum(1)
+                keep = (r2 < rc * rc * (1.0 + SEARCH_SLACK)) & (a != b)
+                out_a.append(a[keep]); out_b.append(b[keep]); out_r2.append(r2[keep])
+    a, b, r2 = np.concatenate(out_a), np.concatenate(out_b), np.concatenate(out_r2)
+    order = np.lexsort((b, a))
+    return a[order], b[order], r2[order]
+
+
+def without_excluded(a, b, n, exc_particles):
+    """the ordered pairs (a, b) that no exception row names, in either order -> the mask"""
+    ep = np.asarray(exc_particles, np.int64).reshape(-1, 2)
+    named = np.concatenate([ep[:, 0] * n + ep[:, 1], ep[:, 1] * n + ep[:, 0]])
+    return ~np.isin(a.astype(np.int64) * n + b, named)
+
+
+def searched_pairs(x, table, box):
+    """-> (a, b) for pair_terms' `pairs`, and the smallest |r2 - rc^2| / rc^2 over the candidates (the CONDITION's figure)"""
+    rc, ep = table[1], table[4]
+    a, b, r2 = candidate_pairs(x, box, rc)
+    keep = without_excluded(a, b, len(x), ep)
+    a, b, r2 = a[keep], b[keep], r2[keep]
+    return (a, b), (float(np.abs(r2 - rc * rc).min() / (rc * rc)) if len(r2) else np.inf)
+
+
+def assert_the_search_is_the_all_pairs_path(x, table, box):
+    """pair_terms over the searched pairs against pair_terms over the n x n matrix: the same a, b, c and d, to the bit, after a
+    lexicographic sort; in fp64 and in fp80"""
+    pairs, gap = searched_pairs(x, table, box)
+    for dtype in (np.float64, L):
+        got, want = pair_terms(x, table, box, dtype, pairs), pair_terms(x, table, box, dtype)
+        og, ow = np.lexsort((got["b"], got["a"])), np.lexsort((want["b"], want["a"]))
+        assert len(want["a"]) > 0 and len(pairs[0]) >= len(want["a"])
+        for key in ("a", "b", "c", "d"):
+            assert np.array_equal(got[key][og], want[key][ow]), key
+    assert np.array_equal(twin_integers(x, table, box, pairs), twin_integers(x, table, box))
+    return gap
 
 
 def stored(x, precision):
@@ -392,6 +465,18 @@ def test_no_state_has_a_pair_at_the_cutoff():
         assert gap >= 1e-9 * CUTOFF ** 2, (name, p, gap)
         t, r = evaluated(name, p, np.float64)[0], evaluated(name, p, L)[0]
         assert np.array_equal(t["a"], r["a"]) and np.array_equal(t["b"], r["b"])
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("name", ("B", "B four", "B more"))
+def test_the_pair_search_is_the_all_pairs_path_on_system_b(name, precision):
+    """What lets tests/test_library_forces_at_size_gpu.py trust the search: on system B (exclusions, a crowded cell, molecules
+    whole box lengths outside, 2 and 3 search cells along an edge) it gives pair_terms the pairs the matrix gives it."""
+    x, table, box = states()[name, precision]
+    gap = assert_the_search_is_the_all_pairs_path(x, table, box)
+    assert gap >= 1e-9
+    # and the search's own grid is not the kernel's: floor(L / rc) against floor(L / 1.001 rc)
+    assert tuple(int(np.floor(e / CUTOFF)) for e in BOX_B_FOUR) == (2, 3, 4) and cells_per_edge(BOX_B_FOUR) == (2, 3, 3)
 
 
 # ---------------------------------------------------------------------------
