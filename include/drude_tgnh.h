@@ -781,7 +781,11 @@ tgnh_status tgnh_set_thermostat_state(tgnh_handle h, int which, void* stream, co
  * reading them (0: they read them), 13 / 14 the patterns of the two, 64 words each, 15 the descriptor masses behind the
  * wave patterns' words, 64 doubles per pattern in 14's order, each as two int32 (a wave pattern is interned by words AND
  * masses; empty where 14 holds its one placeholder row), 16 one word: 1 where every wave tile is patterned and every slot's
- * mass is its pattern entry's bit for bit -- the host's half of what qualifies a handle for the velocity planes --, else 0.
+ * mass is its pattern entry's bit for bit -- the host's half of what qualifies a handle for the velocity planes --, else 0,
+ * 17 where the velocity planes keep a slot (they hold the massive slots only): the stride of a plane in words, the number
+ * of bases B (wave tiles + 1), the B bases -- the first word of each wave tile's segment, a multiple of 16, the last one the
+ * stride again --, then 64 offsets per wave pattern in 14's order, by lane: the massive slots of the tile before that lane;
+ * a massive slot's word is base[tile] + offset[pattern][lane].  0, 0 and nothing else where 16 answers 0.
  * All read-only, all answered by a host-only handle. */
 tgnh_status tgnh_get_topology_len(tgnh_handle h, int which, int* len);
 tgnh_status tgnh_get_topology(tgnh_handle h, int which, int32_t* out);

@@ -80,6 +80,11 @@ struct tgnh_context {
         std::vector<uint32_t> pattern, wpattern;      // 64 words per pattern
         std::vector<double> wpat_mass;                // beside wpattern: the descriptor masses of a wave pattern's slots, 64 per pattern
         bool wpat_all_uniform = false;                // every wave tile is patterned, and every slot's mass is its pattern entry's
+        // wpat_all_uniform: where the velocity planes keep a MASSIVE slot (a massless one has no word there) -- word
+        // wtile_base[tile] + wpat_off[pattern * 64 + lane] of each plane.  wtile_base: [num_wtiles + 1], every entry a multiple of
+        // 16 words (a 128-byte line of 8-byte words), the last one the planes' stride; wpat_off: beside wpattern, per LANE (not per
+        // place in the period), the massive slots of the tile before that lane.  Empty otherwise.
+        std::vector<uint32_t> wtile_base, wpat_off;
         int num_wtiles = 0;
         tgnh::DeviceBuf<uint32_t> d_meta, d_wmeta, d_tile_pat, d_pattern, d_wpattern;
         tgnh::DeviceBuf<int> d_tile_start, d_tile_res;
@@ -268,8 +273,10 @@ struct tgnh_context {
     // The one-launch step's velocities as three planes (tgnh_vplanes.hip): the library's own copy of velm's x, y, z
     // between flushes of a DEFER_SCALE | RESIDENT_STEP sequence.  Owed::planes_live says which of the two holds the velocities.
     struct VelPlanes {
-        tgnh::DeviceBytes d_planes;       // x | y | z of Prec::mixed, stride padded: allocated at create where the handle can take them, never later
+        tgnh::DeviceBytes d_planes;       // x | y | z of Prec::mixed, the massive slots only, stride `stride`: allocated at create where the handle can take them, never later
         tgnh::DeviceBytes d_invm;         // [patterns][64] Prec::mixed: 1 / Topology::wpat_mass (0 for a massless slot), what velm's w must hold
+        tgnh::DeviceBuf<uint32_t> d_base, d_off;    // Topology::wtile_base, wpat_off
+        int stride = 0;                   // words of a plane: wtile_base's last entry
         tgnh::DeviceBuf<uint32_t> d_mismatch;   // the first conversion of a bind ORs 1 in here when some slot's w is not its table entry
         int verdict = 0;                  // of that check: 0 not made yet, 1 the table is velm's w, -1 it is not (the handle stays on velm)
         int streak = 0;                   // one-launch steps in a row since the last settle (enter_planes' hysteresis)

@@ -228,11 +228,15 @@ struct TileArgs {
     const double* st_in;
     double* st_out;
     ChainArgs chain;
-    // wstep_kernel, velocities as planes (tgnh_vplanes.h): vplanes != nullptr = x | y | z of Prec::mixed, stride `padded`, hold the
-    // velocities and velm is neither read nor written; a slot's 1/m is wpat_invm[pattern * PATTERN_WORDS + position in the pattern]
-    // (Prec::mixed, bit for bit velm's w: every tile of such a launch is patterned).  Last, so that no other field moves.
+    // wstep_kernel, velocities as planes (tgnh_vplanes.h): vplanes != nullptr = x | y | z of Prec::mixed, stride `vstride`, hold the
+    // velocities of the MASSIVE slots and velm is neither read nor written; a slot's 1/m is wpat_invm[pattern * PATTERN_WORDS +
+    // position in the pattern] (Prec::mixed, bit for bit velm's w: every tile of such a launch is patterned), and where that is not
+    // 0 its word of a plane is wtile_base[tile] + wpat_off[pattern * PATTERN_WORDS + lane].  Last, so that no other field moves.
     void* vplanes;
     const void* wpat_invm;
+    const uint32_t* wtile_base;    // [num_wtiles + 1], multiples of 16 words; the last entry is vstride
+    const uint32_t* wpat_off;      // [patterns][PATTERN_WORDS], by lane: the massive slots of the tile before it
+    int vstride;
 };
 
 struct BigComArgs {

@@ -194,11 +194,12 @@ static tgnh_status resident_census(tgnh_context* c) {
 // The one-launch step's velocity planes (tgnh_context.h VelPlanes), for a handle that can take them: it steps with wstep_kernel
 // (a whole deferred step over wave tiles: the census above found a grid), every wave tile is patterned and every slot's mass is
 // its pattern entry's -- then 1/m is a function of a lane's place in the pattern and the kernel needs no w per slot.  Allocated
-// here and never later (an allocation inside somebody's stream capture would fail it): 3 x padded x sizeof(mixed), 120 MB for
+// here and never later (an allocation inside somebody's stream capture would fail it): 3 x stride x sizeof(mixed), the stride the
+// box's massive slots with every wave tile's segment padded to a 128-byte line (tgnh_topology.cpp) -- 96 MB for a water box of
 // 5 M slots in mixed precision.  TGNH_VELOCITY_PLANES=0 in the environment keeps a handle on velm (both forms from one build).
 static tgnh_status allocate_velocity_planes(tgnh_context* c) {
     if (const char* e = getenv("TGNH_VELOCITY_PLANES")) if (e[0] == '0') return TGNH_OK;
-    if (!(c->d.flags & TGNH_FLAG_DEFER_SCALE) || c->cfg.wresident_per_cu <= 0 || !c->topo.wpat_all_uniform) return TGNH_OK;
+    if (!(c->d.flags & TGNH_FLAG_DEFER_SCALE) || c->cfg.wresident_per_cu <= 0 || !c->topo.wpat_all_uniform || c->topo.wtile_base.empty()) return TGNH_OK;
     // Single precision stays on velm: there the two kernels do not give the same bits (tgnh_wave_kernels.h, wstep_fn_gb)
     if (c->d.precision == TGNH_PREC_SINGLE) return TGNH_OK;
     // (the census counted work-groups of wstep_kernel: wstep_planes_kernel meets on the same grid, so it must hold as many per compute unit)
@@ -211,7 +212,11 @@ static tgnh_status allocate_velocity_planes(tgnh_context* c) {
     std::vector<float> inv_f(inv.begin(), inv.end());
     HIP_OK(c->vp.d_invm.upload(reinterpret_cast<const unsigned char*>(single ? (const void*)inv_f.data() : (const void*)inv.data()), n * word));
     HIP_OK(c->vp.d_mismatch.alloc(1, true));
-    HIP_OK(c->vp.d_planes.alloc(3 * (size_t)c->d.padded_num_particles * word, true));
+    // the planes hold the massive slots only: a tile's segment at wtile_base[tile], a lane's word wpat_off[pattern][lane] into it
+    c->vp.stride = (int)c->topo.wtile_base.back();
+    HIP_OK(c->vp.d_base.upload(c->topo.wtile_base));
+    HIP_OK(c->vp.d_off.upload(c->topo.wpat_off));
+    HIP_OK(c->vp.d_planes.alloc(3 * (size_t)std::max(c->vp.stride, 1) * word, true));
     return TGNH_OK;
 }
 

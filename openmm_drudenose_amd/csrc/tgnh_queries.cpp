@@ -126,6 +126,8 @@ extern "C" tgnh_status tgnh_get_topology_len(tgnh_handle h, int which, int* len)
     if (which == 14) { *len = (int)h->topo.wpattern.size(); return TGNH_OK; }
     if (which == 15) { *len = 2 * (int)h->topo.wpat_mass.size(); return TGNH_OK; }  // the wave patterns' descriptor masses, 64 doubles each, as pairs of words
     if (which == 16) { *len = 1; return TGNH_OK; }                                   // wpat_all_uniform: every wave tile patterned, every mass its pattern entry's
+    // the velocity planes' layout: the stride of a plane in words, the number of tile bases, the bases, the lane offsets (64 per pattern)
+    if (which == 17) { *len = 2 + (int)h->topo.wtile_base.size() + (int)h->topo.wpat_off.size(); return TGNH_OK; }
     const std::vector<int>* v = topo_vec(h, which);
     if (!v) return fail(TGNH_ERR_ARG, "bad topology array id");
     *len = (int)v->size();
@@ -144,6 +146,13 @@ extern "C" tgnh_status tgnh_get_topology(tgnh_handle h, int which, int32_t* out)
     if (which == 14) return put(h->topo.wpattern.data(), sizeof(uint32_t) * h->topo.wpattern.size());
     if (which == 15) return put(h->topo.wpat_mass.data(), sizeof(double) * h->topo.wpat_mass.size());
     if (which == 16) { *out = h->topo.wpat_all_uniform ? 1 : 0; return TGNH_OK; }
+    if (which == 17) {
+        const std::vector<uint32_t>&base = h->topo.wtile_base, &off = h->topo.wpat_off;
+        out[0] = base.empty() ? 0 : (int32_t)base.back(); out[1] = (int32_t)base.size();
+        if (!base.empty()) std::memcpy(out + 2, base.data(), sizeof(uint32_t) * base.size());
+        if (!off.empty()) std::memcpy(out + 2 + base.size(), off.data(), sizeof(uint32_t) * off.size());
+        return TGNH_OK;
+    }
     const std::vector<int>* v = topo_vec(h, which);
     if (!v) return fail(TGNH_ERR_ARG, "bad topology array id");
     std::copy(v->begin(), v->end(), out);

@@ -416,20 +416,24 @@ extern "C" tgnh_status tgnh_get_resident_kernel(tgnh_handle h, int* which) {
 // ---- wstep_kernel's velocities as three planes (tgnh_vplanes.hip) ----
 // Between the steps of a DEFER_SCALE | RESIDENT_STEP sequence velm is stale by contract (owed.end_pending), and everybody who
 // needs real velocities comes through settle_end.  So between two settles the library may keep the velocities where the kernel
-// moves fewest bytes: x | y | z planes of its own, without the 1/m word (owed.planes_live; VelPlanes in tgnh_context.h).  Both
-// layouts give the same bits: where the velocities live changes no result, only the bytes a step moves.
+// moves fewest bytes: x | y | z planes of its own, without the 1/m word and without the massless slots (owed.planes_live;
+// VelPlanes in tgnh_context.h).  Both layouts give the same bits: where the velocities live changes no result, only the bytes a
+// step moves.
 //
-// Entered by the one-launch step after PLANES_AFTER_STEPS such steps in a row since the last settle.  The two conversions of
-// one stay on the planes move 56 + 88 B per slot (mixed) and a step there saves 24, so a stay pays from its seventh step.  A
-// caller that settles every step never reaches the threshold and never converts; one that settles every 100 steps or more --
-// a reporter -- loses the gain of 8 steps in 100; the worst case, a settle every 10 steps, converts for one step on the planes and is
-// 4 % of its ten steps' bytes slower.  With 4 that worst case is 8 %, with 16 it is 2 % and a stay shorter than 16 steps gains nothing.
+// Entered by the one-launch step after PLANES_AFTER_STEPS such steps in a row since the last settle.  By the bytes (arithmetic, not
+// a measurement; mixed precision, f = the box's share of massive slots, 4/5 for SWM4 water): the two conversions of one stay move
+// (32 + 24 f) + (24 f + 64 f) B per slot -- 121.6 for water, 144 where every slot has mass -- and a step there saves 96 - 72 f
+// of velm's 96 B of V -- 38.4 for water, 24 where every slot has mass --, so a stay pays from its fourth step (water) to its seventh.
+// A caller that settles every step never reaches the threshold and never converts; one that settles every 100 steps or more -- a
+// reporter -- loses the gain of 8 steps in 100; the worst case, a settle every 10 steps, converts for one step on the planes and is
+// 4 % of its ten steps' bytes slower.  The threshold stays where the full planes put it (tests read it).
 constexpr int PLANES_AFTER_STEPS = 8;
 
 // planes -> velm (no Timed scope: tests/test_launch_structure_gpu.py counts the scopes of a settle)
 static tgnh_status leave_planes(tgnh_handle h, hipStream_t s) {
     if (!h->owed.planes_live) return TGNH_OK;
-    HIP_OK(launch_planes_to_velm(h->d.precision, h->vp.d_planes, h->bound.velm, h->d.num_particles, h->d.padded_num_particles, s));
+    HIP_OK(launch_planes_to_velm(h->d.precision, h->vp.d_planes, h->bound.velm, h->topo.d_wave_tile, h->topo.num_wtiles, h->vp.d_invm,
+                                 h->vp.d_base, h->vp.d_off, h->vp.stride, s));
     h->owed.planes_live = false;
     return TGNH_OK;
 }
@@ -446,7 +450,7 @@ static tgnh_status enter_planes(tgnh_handle h, hipStream_t s) {
     const bool check = vp.verdict == 0;
     if (check) HIP_OK(hipMemsetAsync(vp.d_mismatch, 0, sizeof(uint32_t), s));
     HIP_OK(launch_velm_to_planes(h->d.precision, h->bound.velm, vp.d_planes, h->topo.d_wave_tile, h->topo.num_wtiles, vp.d_invm,
-                                 h->d.padded_num_particles, check ? vp.d_mismatch.get() : nullptr, s));
+                                 vp.d_base, vp.d_off, vp.stride, check ? vp.d_mismatch.get() : nullptr, s));
     if (check) {
         uint32_t differs = 1;
         HIP_OK(hipMemcpyAsync(&differs, vp.d_mismatch, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -481,7 +485,10 @@ static tgnh_status run_resident(tgnh_handle h, hipStream_t s, int kind) {
     if (wstep && kind == 0) { tgnh_status rc = enter_planes(h, s); if (rc) return rc; }
     else if (h->owed.planes_live) return fail(TGNH_ERR_STATE, "internal: a launch that reads velm while the velocities live in the planes");
     TileArgs a = tile_args(h, nullptr);
-    if (h->owed.planes_live) { a.vplanes = h->vp.d_planes; a.wpat_invm = h->vp.d_invm; h->vp.stream = s; }
+    if (h->owed.planes_live) {
+        a.vplanes = h->vp.d_planes; a.wpat_invm = h->vp.d_invm; a.wtile_base = h->vp.d_base; a.wpat_off = h->vp.d_off; a.vstride = h->vp.stride;
+        h->vp.stream = s;
+    }
     const int ops2 = step_kind_ops2(kind);
     if ((ops2 & OP_POSDELTA) && !h->bound.pos_delta) return fail(TGNH_ERR_STATE, "posDelta buffer not bound");
     const bool hw = a.hardwall != 0 && (ops2 & (OP_DRIFT | OP_MOVE));

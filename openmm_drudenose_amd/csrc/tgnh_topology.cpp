@@ -360,6 +360,36 @@ tgnh_status build_topology(tgnh_context* c, const tgnh_desc* d) {
             }
             if (!c->topo.wtile_pat[t]) c->topo.wpat_all_uniform = false;
         }
+        // Where the velocity planes keep a slot (tgnh_context.h Topology::wtile_base, wpat_off): the massive slots only, packed in
+        // slot order, every tile's segment on a 128-byte line of the plane (16 words of 8 bytes: the planes exist in mixed and
+        // double precision).  A lane's offset counts the massive slots of its tile before it: a function of pattern and lane.
+        c->topo.wtile_base.clear(); c->topo.wpat_off.clear();
+        if (c->topo.wpat_all_uniform) {
+            const size_t patterns = c->topo.wpattern.size() / PATTERN_WORDS;
+            std::vector<char> made(patterns, 0);
+            c->topo.wpat_off.assign(patterns * PATTERN_WORDS, 0u);
+            c->topo.wtile_base.assign((size_t)c->topo.num_wtiles + 1, 0u);
+            uint64_t base = 0;
+            for (int t = 0; t < c->topo.num_wtiles; t++) {
+                const int ws = c->topo.wave_tile[t].x, n = c->topo.wave_tile[t + 1].x - ws;
+                const uint32_t P = c->topo.wtile_pat[t] & 255u, id = c->topo.wtile_pat[t] >> 8;
+                if (!made[id]) {
+                    uint32_t before = 0;
+                    for (uint32_t lane = 0; lane < (uint32_t)PATTERN_WORDS; lane++) {
+                        c->topo.wpat_off[(size_t)id * PATTERN_WORDS + lane] = before;
+                        before += c->topo.wpat_mass[(size_t)id * PATTERN_WORDS + lane % P] != 0.0;
+                    }
+                    made[id] = 1;
+                }
+                uint32_t massive = 0;
+                for (int k = 0; k < n; k++) massive += c->topo.mass[ws + k] != 0.0;
+                c->topo.wtile_base[t] = (uint32_t)base;
+                base = (base + massive + 15u) & ~(uint64_t)15u;
+            }
+            c->topo.wtile_base[c->topo.num_wtiles] = (uint32_t)base;
+            // (the kernels index the third plane with an int, as they index the force buffer's)
+            if (3 * base > (uint64_t)INT32_MAX) { c->topo.wtile_base.clear(); c->topo.wpat_off.clear(); }
+        }
         if (c->topo.pattern.empty()) c->topo.pattern.assign(PATTERN_WORDS, 0u);
         if (c->topo.wpattern.empty()) c->topo.wpattern.assign(PATTERN_WORDS, 0u);
     }

@@ -7,13 +7,17 @@
 
 namespace tgnh {
 
-// planes[c * padded + i] = velm[i].{x, y, z}, i over the slots of the wave tiles wave_tile[0 .. num_wtiles] (device copy: y carries
-// period | pattern << 8 in its high bits).  mismatch != nullptr: every slot's w is compared, bit for bit, with its entry of
-// wpat_invm (Prec::mixed [patterns][PATTERN_WORDS]); a slot that differs, or a tile without a pattern, ORs 1 into *mismatch.
+// planes[c * stride + word(i)] = velm[i].{x, y, z}, i over the MASSIVE slots of the wave tiles wave_tile[0 .. num_wtiles] (device
+// copy: y carries period | pattern << 8 in its high bits); word(i) = wtile_base[tile] + wpat_off[pattern * PATTERN_WORDS + lane],
+// massive = the slot's entry of wpat_invm (Prec::mixed [patterns][PATTERN_WORDS]) is not 0.  mismatch != nullptr: every slot's w
+// is compared, bit for bit, with that entry; a slot that differs, a tile without a pattern, or a massless slot whose x, y or z is
+// not finite ORs 1 into *mismatch.
 hipError_t launch_velm_to_planes(int precision, const void* velm, void* planes, const int2* wave_tile, int num_wtiles,
-                                 const void* wpat_invm, int padded, uint32_t* mismatch, hipStream_t s);
-// velm[i] = (planes x, y, z of slot i, velm[i].w as read), i < n
-hipError_t launch_planes_to_velm(int precision, const void* planes, void* velm, int n, int padded, hipStream_t s);
+                                 const void* wpat_invm, const uint32_t* wtile_base, const uint32_t* wpat_off, int stride,
+                                 uint32_t* mismatch, hipStream_t s);
+// velm[i] = (planes x, y, z of slot i, velm[i].w as read) for the massive slots; a massless slot of velm is not touched
+hipError_t launch_planes_to_velm(int precision, const void* planes, void* velm, const int2* wave_tile, int num_wtiles,
+                                 const void* wpat_invm, const uint32_t* wtile_base, const uint32_t* wpat_off, int stride, hipStream_t s);
 
 }  // namespace tgnh
 

@@ -77,10 +77,14 @@ template <int PREC> struct WStepIn {
 // rescale, half kick, drift, hard wall, stores.  The arithmetic per slot is tile_body's / wke_kernel's, expression for expression.
 // Reference: K :82-113, :138-200 (COM, bins), :249-301 (rescale), :307-365 (kick), :435-466 (drift), :471-574 (hard wall).
 // ---------------------------------------------------------------------------
-struct WaveBounds { int ws, y, n; };        // first slot; the tile's largest molecule | pattern word << 8; slots
+struct WaveBounds { int ws, y, n, base; };  // first slot; the tile's largest molecule | pattern word << 8; slots; PLANES: the tile's first word of a plane
 
 // PLANES: the velocities are read from and stored to the library's x | y | z planes (TileArgs::vplanes) and a slot's 1/m comes with
-// its pattern word.  A template parameter, so that the velm form is compiled without a trace of the other (as a launch-uniform
+// its pattern word.  The planes hold the MASSIVE slots only, packed in slot order, a tile's segment on a 128-byte line: a lane
+// with 1/m != 0 finds its word at the tile's base (a scalar load beside the tile's bounds) + its offset (fetched with 1/m, kept
+// in one register); a massless lane touches no plane and its image is (0, 0, 0, w = 0) -- what its velocity contributes to every
+// sum, v * 0, as long as velm's words were finite (checked on entry, tgnh_vplanes.hip).  Forces, positions and the LDS image keep
+// lane = slot offset.  A template parameter, so that the velm form is compiled without a trace of the other (as a launch-uniform
 // branch in one kernel the planes' code cost the velm path 2.2 % of its steps/s).
 template <int PREC, int GB, bool PLANES = false> struct WaveStep {
     typedef typename Prec<PREC>::real real;
@@ -92,9 +96,10 @@ template <int PREC, int GB, bool PLANES = false> struct WaveStep {
     const double* s_scale;
     mixed *ix, *iy, *iz, *im, *jx, *jy, *jz;
     mixed4* __restrict__ velm; real4* __restrict__ posq; float4* __restrict__ pcorr;
-    // PLANES: x | y | z, and the lane's 1/m beside its pattern word
+    // PLANES: x | y | z, and the lane's 1/m and offset into its tile's segment beside its pattern word
     mixed* __restrict__ vpl;
     mixed pinvm;
+    int poff;
     int lane, G, nw;
     bool use_com, hardwall;
     mixed dt, fscale;
@@ -104,7 +109,7 @@ template <int PREC, int GB, bool PLANES = false> struct WaveStep {
         : a(a_), e(e_), s_scale(s_scale_), ix(img), iy(img + WAVE_SLOTS), iz(img + 2 * WAVE_SLOTS), im(img + 3 * WAVE_SLOTS),
           jx(img + 4 * WAVE_SLOTS), jy(img + 5 * WAVE_SLOTS), jz(img + 6 * WAVE_SLOTS),
           velm(reinterpret_cast<mixed4*>(a_.velm)), posq(reinterpret_cast<real4*>(a_.posq)), pcorr(reinterpret_cast<float4*>(a_.posq_corr)),
-          vpl(reinterpret_cast<mixed*>(a_.vplanes)), pinvm((mixed)0), lane(lane_), G(a_.num_groups), nw(a_.num_wtiles), use_com(a_.use_com != 0), hardwall(a_.hardwall != 0),
+          vpl(reinterpret_cast<mixed*>(a_.vplanes)), pinvm((mixed)0), poff(0), lane(lane_), G(a_.num_groups), nw(a_.num_wtiles), use_com(a_.use_com != 0), hardwall(a_.hardwall != 0),
           dt((mixed)a_.dt), fscale((mixed)(0.5 * a_.dt / 4294967296.0)) {}     // Cu :295
     __device__ __forceinline__ static void wfence() {      // a wavefront's LDS operations are processed in order: only the compiler is held
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -112,20 +117,29 @@ template <int PREC, int GB, bool PLANES = false> struct WaveStep {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     __device__ __forceinline__ void bounds(const int ww, WaveBounds& b) const {      // (wavefront-uniform: scalar loads)
-        const int2* t = a.wave_tile + (a.reverse ? nw - 1 - ww : ww);
+        const int at = a.reverse ? nw - 1 - ww : ww;
+        const int2* t = a.wave_tile + at;
         b.ws = t[0].x; b.y = t[0].y; b.n = t[1].x - b.ws;
+        if (PLANES) b.base = (int)a.wtile_base[at];
     }
     __device__ __forceinline__ void load_vf(const WaveBounds& b, WStepIn<PREC>& in) {          // what pass 1 needs
         const int idx = b.ws + lane;
         const bool patterned = pw.of(a, (uint32_t)b.y >> 8, lane, [&](const uint32_t at) {
-            if (PLANES) pinvm = reinterpret_cast<const mixed*>(a.wpat_invm)[at];
+            if (PLANES) {
+                pinvm = reinterpret_cast<const mixed*>(a.wpat_invm)[at];
+                poff = (int)a.wpat_off[((uint32_t)b.y >> 16) * PATTERN_WORDS + (uint32_t)lane];      // (by lane, not by place in the period)
+            }
         });
         mixed4 v = mk4((mixed)0, (mixed)0, (mixed)0, (mixed)0);
         uint32_t meta = 64u << 10;
         long long fx = 0, fy = 0, fz = 0;
         if (lane < b.n) {
-            if (PLANES) v = mk4(vpl[idx], vpl[idx + a.padded], vpl[idx + 2 * a.padded], pinvm);     // (w: the bits velm holds, checked on entry)
-            else v = reinterpret_cast<const mixed4*>(a.velm)[idx];
+            if (PLANES) {
+                if (pinvm != (mixed)0) {
+                    const int vi = b.base + poff;
+                    v = mk4(vpl[vi], vpl[vi + a.vstride], vpl[vi + 2 * a.vstride], pinvm);           // (w: the bits velm holds, checked on entry)
+                }
+            } else v = reinterpret_cast<const mixed4*>(a.velm)[idx];
             if (!patterned) meta = a.wmeta[idx];
             fx = a.force[idx]; fy = a.force[idx + a.padded]; fz = a.force[idx + 2 * a.padded];
         }
@@ -278,8 +292,12 @@ template <int PREC, int GB, bool PLANES = false> struct WaveStep {
         wfence();                                                        // the next tile's image comes after this tile's reads
         if (lane < bd.n) {
             const int idx = bd.ws + lane;
-            if (PLANES) { vpl[idx] = v.x; vpl[idx + a.padded] = v.y; vpl[idx + 2 * a.padded] = v.z; }
-            else velm[idx] = v;
+            if (PLANES) {
+                if (pinvm != (mixed)0) {
+                    const int vi = bd.base + poff;
+                    vpl[vi] = v.x; vpl[vi + a.vstride] = v.y; vpl[vi + 2 * a.vstride] = v.z;
+                }
+            } else velm[idx] = v;
             store_position<PREC>(posq, pcorr, idx, px, py, pz, pq);
         }
     }

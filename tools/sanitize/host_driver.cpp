@@ -35,6 +35,13 @@ static int run(int mode, int chains, int drude_chains) {
     EXPECT(tgnh_set_temperatures(nullptr, 300, 1, nullptr) == TGNH_ERR_ARG);
     EXPECT(tgnh_set_temperatures(a, 350, 2, nullptr) == TGNH_OK);
     int nt = 0, len = 0;
+    // the velocity planes' layout (tgnh_get_topology 17: stride, number of bases, bases, lane offsets): four wave tiles of 12, 12, 12
+    // and 1 molecules with 4 massive slots each, every segment on a 16-word line; one pattern, the massless slot last of five
+    EXPECT(tgnh_get_topology_len(a, 17, &len) == TGNH_OK && len == 2 + 5 + 64);
+    std::vector<int32_t> lay(len);
+    EXPECT(tgnh_get_topology(a, 17, lay.data()) == TGNH_OK && lay[0] == 160 && lay[1] == 5);
+    EXPECT(lay[2] == 0 && lay[3] == 48 && lay[4] == 96 && lay[5] == 144 && lay[6] == 160);
+    for (int lane = 0; lane < 64; lane++) EXPECT(lay[7 + lane] == lane - lane / 5);
     EXPECT(tgnh_get_num_thermostats(a, &nt) == TGNH_OK && nt >= 3);
     std::vector<double> da(nt), na(nt), db(nt), nb(nt);
     EXPECT(tgnh_get_dof(a, da.data(), na.data()) == TGNH_OK && tgnh_get_dof(b, db.data(), nb.data()) == TGNH_OK);

@@ -6,6 +6,11 @@
 #include "../../openmm_drudenose_amd/csrc/tgnh_wrap.h"
 #include "../../openmm_drudenose_amd/csrc/tgnh_minimize.h"
 #include "../../openmm_drudenose_amd/csrc/tgnh_vplanes.h"
+#include "../../openmm_drudenose_amd/csrc/tgnh_constraints.h"
+#include "../../openmm_drudenose_amd/csrc/tgnh_virtual_sites.h"
+#include "../../openmm_drudenose_amd/csrc/tgnh_drude_force.h"
+#include "../../openmm_drudenose_amd/csrc/tgnh_bonded.h"
+#include "../../openmm_drudenose_amd/csrc/tgnh_nonbonded.h"
 
 namespace tgnh {
 hipError_t launch_tile(int, int, int, const TileArgs&, int, size_t, hipStream_t) { return hipErrorNoDevice; }
@@ -28,8 +33,20 @@ hipError_t launch_cm_momentum(int, const void*, int, CmRow*, int, hipStream_t) {
 hipError_t launch_cm_shift(int, void*, int, const double*, const double*, int, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_rescale_put(double*, const double*, int, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_rescale_factors(const double*, const double*, int, double*, uint32_t*, hipStream_t) { return hipErrorNoDevice; }
-hipError_t launch_velm_to_planes(int, const void*, void*, const int2*, int, const void*, int, uint32_t*, hipStream_t) { return hipErrorNoDevice; }
-hipError_t launch_planes_to_velm(int, const void*, void*, int, int, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_velm_to_planes(int, const void*, void*, const int2*, int, const void*, const uint32_t*, const uint32_t*, int, uint32_t*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_planes_to_velm(int, const void*, void*, const int2*, int, const void*, const uint32_t*, const uint32_t*, int, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_constrain_positions(int, const ConstraintArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_constrain_velocities(int, const ConstraintArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_place_sites(int, const SitePlaceArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_spread_site_forces(int, const SiteSpreadArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_drude_force(int, const DrudeForceArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_drude_energy_sum(const double*, int, double*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_bonded_forces(int, const BondedArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_bonded_energy_sum(const double*, int, double*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_nonbonded_cells(int, const NonbondedArgs&, hipStream_t, int) { return hipErrorNoDevice; }
+hipError_t launch_nonbonded_pairs(int, const NonbondedArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_nonbonded_exceptions(int, const NbExceptionArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_nonbonded_energy_sum(const double*, int, const double*, int, double*, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_scale_positions_spans(int, const ScalePosArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_scale_positions_table(int, const ScalePosArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_wrap_spans(int, const WrapArgs&, hipStream_t) { return hipErrorNoDevice; }
