@@ -902,6 +902,8 @@ tgnh_status tgnh_apply_velocity_constraints(tgnh_handle h, double tol, void* str
  * finite, local-coordinates weights with |sum wo - 1|, |sum wx| or |sum wy| above 1e-6 (OpenMM's own gate).  TGNH_ERR_UNSUPPORTED,
  * with the site's number in tgnh_last_error(): a site whose mass in the descriptor is not zero, a site that is a member of a Drude
  * pair.  Not inside a stream capture (the table is uploaded synchronously).  tgnh_get_num_virtual_sites: the sites in force.
+ * A refused table leaves the one in force as it was, and so does a table whose upload fails (TGNH_ERR_HIP): the new one is built
+ * aside and replaces the old one only when it is complete.
  *
  * Everything below in fp64 in every precision.  A parent's position is posq, + posq_correction in mixed precision, as
  * tgnh_get_drude_statistics defines it.  For the two average kinds every operation is rounded on its own (no fused multiply-add), in

@@ -1,5 +1,5 @@
 // tgnh_bonded.cpp -- the library's bonded forces: the tables of harmonic bonds, harmonic angles and periodic torsions (checks, the
-// phases' cosine and sine formed in fp64, the three tables inverted into receiving slots), tgnh_compute_bonded_forces and
+// phases' cosine and sine formed in fp64, the three tables' shares by receiving slot), tgnh_compute_bonded_forces and
 // tgnh_get_bonded_energy (tgnh_bonded.hip has the kernels; include/drude_tgnh.h the contract)
 #include <climits>
 
@@ -53,15 +53,14 @@ extern "C" tgnh_status tgnh_set_bonded_forces(tgnh_handle h, int num_bonds, cons
     rc = bonded_check(h, "torsion", num_torsions, 4, torsion_particles, torsion_params, torsion_periodicity); if (rc) return rc;
     if (h->host_only) { h->bonded.bonds = num_bonds; h->bonded.angles = num_angles; h->bonded.torsions = num_torsions; return TGNH_OK; }
     HIP_OK(hipSetDevice(h->device));
-    if (num_bonds + num_angles + num_torsions == 0) { h->bonded.drop(); return TGNH_OK; }
+    if (num_bonds + num_angles + num_torsions == 0) { h->bonded = tgnh_context::BondedForces(); return TGNH_OK; }
     const size_t nb = (size_t)num_bonds, na = (size_t)num_angles, nt = (size_t)num_torsions;
     std::vector<int2> b_atoms(nb);
     std::vector<double2> b_par(nb), a_par(na);
     std::vector<int4> a_atoms(na), t_atoms(nt);
     std::vector<int> t_n(nt);
     std::vector<double> t_par(3 * nt);
-    struct Share { int slot, term; unsigned char role; };
-    std::vector<Share> shares;                                   // pushed in term order, sorted below by receiving slot
+    std::vector<Share> shares;                                   // pushed in term order
     shares.reserve(2 * nb + 3 * na + 4 * nt);
     for (size_t r = 0; r < nb; r++) {
         const int32_t* at = bond_particles + 2 * r;
@@ -82,16 +81,6 @@ extern "C" tgnh_status tgnh_set_bonded_forces(tgnh_handle h, int num_bonds, cons
         t_par[r] = std::cos(torsion_params[2 * r]); t_par[nt + r] = std::sin(torsion_params[2 * r]); t_par[2 * nt + r] = torsion_params[2 * r + 1];
         for (int m = 0; m < 4; m++) shares.push_back({at[m], (int)(nb + na + r), (unsigned char)m});
     }
-    // (stable: a slot's entries keep the ascending term order they were pushed in -- the order the kernel sums them in)
-    std::stable_sort(shares.begin(), shares.end(), [](const Share& x, const Share& y) { return x.slot < y.slot; });
-    std::vector<int> recv_slot, recv_start, recv_term(shares.size());
-    std::vector<unsigned char> recv_role(shares.size());
-    for (size_t e = 0; e < shares.size(); e++) {
-        if (recv_slot.empty() || recv_slot.back() != shares[e].slot) { recv_slot.push_back(shares[e].slot); recv_start.push_back((int)e); }
-        recv_term[e] = shares[e].term;
-        recv_role[e] = shares[e].role;
-    }
-    recv_start.push_back((int)shares.size());
     tgnh_context::BondedForces f;                                // built aside: an upload that fails leaves the tables in force as they were
     HIP_OK(f.d_bond_atoms.upload(b_atoms));
     HIP_OK(f.d_bond_par.upload(b_par));
@@ -100,12 +89,8 @@ extern "C" tgnh_status tgnh_set_bonded_forces(tgnh_handle h, int num_bonds, cons
     HIP_OK(f.d_torsion_atoms.upload(t_atoms));
     HIP_OK(f.d_torsion_n.upload(t_n));
     HIP_OK(f.d_torsion_par.upload(t_par));
-    HIP_OK(f.d_recv_slot.upload(recv_slot));
-    HIP_OK(f.d_recv_start.upload(recv_start));
-    HIP_OK(f.d_recv_term.upload(recv_term));
-    HIP_OK(f.d_recv_role.upload(recv_role));
-    HIP_OK(f.d_energy.alloc(4 * ((size_t)bf_grid((int)recv_slot.size()) + 1), true));     // the energy rows now: the launch may be recorded into a graph
-    f.receivers = (int)recv_slot.size();
+    HIP_OK(f.recv.upload(invert_shares(std::move(shares))));
+    HIP_OK(f.d_energy.alloc(4 * ((size_t)bf_grid(f.recv.n) + 1), true));     // the energy rows now: the launch may be recorded into a graph
     f.bonds = num_bonds; f.angles = num_angles; f.torsions = num_torsions;
     h->bonded = std::move(f);                                    // (the old tables' buffers are released here)
     return TGNH_OK;
@@ -118,16 +103,8 @@ extern "C" tgnh_status tgnh_get_num_bonded_terms(tgnh_handle h, int out[3]) {
     return TGNH_OK;
 }
 
-static tgnh_status bonded_ready(tgnh_handle h, const char* what) {
-    CHECK_H(h);
-    if (h->host_only) return fail(TGNH_ERR_STATE, std::string(what) + ": host-only handle (device -1): no GPU work can be launched on it");
-    if (!h->bound.posq) return fail(TGNH_ERR_STATE, std::string(what) + ": tgnh_bind_buffers has not been called");
-    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);        // tgnh_get_status_flags' rule
-    return TGNH_OK;
-}
-
 extern "C" tgnh_status tgnh_compute_bonded_forces(tgnh_handle h, void* force, int want_energy, void* stream) {
-    tgnh_status rc = bonded_ready(h, "tgnh_compute_bonded_forces"); if (rc) return rc;
+    tgnh_status rc = feature_ready(h, "tgnh_compute_bonded_forces", &tgnh_context::Bound::posq, true); if (rc) return rc;
     if (!force) return fail(TGNH_ERR_STATE, "tgnh_compute_bonded_forces: no force buffer");
     const tgnh_context::BondedForces& f = h->bonded;
     if (f.empty()) return TGNH_OK;
@@ -136,8 +113,7 @@ extern "C" tgnh_status tgnh_compute_bonded_forces(tgnh_handle h, void* force, in
     a.bond_atoms = f.d_bond_atoms; a.bond_par = f.d_bond_par; a.angle_atoms = f.d_angle_atoms; a.angle_par = f.d_angle_par;
     a.torsion_atoms = f.d_torsion_atoms; a.torsion_n = f.d_torsion_n; a.torsion_par = f.d_torsion_par;
     a.n_bonds = f.bonds; a.n_angles = f.angles; a.n_torsions = f.torsions;
-    a.recv_slot = f.d_recv_slot; a.recv_start = f.d_recv_start; a.recv_term = f.d_recv_term; a.recv_role = f.d_recv_role;
-    a.n_recv = f.receivers;
+    a.recv = f.recv.view();
     a.posq = h->bound.posq; a.posq_corr = h->bound.posq_corr;
     a.force = static_cast<long long*>(force); a.padded = h->d.padded_num_particles;
     a.rows = want_energy ? f.d_energy.get() : nullptr;
@@ -151,17 +127,16 @@ extern "C" tgnh_status tgnh_compute_bonded_forces(tgnh_handle h, void* force, in
 extern "C" tgnh_status tgnh_get_bonded_energy(tgnh_handle h, void* stream, double out[3]) {
     CHECK_H(h);
     if (!out) return fail(TGNH_ERR_ARG, "null out");
-    tgnh_status rc = bonded_ready(h, "tgnh_get_bonded_energy"); if (rc) return rc;
+    tgnh_status rc = feature_ready(h, "tgnh_get_bonded_energy", &tgnh_context::Bound::posq, true); if (rc) return rc;
     const tgnh_context::BondedForces& f = h->bonded;
     if (!f.energy_launched) return fail(TGNH_ERR_STATE, "tgnh_get_bonded_energy: no tgnh_compute_bonded_forces with want_energy since the tables were set");
     HIP_OK(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const int grid = bf_grid(f.receivers);
+    const int grid = bf_grid(f.recv.n);
     double* totals = f.d_energy.get() + 4 * (size_t)grid;
     HIP_OK(launch_bonded_energy_sum(f.d_energy, grid, totals, s));
     double got[4];
-    HIP_OK(hipMemcpyAsync(got, totals, sizeof(got), hipMemcpyDeviceToHost, s));
-    rc = finish_query(h, s); if (rc) return rc;
+    rc = fetch_totals(h, totals, s, got); if (rc) return rc;
     out[0] = got[0]; out[1] = got[1]; out[2] = got[2];
     return TGNH_OK;
 }

@@ -5,16 +5,17 @@
 #define TGNH_BONDED_H_
 
 #include "tgnh_by_index.h"
+#include "tgnh_receivers.h"
 
 namespace tgnh {
 
-// role of a receiving slot in a term (BondedArgs::recv_role): p1, p2, p3, p4 of the term's row
+// role of a receiving slot in a term (BondedArgs::recv): p1, p2, p3, p4 of the term's row
 enum : int { BF_P1 = 0, BF_P2 = 1, BF_P3 = 2, BF_P4 = 3 };
 constexpr int BONDED_MAX_PERIODICITY = 12;
 
-// The three tables in the kernel's form, rows in the caller's order, and their inverse: the slots that receive a share, ascending,
-// each with its list of (term, role) in CSR form, in ascending term order.  Bonds are numbered first, then angles, then torsions:
-// term t < n_bonds is bond t, t < n_bonds + n_angles angle t - n_bonds, else torsion t - n_bonds - n_angles.
+// The three tables in the kernel's form, rows in the caller's order, and their one inverse (tgnh_receivers.h).  Bonds are numbered
+// first, then angles, then torsions: term t < n_bonds is bond t, t < n_bonds + n_angles angle t - n_bonds, else torsion
+// t - n_bonds - n_angles.
 struct BondedArgs {
     const int2* bond_atoms;         // [n_bonds] (p1, p2)
     const double2* bond_par;        // [n_bonds] (length, k)
@@ -24,11 +25,7 @@ struct BondedArgs {
     const int* torsion_n;           // [n_torsions] periodicity, 1 .. BONDED_MAX_PERIODICITY (the host checked)
     const double* torsion_par;      // [3][n_torsions] planes cos(phase), sin(phase), k: the first two formed on the host at set time
     int n_bonds, n_angles, n_torsions;
-    const int* recv_slot;           // [n_recv]
-    const int* recv_start;          // [n_recv + 1] into the two arrays below
-    const int* recv_term;           // [entries]
-    const unsigned char* recv_role; // [entries] BF_*
-    int n_recv;                     // (every index above is a slot of the bound arrays, every term a row: the host checked at set time)
+    ReceiverTable recv;             // roles: BF_*
     const void* posq; const void* posq_corr;
     long long* force;               // [3 * padded] fixed point x 2^32, planes x | y | z
     int padded;

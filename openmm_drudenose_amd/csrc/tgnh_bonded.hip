@@ -13,20 +13,17 @@
 // Everything in fp64 in every precision, every operation rounded on its own (no fused multiply-add: a test restates the bond shares in
 // numpy and asks for the same bits); sqrt and the divisions are the IEEE ones.  Periodic images are not applied.
 //
-// FORM (drude_force_kernel's): one lane per RECEIVING slot over the tables the host inverted at set time (BondedArgs), a grid-stride
-// loop over the receivers in index_grid's grid.  A lane walks its list; per entry (term, role) it recomputes the term from its
-// positions and forms its own share, converts each component on its own with llrint(c * 2^32) and sums the integers in list order;
-// then one plain 64-bit load, add and store on each of the slot's three plane entries.  No lane reads an entry another lane writes,
-// positions are only read: the result is a function of the inputs alone.  No atomic, no inline assembly, no LDS on the force path.
+// FORM: tgnh_receiver_device.h's, one lane per RECEIVING slot over the tables the host inverted at set time (BondedArgs).  Per entry
+// (term, role) a lane recomputes the term from its positions and forms its own share.
 //
 // ENERGY (the second instantiation, want_energy): the lane of a term's p1 counts it, once.  A thread adds its receivers in ascending
 // order, the three kinds apart; the rest of the order is tgnh_rows_device.h's, and bonded_energy_sum_kernel -- one work-group -- adds
 // the rows: the same bits from any handle over the same slots and the same tables.
 //
-// A bond of length 0 or a torsion whose c0 or c1 has length 0 divides by zero and stores what comes out; llrint of a non-finite share
-// is whatever the conversion instruction gives.  A unit of its own so that the other units compile to what they compiled to before.
+// A bond of length 0 or a torsion whose c0 or c1 has length 0 divides by zero and stores what comes out.  A unit of its own so that
+// the other units compile to what they compiled to before.
 #include "tgnh_bonded.h"
-#include "tgnh_position_device.h"
+#include "tgnh_receiver_device.h"
 #include "tgnh_rows_device.h"
 
 namespace tgnh {
@@ -34,12 +31,6 @@ namespace tgnh {
 #pragma clang fp contract(off)
 
 namespace {
-struct Fixed3 {
-    long long x = 0, y = 0, z = 0;
-    __device__ __forceinline__ void add(const Vec3 c) { x += llrint(c.x * 4294967296.0); y += llrint(c.y * 4294967296.0); z += llrint(c.z * 4294967296.0); }
-};
-__device__ __forceinline__ Vec3 neg(const Vec3 a) { return {-a.x, -a.y, -a.z}; }
-
 template <int PREC, bool ENERGY>
 __device__ __forceinline__ void bond_term(const BondedArgs& a, const int t, const int role, Fixed3& sum, double& e_bond) {
     const int2 at = a.bond_atoms[t];
@@ -95,21 +86,19 @@ __device__ __forceinline__ void torsion_term(const BondedArgs& a, const int t, c
 template <int PREC, bool ENERGY>
 __device__ __forceinline__ void bonded_body(const BondedArgs& a, double& e_bond, double& e_angle, double& e_torsion) {
     const int first_angle = a.n_bonds, first_torsion = a.n_bonds + a.n_angles;
-    for (long long it = (long long)blockIdx.x * BLOCK + threadIdx.x; it < a.n_recv; it += (long long)gridDim.x * BLOCK) {
+    // for_each_receiver's loop, written out (tgnh_receiver_device.h says why)
+    for (long long it = (long long)blockIdx.x * BLOCK + threadIdx.x; it < a.recv.n; it += (long long)gridDim.x * BLOCK) {
         const int r = (int)it;
-        const int slot = a.recv_slot[r];
-        const int e1 = a.recv_start[r + 1];
+        const int slot = a.recv.slot[r];
+        const int e1 = a.recv.start[r + 1];
         Fixed3 sum;
-        for (int e = a.recv_start[r]; e < e1; e++) {
-            const int term = a.recv_term[e], role = a.recv_role[e];
+        for (int e = a.recv.start[r]; e < e1; e++) {
+            const int term = a.recv.term[e], role = a.recv.role[e];
             if (term < first_angle) bond_term<PREC, ENERGY>(a, term, role, sum, e_bond);
             else if (term < first_torsion) angle_term<PREC, ENERGY>(a, term - first_angle, role, sum, e_angle);
             else torsion_term<PREC, ENERGY>(a, term - first_torsion, role, sum, e_torsion);
         }
-        long long* fx = a.force + slot;
-        long long* fy = a.force + (size_t)a.padded + slot;
-        long long* fz = a.force + 2 * (size_t)a.padded + slot;
-        *fx = *fx + sum.x; *fy = *fy + sum.y; *fz = *fz + sum.z;
+        add_to_planes(a.force, a.padded, slot, sum);
     }
 }
 }  // namespace
@@ -125,9 +114,7 @@ __global__ __launch_bounds__(BLOCK) void bonded_forces_energy_kernel(const Bonde
     __shared__ Sum4Lds l;
     double e0 = 0.0, e1 = 0.0, e2 = 0.0;
     bonded_body<PREC, true>(a, e0, e1, e2);
-    sum4_put(l, e0, e1, e2, 0.0);
-    __syncthreads();
-    if (threadIdx.x < 4) a.rows[4 * (size_t)blockIdx.x + threadIdx.x] = sum4_total(l);
+    sum4_store(l, a.rows, e0, e1, e2, 0.0);
 }
 
 // rows [0, nrows)[4] -> out[4].  One work-group, a thread its chunk of the rows (row_chunk).
@@ -145,10 +132,10 @@ __global__ __launch_bounds__(BLOCK) void bonded_energy_sum_kernel(const double* 
 hipError_t launch_bonded_forces(int precision, const BondedArgs& a, hipStream_t s) {
     if (a.n_bonds < 0 || a.n_angles < 0 || a.n_torsions < 0 || (a.n_bonds > 0 && (!a.bond_atoms || !a.bond_par)) ||
         (a.n_angles > 0 && (!a.angle_atoms || !a.angle_par)) || (a.n_torsions > 0 && (!a.torsion_atoms || !a.torsion_n || !a.torsion_par)) ||
-        a.n_recv < 1 || !a.recv_slot || !a.recv_start || !a.recv_term || !a.recv_role || !a.posq || !a.force || a.padded < 1 ||
+        !receivers_ok(a.recv) || !a.posq || !a.force || a.padded < 1 ||
         (precision == TGNH_PREC_MIXED && !a.posq_corr))
         return hipErrorInvalidValue;
-    const int grid = bf_grid(a.n_recv);
+    const int grid = bf_grid(a.recv.n);
     if (a.rows) TGNH_LAUNCH_PREC(bonded_forces_energy_kernel, precision, dim3(grid), dim3(BLOCK), 0, s, a);
     else TGNH_LAUNCH_PREC(bonded_forces_kernel, precision, dim3(grid), dim3(BLOCK), 0, s, a);
     return hipGetLastError();

@@ -102,13 +102,6 @@ extern "C" tgnh_status tgnh_get_num_constraint_clusters(tgnh_handle h, int* coun
     return TGNH_OK;
 }
 
-static tgnh_status constraints_ready(tgnh_handle h, const char* what) {
-    CHECK_H(h);
-    if (h->host_only) return fail(TGNH_ERR_STATE, std::string(what) + ": host-only handle (device -1): no GPU work can be launched on it");
-    if (!h->bound.velm) return fail(TGNH_ERR_STATE, std::string(what) + ": tgnh_bind_buffers has not been called");
-    return TGNH_OK;
-}
-
 static ConstraintArgs constraint_args(tgnh_handle h, double tol) {
     ConstraintArgs a{};
     a.atoms = h->cons.d_atoms; a.invmass = h->cons.d_invmass; a.d2 = h->cons.d_d2; a.pairs = h->cons.d_pairs; a.n = h->cons.count;
@@ -118,7 +111,7 @@ static ConstraintArgs constraint_args(tgnh_handle h, double tol) {
 }
 
 extern "C" tgnh_status tgnh_apply_constraints(tgnh_handle h, double tol, void* stream) {
-    tgnh_status rc = constraints_ready(h, "tgnh_apply_constraints"); if (rc) return rc;
+    tgnh_status rc = feature_ready(h, "tgnh_apply_constraints", &tgnh_context::Bound::velm, false); if (rc) return rc;
     if (!h->bound.pos_delta) return fail(TGNH_ERR_STATE, "tgnh_apply_constraints: posDelta buffer not bound");
     if (h->cons.count == 0) return TGNH_OK;
     HIP_OK(hipSetDevice(h->device));
@@ -127,7 +120,7 @@ extern "C" tgnh_status tgnh_apply_constraints(tgnh_handle h, double tol, void* s
 }
 
 extern "C" tgnh_status tgnh_apply_velocity_constraints(tgnh_handle h, double tol, void* stream) {
-    tgnh_status rc = constraints_ready(h, "tgnh_apply_velocity_constraints"); if (rc) return rc;
+    tgnh_status rc = feature_ready(h, "tgnh_apply_velocity_constraints", &tgnh_context::Bound::velm, false); if (rc) return rc;
     h->owed.ke_carry = false;                 // velocities are about to change behind the integrator, as in tgnh_harness_shake_velocities
     if (h->cons.count == 0) return TGNH_OK;
     HIP_OK(hipSetDevice(h->device));

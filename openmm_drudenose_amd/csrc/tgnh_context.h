@@ -10,6 +10,7 @@
 #include "tgnh_internal.h"
 #include "tgnh_by_index.h"
 #include "tgnh_minimize.h"
+#include "tgnh_receivers.h"
 
 void tgnh_set_error(const std::string& msg);   // sets what tgnh_last_error() returns (tgnh_lifecycle.cpp)
 
@@ -55,6 +56,22 @@ template <typename Row> struct __attribute__((visibility("hidden"))) RowScratch 
     Row h_row{};                      // where the result lands on the host
     // the rows of a pass of `grid` work-groups (zero: cleared when they are allocated); too_small: what to say when grid exceeds them
     tgnh_status ensure(int grid, bool zero, const char* too_small);      // (tgnh_host.h)
+};
+
+// A table of receiving slots on the device (tgnh_receivers.h): uploaded at set time, never inside a capture
+struct Receivers {
+    int n = 0;                        // slots that receive a share of some term
+    DeviceBuf<int> d_slot, d_start, d_term;   // [n], [n + 1], [entries]: the inverse in CSR form
+    DeviceBuf<unsigned char> d_role;          // [entries]
+    hipError_t upload(const ReceiverLists& l) {
+        hipError_t e = d_slot.upload(l.slot);
+        if (e == hipSuccess) e = d_start.upload(l.start);
+        if (e == hipSuccess) e = d_term.upload(l.term);
+        if (e == hipSuccess) e = d_role.upload(l.role);
+        if (e == hipSuccess) n = (int)l.slot.size();
+        return e;
+    }
+    ReceiverTable view() const { return {d_slot, d_start, d_term, d_role, n}; }
 };
 }  // namespace tgnh
 
@@ -171,37 +188,27 @@ struct tgnh_context {
         tgnh::DeviceBuf<uint32_t> d_pairs;    // [count]
         void drop() { count = 0; d_atoms.reset(); d_invmass.reset(); d_d2.reset(); d_pairs.reset(); }
     } cons;
+    // The four tables of the library's forces below are built aside by their setters and moved in whole; a clear assigns a fresh value.
     struct VirtualSites {             // tgnh_set_virtual_sites (tgnh_virtual_sites.cpp): the site table, rows sorted by site slot, and its inverse
         int count = 0;                    // sites in force (a host-only handle keeps the count and nothing else)
-        int receivers = 0;                // slots that receive a share of some site's force
         tgnh::DeviceBuf<int4> d_atoms;    // [count] (site, p1, p2, p3), uploaded at set time, never inside a capture
         tgnh::DeviceBuf<int> d_kind;      // [count]
         tgnh::DeviceBuf<double> d_params; // [12][count]
-        tgnh::DeviceBuf<int> d_recv_slot, d_recv_start, d_recv_row;    // [receivers], [receivers + 1], [entries]: the inverse in CSR form
-        tgnh::DeviceBuf<unsigned char> d_recv_role;                    // [entries]
-        void drop() { count = receivers = 0; d_atoms.reset(); d_kind.reset(); d_params.reset(); d_recv_slot.reset(); d_recv_start.reset(); d_recv_row.reset(); d_recv_role.reset(); }
+        tgnh::Receivers recv;             // the slots that receive a share of some site's force
     } vsites;
     struct DrudeForce {               // tgnh_set_drude_force (tgnh_drude_force.cpp): the rows in the descriptor's pair order, the screened pairs, the inverse
         int rows = 0, screened = 0;       // terms in force (a host-only handle keeps the counts and nothing else)
-        int receivers = 0;                // slots that receive a share of some term
         bool energy_launched = false;     // a want_energy launch has filled d_energy's rows since the table was set
         tgnh::DeviceBuf<int4> d_atoms;    // [rows] (p, p1, p2, p3), uploaded at set time, never inside a capture
         tgnh::DeviceBuf<int> d_p4;        // [rows]
         tgnh::DeviceBuf<double> d_k;      // [3][rows] k1, k2, k3
         tgnh::DeviceBuf<int2> d_pair_rows;        // [screened]
         tgnh::DeviceBuf<double2> d_pair_par;      // [screened] (a, K)
-        tgnh::DeviceBuf<int> d_recv_slot, d_recv_start, d_recv_term;   // [receivers], [receivers + 1], [entries]: the inverse in CSR form
-        tgnh::DeviceBuf<unsigned char> d_recv_role;                    // [entries]
-        tgnh::DeviceBuf<double> d_energy; // [index_grid(receivers) + 1][4]: a row per work-group of the launch, then the totals; allocated at set time
-        void drop() {
-            rows = screened = receivers = 0; energy_launched = false;
-            d_atoms.reset(); d_p4.reset(); d_k.reset(); d_pair_rows.reset(); d_pair_par.reset();
-            d_recv_slot.reset(); d_recv_start.reset(); d_recv_term.reset(); d_recv_role.reset(); d_energy.reset();
-        }
+        tgnh::Receivers recv;             // the slots that receive a share of some term
+        tgnh::DeviceBuf<double> d_energy; // [index_grid(recv.n) + 1][4]: a row per work-group of the launch, then the totals; allocated at set time
     } dforce;
     struct BondedForces {             // tgnh_set_bonded_forces (tgnh_bonded.cpp): the three tables in the caller's order and their one inverse
         int bonds = 0, angles = 0, torsions = 0;  // terms in force (a host-only handle keeps the counts and nothing else)
-        int receivers = 0;                // slots that receive a share of some term
         bool energy_launched = false;     // a want_energy launch has filled d_energy's rows since the tables were set
         tgnh::DeviceBuf<int2> d_bond_atoms;       // [bonds] (p1, p2), uploaded at set time, never inside a capture
         tgnh::DeviceBuf<double2> d_bond_par;      // [bonds] (length, k)
@@ -210,21 +217,13 @@ struct tgnh_context {
         tgnh::DeviceBuf<int4> d_torsion_atoms;    // [torsions]
         tgnh::DeviceBuf<int> d_torsion_n;         // [torsions]
         tgnh::DeviceBuf<double> d_torsion_par;    // [3][torsions] cos(phase), sin(phase), k
-        tgnh::DeviceBuf<int> d_recv_slot, d_recv_start, d_recv_term;   // [receivers], [receivers + 1], [entries]: the inverse in CSR form
-        tgnh::DeviceBuf<unsigned char> d_recv_role;                    // [entries]
-        tgnh::DeviceBuf<double> d_energy; // [index_grid(receivers) + 1][4]: a row per work-group of the launch, then the totals; allocated at set time
+        tgnh::Receivers recv;             // the slots that receive a share of some term
+        tgnh::DeviceBuf<double> d_energy; // [index_grid(recv.n) + 1][4]: a row per work-group of the launch, then the totals; allocated at set time
         bool empty() const { return bonds + angles + torsions == 0; }
-        void drop() {
-            bonds = angles = torsions = receivers = 0; energy_launched = false;
-            d_bond_atoms.reset(); d_bond_par.reset(); d_angle_atoms.reset(); d_angle_par.reset();
-            d_torsion_atoms.reset(); d_torsion_n.reset(); d_torsion_par.reset();
-            d_recv_slot.reset(); d_recv_start.reset(); d_recv_term.reset(); d_recv_role.reset(); d_energy.reset();
-        }
     } bonded;
     struct Nonbonded {                // tgnh_set_nonbonded_force (tgnh_nonbonded.cpp): the particle table, the exclusion lists, the evaluated exceptions' inverse
         int particles = 0, exceptions = 0, evaluated = 0;   // in force (a host-only handle keeps these, the scalars below, and nothing else)
         double cutoff = 0, dielectric = 0, krf = 0, crf = 0;
-        int receivers = 0;                // slots that receive a share of some evaluated exception
         bool energy_launched = false;     // a want_energy call has filled the rows since the tables were set
         int energy_rows = 0;              // ... and the pair launch of the last such call wrote this many
         int cells_allocated = 0;          // what the per-cell buffers below hold; they grow at the first call that needs more, never inside a capture
@@ -233,9 +232,8 @@ struct tgnh_context {
         tgnh::DeviceBuf<int2> d_excl_range;       // [particles] (lowest, highest) excluded partner, (1, 0): none
         tgnh::DeviceBuf<int2> d_exc_atoms;        // [evaluated] (p1, p2)
         tgnh::DeviceBuf<double> d_exc_par;        // [evaluated][3] chargeProd, sigma, epsilon
-        tgnh::DeviceBuf<int> d_recv_slot, d_recv_start, d_recv_term;   // [receivers], [receivers + 1], [entries]: the inverse in CSR form
-        tgnh::DeviceBuf<unsigned char> d_recv_role;                    // [entries]
-        tgnh::DeviceBuf<double> d_exc_rows;       // [index_grid(receivers)][4]
+        tgnh::Receivers recv;                     // the slots that receive a share of some evaluated exception
+        tgnh::DeviceBuf<double> d_exc_rows;       // [index_grid(recv.n)][4]
         tgnh::DeviceBuf<int> d_cell_of, d_placed, d_sorted_slot, d_n_chunks;   // [particles] x 3, [1]: the cell build's per-slot scratch
         tgnh::DeviceBuf<double> d_sorted;         // [6][particles]
         tgnh::DeviceBuf<int2> d_sorted_range;     // [particles]

@@ -1,5 +1,5 @@
-// tgnh_drude_force.cpp -- the library's DrudeForce table (checks, the spring constants formed in fp64, the table inverted into
-// receiving slots), tgnh_compute_drude_force and tgnh_get_drude_energy (tgnh_drude_force.hip has the kernels; include/drude_tgnh.h
+// tgnh_drude_force.cpp -- the library's DrudeForce table (checks, the spring constants formed in fp64, the shares by
+// receiving slot), tgnh_compute_drude_force and tgnh_get_drude_energy (tgnh_drude_force.hip has the kernels; include/drude_tgnh.h
 // the contract)
 #include <climits>
 #include <set>
@@ -68,14 +68,13 @@ extern "C" tgnh_status tgnh_set_drude_force(tgnh_handle h, int n, const int32_t*
     tgnh_status rc = drude_force_check(h, n, particles, params, num_screened, screened, thole, &k); if (rc) return rc;
     if (h->host_only) { h->dforce.rows = n; h->dforce.screened = num_screened; return TGNH_OK; }
     HIP_OK(hipSetDevice(h->device));
-    if (n == 0) { h->dforce.drop(); return TGNH_OK; }
+    if (n == 0) { h->dforce = tgnh_context::DrudeForce(); return TGNH_OK; }
     std::vector<int4> r_atoms((size_t)n);
     std::vector<int> r_p4((size_t)n);
     std::vector<double> r_k(3 * (size_t)n);
     std::vector<int2> r_pair((size_t)num_screened);
     std::vector<double2> r_par((size_t)num_screened);
-    struct Share { int slot, term; unsigned char role; };
-    std::vector<Share> shares;                                   // pushed in term order, sorted below by receiving slot
+    std::vector<Share> shares;                                   // pushed in term order
     for (int r = 0; r < n; r++) {
         const int32_t* at = particles + 5 * (size_t)r;
         r_atoms[r] = make_int4(at[0], at[1], at[2], at[3]);
@@ -92,28 +91,14 @@ extern "C" tgnh_status tgnh_set_drude_force(tgnh_handle h, int n, const int32_t*
         const int site[4] = {particles[5 * (size_t)i], particles[5 * (size_t)i + 1], particles[5 * (size_t)j], particles[5 * (size_t)j + 1]};
         for (int role = 0; role < 4; role++) shares.push_back({site[role], n + m, (unsigned char)role});
     }
-    // (stable: a slot's entries keep the ascending term order they were pushed in -- the order the kernel sums them in)
-    std::stable_sort(shares.begin(), shares.end(), [](const Share& x, const Share& y) { return x.slot < y.slot; });
-    std::vector<int> recv_slot, recv_start, recv_term(shares.size());
-    std::vector<unsigned char> recv_role(shares.size());
-    for (size_t e = 0; e < shares.size(); e++) {
-        if (recv_slot.empty() || recv_slot.back() != shares[e].slot) { recv_slot.push_back(shares[e].slot); recv_start.push_back((int)e); }
-        recv_term[e] = shares[e].term;
-        recv_role[e] = shares[e].role;
-    }
-    recv_start.push_back((int)shares.size());
     tgnh_context::DrudeForce f;                                  // built aside: an upload that fails leaves the table in force as it was
     HIP_OK(f.d_atoms.upload(r_atoms));
     HIP_OK(f.d_p4.upload(r_p4));
     HIP_OK(f.d_k.upload(r_k));
     HIP_OK(f.d_pair_rows.upload(r_pair));
     HIP_OK(f.d_pair_par.upload(r_par));
-    HIP_OK(f.d_recv_slot.upload(recv_slot));
-    HIP_OK(f.d_recv_start.upload(recv_start));
-    HIP_OK(f.d_recv_term.upload(recv_term));
-    HIP_OK(f.d_recv_role.upload(recv_role));
-    HIP_OK(f.d_energy.alloc(4 * ((size_t)df_grid((int)recv_slot.size()) + 1), true));     // the energy rows now: the launch may be recorded into a graph
-    f.receivers = (int)recv_slot.size();
+    HIP_OK(f.recv.upload(invert_shares(std::move(shares))));
+    HIP_OK(f.d_energy.alloc(4 * ((size_t)df_grid(f.recv.n) + 1), true));     // the energy rows now: the launch may be recorded into a graph
     f.rows = n; f.screened = num_screened;
     h->dforce = std::move(f);                                    // (the old table's buffers are released here)
     return TGNH_OK;
@@ -127,16 +112,8 @@ extern "C" tgnh_status tgnh_get_num_drude_force_terms(tgnh_handle h, int* rows, 
     return TGNH_OK;
 }
 
-static tgnh_status drude_force_ready(tgnh_handle h, const char* what) {
-    CHECK_H(h);
-    if (h->host_only) return fail(TGNH_ERR_STATE, std::string(what) + ": host-only handle (device -1): no GPU work can be launched on it");
-    if (!h->bound.posq) return fail(TGNH_ERR_STATE, std::string(what) + ": tgnh_bind_buffers has not been called");
-    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);        // tgnh_get_status_flags' rule
-    return TGNH_OK;
-}
-
 extern "C" tgnh_status tgnh_compute_drude_force(tgnh_handle h, void* force, int want_energy, void* stream) {
-    tgnh_status rc = drude_force_ready(h, "tgnh_compute_drude_force"); if (rc) return rc;
+    tgnh_status rc = feature_ready(h, "tgnh_compute_drude_force", &tgnh_context::Bound::posq, true); if (rc) return rc;
     if (!force) return fail(TGNH_ERR_STATE, "tgnh_compute_drude_force: no force buffer");
     const tgnh_context::DrudeForce& f = h->dforce;
     if (f.rows == 0) return TGNH_OK;
@@ -144,8 +121,7 @@ extern "C" tgnh_status tgnh_compute_drude_force(tgnh_handle h, void* force, int 
     DrudeForceArgs a{};
     a.atoms = f.d_atoms; a.p4 = f.d_p4; a.k = f.d_k; a.pair_rows = f.d_pair_rows; a.pair_par = f.d_pair_par;
     a.n_rows = f.rows; a.n_screened = f.screened;
-    a.recv_slot = f.d_recv_slot; a.recv_start = f.d_recv_start; a.recv_term = f.d_recv_term; a.recv_role = f.d_recv_role;
-    a.n_recv = f.receivers;
+    a.recv = f.recv.view();
     a.posq = h->bound.posq; a.posq_corr = h->bound.posq_corr;
     a.force = static_cast<long long*>(force); a.padded = h->d.padded_num_particles;
     a.rows = want_energy ? f.d_energy.get() : nullptr;
@@ -159,17 +135,16 @@ extern "C" tgnh_status tgnh_compute_drude_force(tgnh_handle h, void* force, int 
 extern "C" tgnh_status tgnh_get_drude_energy(tgnh_handle h, void* stream, double out[2]) {
     CHECK_H(h);
     if (!out) return fail(TGNH_ERR_ARG, "null out");
-    tgnh_status rc = drude_force_ready(h, "tgnh_get_drude_energy"); if (rc) return rc;
+    tgnh_status rc = feature_ready(h, "tgnh_get_drude_energy", &tgnh_context::Bound::posq, true); if (rc) return rc;
     const tgnh_context::DrudeForce& f = h->dforce;
     if (!f.energy_launched) return fail(TGNH_ERR_STATE, "tgnh_get_drude_energy: no tgnh_compute_drude_force with want_energy since the table was set");
     HIP_OK(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const int grid = df_grid(f.receivers);
+    const int grid = df_grid(f.recv.n);
     double* totals = f.d_energy.get() + 4 * (size_t)grid;
     HIP_OK(launch_drude_energy_sum(f.d_energy, grid, totals, s));
     double got[4];
-    HIP_OK(hipMemcpyAsync(got, totals, sizeof(got), hipMemcpyDeviceToHost, s));
-    rc = finish_query(h, s); if (rc) return rc;
+    rc = fetch_totals(h, totals, s, got); if (rc) return rc;
     out[0] = got[0]; out[1] = got[1];
     return TGNH_OK;
 }

@@ -5,16 +5,16 @@
 #define TGNH_DRUDE_FORCE_H_
 
 #include "tgnh_by_index.h"
+#include "tgnh_receivers.h"
 
 namespace tgnh {
 
-// roles of a receiving slot in a term (DrudeForceArgs::recv_role)
+// roles of a receiving slot in a term (DrudeForceArgs::recv)
 enum : int { DF_P = 0, DF_P1 = 1, DF_P2 = 2, DF_P3 = 3, DF_P4 = 4 };          // in a row: p, p1, p2, p3, p4
 enum : int { DF_DRUDE_I = 0, DF_PARENT_I = 1, DF_DRUDE_J = 2, DF_PARENT_J = 3 };   // in a screened pair of rows (i, j)
 
-// The table in the kernel's form, rows in the caller's order (row k is the descriptor's pair k), and its inverse: the slots that
-// receive a share, ascending, each with its list of (term, role) in CSR form, in ascending term order.  A term below n_rows is that
-// row (its isotropic and anisotropic springs); term n_rows + m is screened pair m.
+// The table in the kernel's form, rows in the caller's order (row k is the descriptor's pair k), and its inverse
+// (tgnh_receivers.h).  A term below n_rows is that row (its isotropic and anisotropic springs); term n_rows + m is screened pair m.
 struct DrudeForceArgs {
     const int4* atoms;              // [n_rows] (p, p1, p2, p3); -1: none
     const int* p4;                  // [n_rows]; -1 where p3 is (the host checked: both or neither)
@@ -22,11 +22,7 @@ struct DrudeForceArgs {
     const int2* pair_rows;          // [n_screened] (i, j)
     const double2* pair_par;        // [n_screened] (a = thole / (alpha_i alpha_j)^(1/6), K = C q_i q_j)
     int n_rows, n_screened;
-    const int* recv_slot;           // [n_recv]
-    const int* recv_start;          // [n_recv + 1] into the two arrays below
-    const int* recv_term;           // [entries]
-    const unsigned char* recv_role; // [entries] DF_*
-    int n_recv;                     // (every index above is a slot of the bound arrays, every row a row: the host checked at set time)
+    ReceiverTable recv;             // roles: DF_*
     const void* posq; const void* posq_corr;
     long long* force;               // [3 * padded] fixed point x 2^32, planes x | y | z
     int padded;

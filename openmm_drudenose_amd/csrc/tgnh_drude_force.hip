@@ -12,33 +12,24 @@
 // Everything in fp64 in every precision, every operation rounded on its own (no fused multiply-add: a test restates the isotropic
 // shares in numpy and asks for the same bits); sqrt, exp and the divisions are the IEEE ones.
 //
-// FORM (spread_site_forces_kernel's, tgnh_virtual_sites.hip): one lane per RECEIVING slot over the table the host inverted at set time
-// (DrudeForceArgs), a grid-stride loop over the receivers in index_grid's grid.  A lane walks its list; per entry (term, role) it
-// recomputes the term from the positions its role needs and forms its own share of every spring or site pair of that term, converts
-// each component of each share on its own with llrint(c * 2^32) and sums the integers in list order; then one plain 64-bit load, add
-// and store on each of the slot's three plane entries.  No lane reads an entry another lane writes, positions are only read: the
-// result is a function of the inputs alone.  No atomic, no inline assembly, no LDS on the force path.
+// FORM: tgnh_receiver_device.h's, one lane per RECEIVING slot over the table the host inverted at set time (DrudeForceArgs).  Per
+// entry (term, role) a lane recomputes the term from the positions its role needs and forms its own share of every spring or site
+// pair of that term.
 //
 // ENERGY (the second instantiation, want_energy): the lane of a row's p counts that row's springs, the lane of row i's p a screened
 // pair's four site pairs (it forms the two pairs of p1_i for that alone); a term is counted once.  A thread adds its receivers in
 // ascending order, springs and screened pairs apart; the rest of the order is tgnh_rows_device.h's, and drude_energy_sum_kernel -- one
 // work-group -- adds the rows: the same bits from any handle over the same slots and the same table.
 //
-// A pair at r = 0 or an axis of length 0 divides by zero and stores what comes out; llrint of a non-finite share is whatever the
-// conversion instruction gives.  A unit of its own so that the step kernels' units compile to what they compiled to before.
+// A pair at r = 0 or an axis of length 0 divides by zero and stores what comes out.  A unit of its own so that the step kernels'
+// units compile to what they compiled to before.
 #include "tgnh_drude_force.h"
-#include "tgnh_position_device.h"
+#include "tgnh_receiver_device.h"
 #include "tgnh_rows_device.h"
 
 namespace tgnh {
 
 #pragma clang fp contract(off)
-
-struct Fixed3 {
-    long long x = 0, y = 0, z = 0;
-    __device__ __forceinline__ void add(const Vec3 c) { x += llrint(c.x * 4294967296.0); y += llrint(c.y * 4294967296.0); z += llrint(c.z * 4294967296.0); }
-};
-__device__ __forceinline__ Vec3 neg(const Vec3 a) { return {-a.x, -a.y, -a.z}; }
 
 // one anisotropic spring along d: f1 = (k s) e, f2 = (k s / |d|)(delta - s e), E = 1/2 k s^2
 struct AxisTerm { Vec3 f1, f2; double energy; };
@@ -68,13 +59,14 @@ __device__ __forceinline__ ScreenedTerm screened_term(const double a, const doub
 
 template <int PREC, bool ENERGY>
 __device__ __forceinline__ void drude_force_body(const DrudeForceArgs& a, double& e_spring, double& e_screened) {
-    for (long long it = (long long)blockIdx.x * BLOCK + threadIdx.x; it < a.n_recv; it += (long long)gridDim.x * BLOCK) {
+    // for_each_receiver's loop, written out (tgnh_receiver_device.h says why)
+    for (long long it = (long long)blockIdx.x * BLOCK + threadIdx.x; it < a.recv.n; it += (long long)gridDim.x * BLOCK) {
         const int r = (int)it;
-        const int slot = a.recv_slot[r];
-        const int e1 = a.recv_start[r + 1];
+        const int slot = a.recv.slot[r];
+        const int e1 = a.recv.start[r + 1];
         Fixed3 sum;
-        for (int e = a.recv_start[r]; e < e1; e++) {
-            const int term = a.recv_term[e], role = a.recv_role[e];
+        for (int e = a.recv.start[r]; e < e1; e++) {
+            const int term = a.recv.term[e], role = a.recv.role[e];
             if (term < a.n_rows) {
                 const int4 at = a.atoms[term];
                 const Vec3 xp = slot_position<PREC>(a.posq, a.posq_corr, at.x), x1 = slot_position<PREC>(a.posq, a.posq_corr, at.y);
@@ -119,10 +111,7 @@ __device__ __forceinline__ void drude_force_body(const DrudeForceArgs& a, double
                 }
             }
         }
-        long long* fx = a.force + slot;
-        long long* fy = a.force + (size_t)a.padded + slot;
-        long long* fz = a.force + 2 * (size_t)a.padded + slot;
-        *fx = *fx + sum.x; *fy = *fy + sum.y; *fz = *fz + sum.z;
+        add_to_planes(a.force, a.padded, slot, sum);
     }
 }
 
@@ -137,9 +126,7 @@ __global__ __launch_bounds__(BLOCK) void drude_force_energy_kernel(const DrudeFo
     __shared__ Sum4Lds l;
     double e0 = 0.0, e1 = 0.0;
     drude_force_body<PREC, true>(a, e0, e1);
-    sum4_put(l, e0, e1, 0.0, 0.0);
-    __syncthreads();
-    if (threadIdx.x < 4) a.rows[4 * (size_t)blockIdx.x + threadIdx.x] = sum4_total(l);
+    sum4_store(l, a.rows, e0, e1, 0.0, 0.0);
 }
 
 // rows [0, nrows)[4] -> out[4].  One work-group, a thread its chunk of the rows (row_chunk).
@@ -155,11 +142,11 @@ __global__ __launch_bounds__(BLOCK) void drude_energy_sum_kernel(const double* _
 }
 
 hipError_t launch_drude_force(int precision, const DrudeForceArgs& a, hipStream_t s) {
-    if (a.n_rows < 1 || a.n_screened < 0 || !a.atoms || !a.p4 || !a.k || (a.n_screened > 0 && (!a.pair_rows || !a.pair_par)) || a.n_recv < 1 ||
-        !a.recv_slot || !a.recv_start || !a.recv_term || !a.recv_role || !a.posq || !a.force || a.padded < 1 ||
+    if (a.n_rows < 1 || a.n_screened < 0 || !a.atoms || !a.p4 || !a.k || (a.n_screened > 0 && (!a.pair_rows || !a.pair_par)) ||
+        !receivers_ok(a.recv) || !a.posq || !a.force || a.padded < 1 ||
         (precision == TGNH_PREC_MIXED && !a.posq_corr))
         return hipErrorInvalidValue;
-    const int grid = df_grid(a.n_recv);
+    const int grid = df_grid(a.recv.n);
     if (a.rows) TGNH_LAUNCH_PREC(drude_force_energy_kernel, precision, dim3(grid), dim3(BLOCK), 0, s, a);
     else TGNH_LAUNCH_PREC(drude_force_kernel, precision, dim3(grid), dim3(BLOCK), 0, s, a);
     return hipGetLastError();

@@ -2,6 +2,8 @@
 // tgnh_exchange.cpp, tgnh_step.cpp, tgnh_velocities.cpp, tgnh_queries.cpp, tgnh_positions.cpp, tgnh_frames.cpp, tgnh_minimize.cpp, tgnh_constraints.cpp, tgnh_virtual_sites.cpp, tgnh_drude_force.cpp, tgnh_bonded.cpp, tgnh_nonbonded.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
 // live in tgnh_kernels.hip (tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h), tgnh_gather.hip, tgnh_velinit.hip,
 // tgnh_drude_stats.hip, tgnh_cm_motion.hip, tgnh_rescale.hip, tgnh_scale_positions.hip, tgnh_wrap.hip, tgnh_minimize.hip, tgnh_constraints.hip, tgnh_virtual_sites.hip, tgnh_drude_force.hip, tgnh_bonded.hip, tgnh_nonbonded.hip, tgnh_vplanes.hip and tgnh_harness.hip.
+// The library's forces (virtual sites, DrudeForce, bonded, the nonbonded exceptions) share one form, said once: the table of receiving
+// slots and its inversion in tgnh_receivers.h, its owner in tgnh_context.h (Receivers), the lane's loop in tgnh_receiver_device.h.
 //
 // Reference semantics followed (scychon/openmm_drudeNose):
 //   Ref = platforms/reference/src/ReferenceDrudeTGNHKernels.cpp
@@ -92,6 +94,21 @@ struct Timed {
     }
     ~Timed() { if (ev) (void)hipEventRecord(ev->b, s); }
 };
+// What a feature call (constraints, virtual sites, the library's forces) refuses before it launches anything: a host-only handle, a
+// handle whose arrays are not bound -- `needs` names the one the call works on -- and, where `sticky`, a failure the device
+// reported earlier (tgnh_get_status_flags' rule).
+inline tgnh_status feature_ready(tgnh_handle h, const char* what, void* tgnh_context::Bound::*needs, bool sticky) {
+    CHECK_H(h);
+    if (h->host_only) return fail(TGNH_ERR_STATE, std::string(what) + ": host-only handle (device -1): no GPU work can be launched on it");
+    if (!(h->bound.*needs)) return fail(TGNH_ERR_STATE, std::string(what) + ": tgnh_bind_buffers has not been called");
+    if (sticky && h->status.failed_code) return fail(h->status.failed_code, h->status.failed);
+    return TGNH_OK;
+}
+// An energy query's tail: the four totals that the one-work-group sum enqueued on s leaves at `totals`, on the host when this returns
+inline tgnh_status fetch_totals(tgnh_handle h, const double* totals, hipStream_t s, double (&got)[4]) {
+    HIP_OK(hipMemcpyAsync(got, totals, sizeof(got), hipMemcpyDeviceToHost, s));
+    return finish_query(h, s);
+}
 template <typename Row> tgnh_status tgnh::RowScratch<Row>::ensure(int grid, bool zero, const char* too_small) {
     if (!d_rows) {
         HIP_OK(d_rows.alloc((size_t)grid + 1, zero));

@@ -1,5 +1,5 @@
 // tgnh_nonbonded.cpp -- the library's NonbondedForce: the particle table and the exceptions (checks, krf and crf formed in fp64, the
-// exclusion lists per slot, the evaluated exceptions inverted into receiving slots), tgnh_compute_nonbonded_force (the box's checks,
+// exclusion lists per slot, the evaluated exceptions' shares by receiving slot), tgnh_compute_nonbonded_force (the box's checks,
 // the cell grid, the per-cell buffers, the launches) and tgnh_get_nonbonded_energy (tgnh_nonbonded.hip has the kernels;
 // include/drude_tgnh.h the contract)
 #include <climits>
@@ -87,9 +87,8 @@ extern "C" tgnh_status tgnh_set_nonbonded_force(tgnh_handle h, const tgnh_nonbon
             if (excl_start[i + 1] > excl_start[i]) excl_range[i] = make_int2(excl[excl_start[i]], excl[excl_start[i + 1] - 1]);
         }
     }
-    // the evaluated rows in the caller's order, and their inverse (tgnh_bonded.cpp's form)
+    // the evaluated rows in the caller's order, and their shares
     std::vector<int2> exc_atoms; std::vector<double> exc_par;
-    struct Share { int slot, term; unsigned char role; };
     std::vector<Share> shares;
     for (int r = 0; r < ne; r++) {
         const double* p = d->exception_params + 3 * (size_t)r;
@@ -100,16 +99,6 @@ extern "C" tgnh_status tgnh_set_nonbonded_force(tgnh_handle h, const tgnh_nonbon
         exc_par.insert(exc_par.end(), p, p + 3);
         shares.push_back({at[0], t, 0}); shares.push_back({at[1], t, 1});
     }
-    std::stable_sort(shares.begin(), shares.end(), [](const Share& x, const Share& y) { return x.slot < y.slot; });
-    std::vector<int> recv_slot, recv_start, recv_term(shares.size());
-    std::vector<unsigned char> recv_role(shares.size());
-    for (size_t e = 0; e < shares.size(); e++) {
-        if (recv_slot.empty() || recv_slot.back() != shares[e].slot) { recv_slot.push_back(shares[e].slot); recv_start.push_back((int)e); }
-        recv_term[e] = shares[e].term;
-        recv_role[e] = shares[e].role;
-    }
-    recv_start.push_back((int)shares.size());
-    f.receivers = (int)recv_slot.size();
     HIP_OK(f.d_par.upload(d->particles, 3 * (size_t)N));
     HIP_OK(f.d_excl_start.upload(excl_start));
     HIP_OK(f.d_excl.upload(excl));
@@ -117,11 +106,8 @@ extern "C" tgnh_status tgnh_set_nonbonded_force(tgnh_handle h, const tgnh_nonbon
     if (evaluated) {
         HIP_OK(f.d_exc_atoms.upload(exc_atoms));
         HIP_OK(f.d_exc_par.upload(exc_par));
-        HIP_OK(f.d_recv_slot.upload(recv_slot));
-        HIP_OK(f.d_recv_start.upload(recv_start));
-        HIP_OK(f.d_recv_term.upload(recv_term));
-        HIP_OK(f.d_recv_role.upload(recv_role));
-        HIP_OK(f.d_exc_rows.alloc(4 * (size_t)index_grid(f.receivers), true));
+        HIP_OK(f.recv.upload(invert_shares(std::move(shares))));
+        HIP_OK(f.d_exc_rows.alloc(4 * (size_t)index_grid(f.recv.n), true));
     }
     // the per-slot buffers of the cell build now: a call may be recorded into a graph
     HIP_OK(f.d_cell_of.alloc((size_t)N));
@@ -142,17 +128,9 @@ extern "C" tgnh_status tgnh_get_num_nonbonded_terms(tgnh_handle h, int out[3]) {
     return TGNH_OK;
 }
 
-static tgnh_status nonbonded_ready(tgnh_handle h, const char* what) {
-    CHECK_H(h);
-    if (h->host_only) return fail(TGNH_ERR_STATE, std::string(what) + ": host-only handle (device -1): no GPU work can be launched on it");
-    if (!h->bound.posq) return fail(TGNH_ERR_STATE, std::string(what) + ": tgnh_bind_buffers has not been called");
-    if (h->status.failed_code) return fail(h->status.failed_code, h->status.failed);        // tgnh_get_status_flags' rule
-    return TGNH_OK;
-}
-
 extern "C" tgnh_status tgnh_compute_nonbonded_force(tgnh_handle h, void* force, int want_energy, void* stream) {
     const char* me = "tgnh_compute_nonbonded_force: ";
-    tgnh_status rc = nonbonded_ready(h, "tgnh_compute_nonbonded_force"); if (rc) return rc;
+    tgnh_status rc = feature_ready(h, "tgnh_compute_nonbonded_force", &tgnh_context::Bound::posq, true); if (rc) return rc;
     if (!force) return fail(TGNH_ERR_STATE, std::string(me) + "no force buffer");
     tgnh_context::Nonbonded& f = h->nonbonded;
     if (f.particles == 0) return TGNH_OK;
@@ -210,7 +188,7 @@ extern "C" tgnh_status tgnh_compute_nonbonded_force(tgnh_handle h, void* force, 
     if (f.evaluated) {
         NbExceptionArgs x{};
         x.atoms = f.d_exc_atoms; x.par = f.d_exc_par;
-        x.recv_slot = f.d_recv_slot; x.recv_start = f.d_recv_start; x.recv_term = f.d_recv_term; x.recv_role = f.d_recv_role; x.n_recv = f.receivers;
+        x.recv = f.recv.view();
         x.posq = h->bound.posq; x.posq_corr = h->bound.posq_corr;
         x.force = a.force; x.padded = a.padded;
         x.rows = want_energy ? f.d_exc_rows.get() : nullptr;
@@ -225,15 +203,14 @@ extern "C" tgnh_status tgnh_compute_nonbonded_force(tgnh_handle h, void* force, 
 extern "C" tgnh_status tgnh_get_nonbonded_energy(tgnh_handle h, void* stream, double out[4]) {
     CHECK_H(h);
     if (!out) return fail(TGNH_ERR_ARG, "null out");
-    tgnh_status rc = nonbonded_ready(h, "tgnh_get_nonbonded_energy"); if (rc) return rc;
+    tgnh_status rc = feature_ready(h, "tgnh_get_nonbonded_energy", &tgnh_context::Bound::posq, true); if (rc) return rc;
     const tgnh_context::Nonbonded& f = h->nonbonded;
     if (!f.energy_launched) return fail(TGNH_ERR_STATE, "tgnh_get_nonbonded_energy: no tgnh_compute_nonbonded_force with want_energy since the tables were set");
     HIP_OK(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    HIP_OK(launch_nonbonded_energy_sum(f.d_pair_rows, f.energy_rows, f.d_exc_rows, f.evaluated ? index_grid(f.receivers) : 0, f.d_totals, s));
+    HIP_OK(launch_nonbonded_energy_sum(f.d_pair_rows, f.energy_rows, f.d_exc_rows, f.evaluated ? index_grid(f.recv.n) : 0, f.d_totals, s));
     double got[4];
-    HIP_OK(hipMemcpyAsync(got, f.d_totals, sizeof(got), hipMemcpyDeviceToHost, s));
-    rc = finish_query(h, s); if (rc) return rc;
+    rc = fetch_totals(h, f.d_totals, s, got); if (rc) return rc;
     for (int k = 0; k < 4; k++) out[k] = got[k];
     return TGNH_OK;
 }

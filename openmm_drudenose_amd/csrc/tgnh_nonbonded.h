@@ -5,6 +5,7 @@
 #define TGNH_NONBONDED_H_
 
 #include "tgnh_by_index.h"
+#include "tgnh_receivers.h"
 
 namespace tgnh {
 
@@ -40,18 +41,14 @@ struct NonbondedArgs {
     double* rows;                   // want_energy: [pair_grid][4] a work-group's {E_C, E_LJ, 0, 0}; nullptr: forces only
 };
 
-// The evaluated exceptions, inverted at set time as tgnh_bonded.cpp inverts its tables: one lane per receiving slot
+// The evaluated exceptions and their inverse (tgnh_receivers.h): a term is a row, a role 0 for the row's p1, 1 for its p2
 struct NbExceptionArgs {
     const int2* atoms;              // [rows] (p1, p2)
     const double* par;              // [rows][3] chargeProd, sigma, epsilon
-    const int* recv_slot;           // [n_recv]
-    const int* recv_start;          // [n_recv + 1]
-    const int* recv_term;           // [entries]
-    const unsigned char* recv_role; // [entries] 0: the row's p1, 1: its p2
-    int n_recv;
+    ReceiverTable recv;
     const void* posq; const void* posq_corr;
     long long* force; int padded;
-    double* rows;                   // want_energy: [index_grid(n_recv)][4] {E_C, E_LJ, 0, 0}
+    double* rows;                   // want_energy: [index_grid(recv.n)][4] {E_C, E_LJ, 0, 0}
 };
 
 inline int nb_chunk_cap(int n, int ncells) { return ncells + (n + 63) / 64; }

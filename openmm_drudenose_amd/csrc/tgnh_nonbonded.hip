@@ -24,10 +24,10 @@
 // whole launch.  No atomic touches the force buffer; no inline assembly.
 // THE ENERGY (second instantiation).  A lane adds E_C and E_LJ only for neighbours whose slot is larger than its own, in traversal
 // order; the rest of the order is tgnh_rows_device.h's.
-// THE EXCEPTIONS.  tgnh_bonded.hip's form: one lane per receiving slot over the table inverted at set time; no cutoff, no reaction
-// field, no periodic image.
+// THE EXCEPTIONS.  tgnh_receiver_device.h's form: one lane per receiving slot over the table inverted at set time; no cutoff, no
+// reaction field, no periodic image.
 #include "tgnh_nonbonded.h"
-#include "tgnh_position_device.h"
+#include "tgnh_receiver_device.h"
 #include "tgnh_rows_device.h"
 
 namespace tgnh {
@@ -129,12 +129,7 @@ __device__ __forceinline__ void pair_wave(const NonbondedArgs& a, NbImage& img, 
             }
         }
     }
-    if (active) {
-        long long* px = a.force + slot;
-        long long* py = a.force + (size_t)a.padded + slot;
-        long long* pz = a.force + 2 * (size_t)a.padded + slot;
-        *px = *px + fx; *py = *py + fy; *pz = *pz + fz;
-    }
+    if (active) add_to_planes(a.force, a.padded, slot, {fx, fy, fz});
 }
 }  // namespace
 
@@ -218,9 +213,7 @@ __global__ __launch_bounds__(BLOCK) void nb_pair_energy_kernel(const NonbondedAr
     const int w = threadIdx.x >> 6, wave = blockIdx.x * NB_WAVES + w;
     double e_c = 0.0, e_lj = 0.0;
     if (wave < *a.n_chunks) pair_wave<true>(a, img, w, wave, e_c, e_lj);
-    sum4_put(l, e_c, e_lj, 0.0, 0.0);
-    __syncthreads();
-    if (threadIdx.x < 4) a.rows[4 * (size_t)blockIdx.x + threadIdx.x] = sum4_total(l);
+    sum4_store(l, a.rows, e_c, e_lj, 0.0, 0.0);
 }
 
 // An evaluated exception (p1, p2; chargeProd, sigma, epsilon), for the receiving slot at `role`:
@@ -228,34 +221,22 @@ __global__ __launch_bounds__(BLOCK) void nb_pair_energy_kernel(const NonbondedAr
 //   s2 = (sigma sigma) / r2, s6 = (s2 s2) s2, s12 = s6 s6, dc = qq (-(inv inv)), dl = (e4 (6 s6 - 12 s12)) inv, c = -((dc + dl) inv)
 template <int PREC, bool ENERGY>
 __device__ __forceinline__ void exception_body(const NbExceptionArgs& a, double& e_c, double& e_lj) {
-    for (long long it = (long long)blockIdx.x * BLOCK + threadIdx.x; it < a.n_recv; it += (long long)gridDim.x * BLOCK) {
-        const int r = (int)it;
-        const int slot = a.recv_slot[r];
-        const int e1 = a.recv_start[r + 1];
-        const Vec3 xs = slot_position<PREC>(a.posq, a.posq_corr, slot);
-        long long fx = 0, fy = 0, fz = 0;
-        for (int e = a.recv_start[r]; e < e1; e++) {
-            const int t = a.recv_term[e], role = a.recv_role[e];
-            const int2 at = a.atoms[t];
-            const Vec3 d = xs - slot_position<PREC>(a.posq, a.posq_corr, role == 0 ? at.y : at.x);
-            const double r2 = dot(d, d), rr = sqrt(r2), inv = 1.0 / rr;
-            const double qq = NB_COULOMB * a.par[3 * (size_t)t], sig = a.par[3 * (size_t)t + 1], e4 = 4.0 * a.par[3 * (size_t)t + 2];
-            const double s2 = (sig * sig) / r2;
-            const double s6 = (s2 * s2) * s2, s12 = s6 * s6;
-            const double dc = qq * (-(inv * inv));
-            const double dl = (e4 * (6.0 * s6 - 12.0 * s12)) * inv;
-            const double c = -((dc + dl) * inv);
-            fx += llrint((c * d.x) * NB_FIXED); fy += llrint((c * d.y) * NB_FIXED); fz += llrint((c * d.z) * NB_FIXED);
-            if (ENERGY && role == 0) {
-                e_c = e_c + qq * inv;
-                e_lj = e_lj + e4 * (s12 - s6);
-            }
+    for_each_receiver(a.recv, a.force, a.padded, [&](const int slot, const int t, const int role, Fixed3& sum) {
+        const int2 at = a.atoms[t];
+        const Vec3 d = slot_position<PREC>(a.posq, a.posq_corr, slot) - slot_position<PREC>(a.posq, a.posq_corr, role == 0 ? at.y : at.x);
+        const double r2 = dot(d, d), rr = sqrt(r2), inv = 1.0 / rr;
+        const double qq = NB_COULOMB * a.par[3 * (size_t)t], sig = a.par[3 * (size_t)t + 1], e4 = 4.0 * a.par[3 * (size_t)t + 2];
+        const double s2 = (sig * sig) / r2;
+        const double s6 = (s2 * s2) * s2, s12 = s6 * s6;
+        const double dc = qq * (-(inv * inv));
+        const double dl = (e4 * (6.0 * s6 - 12.0 * s12)) * inv;
+        const double c = -((dc + dl) * inv);
+        sum.add(c * d);
+        if (ENERGY && role == 0) {
+            e_c = e_c + qq * inv;
+            e_lj = e_lj + e4 * (s12 - s6);
         }
-        long long* px = a.force + slot;
-        long long* py = a.force + (size_t)a.padded + slot;
-        long long* pz = a.force + 2 * (size_t)a.padded + slot;
-        *px = *px + fx; *py = *py + fy; *pz = *pz + fz;
-    }
+    });
 }
 
 template <int PREC>
@@ -269,9 +250,7 @@ __global__ __launch_bounds__(BLOCK) void nb_exception_energy_kernel(const NbExce
     __shared__ Sum4Lds l;
     double e0 = 0.0, e1 = 0.0;
     exception_body<PREC, true>(a, e0, e1);
-    sum4_put(l, e0, e1, 0.0, 0.0);
-    __syncthreads();
-    if (threadIdx.x < 4) a.rows[4 * (size_t)blockIdx.x + threadIdx.x] = sum4_total(l);
+    sum4_store(l, a.rows, e0, e1, 0.0, 0.0);
 }
 
 // pair rows [0, n_pair)[4] and exception rows [0, n_exc)[4] -> out[4].  One work-group, a thread its chunk of each (row_chunk).
@@ -318,10 +297,10 @@ hipError_t launch_nonbonded_pairs(int precision, const NonbondedArgs& a, hipStre
 }
 
 hipError_t launch_nonbonded_exceptions(int precision, const NbExceptionArgs& a, hipStream_t s) {
-    if (!a.atoms || !a.par || a.n_recv < 1 || !a.recv_slot || !a.recv_start || !a.recv_term || !a.recv_role || !a.posq || !a.force ||
+    if (!a.atoms || !a.par || !receivers_ok(a.recv) || !a.posq || !a.force ||
         a.padded < 1 || (precision == TGNH_PREC_MIXED && !a.posq_corr))
         return hipErrorInvalidValue;
-    const int grid = index_grid(a.n_recv);
+    const int grid = index_grid(a.recv.n);
     if (a.rows) TGNH_LAUNCH_PREC(nb_exception_energy_kernel, precision, dim3(grid), dim3(BLOCK), 0, s, a);
     else TGNH_LAUNCH_PREC(nb_exception_kernel, precision, dim3(grid), dim3(BLOCK), 0, s, a);
     return hipGetLastError();

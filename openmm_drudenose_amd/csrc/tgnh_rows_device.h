@@ -1,5 +1,5 @@
 // tgnh_rows_device.h -- what the passes by global slot index that leave a row of sums per work-group share on the device
-// (tgnh_cm_motion.hip, tgnh_drude_stats.hip, tgnh_minimize.hip).  Included by .hip files only, by none of the step kernels' units.
+// (tgnh_cm_motion.hip, tgnh_drude_stats.hip, tgnh_minimize.hip, the energies of tgnh_drude_force.hip, tgnh_bonded.hip, tgnh_nonbonded.hip).  Included by .hip files only, by none of the step kernels' units.
 //
 // The order of these sums is a contract -- same bits from any handle over the same slots -- written down
 // here: the grid is a function of the slot count alone (index_grid); a thread adds its slots in ascending index order (the
@@ -31,6 +31,13 @@ __device__ __forceinline__ double sum4_total(const Sum4Lds& l) {       // thread
 #pragma unroll
     for (int w = 1; w < BLOCK / 64; w++) s += l.wsum[w][threadIdx.x];      // wavefront order
     return s;
+}
+// the two with the barrier between them: a work-group's four sums into its row of rows [grid][4].  Every thread calls this, as it
+// calls sum4_put
+__device__ __forceinline__ void sum4_store(Sum4Lds& l, double* rows, const double s0, const double s1, const double s2, const double s3) {
+    sum4_put(l, s0, s1, s2, s3);
+    __syncthreads();
+    if (threadIdx.x < 4) rows[4 * (size_t)blockIdx.x + threadIdx.x] = sum4_total(l);
 }
 // One work-group adds rows [0, nrows): thread t the run of consecutive rows [r0, r1) = [t c, (t + 1) c), c = ceil(nrows / BLOCK), in
 // row order; the threads' sums then meet as a work-group's do in the pass.

@@ -1,5 +1,5 @@
-// tgnh_virtual_sites.cpp -- the library's virtual-site table (checks, the rows in the kernels' form sorted by site slot, the table
-// inverted into receiving slots), tgnh_compute_virtual_sites and tgnh_distribute_virtual_site_forces (tgnh_virtual_sites.hip has the
+// tgnh_virtual_sites.cpp -- the library's virtual-site table (checks, the rows in the kernels' form sorted by site slot, its
+// shares by receiving slot), tgnh_compute_virtual_sites and tgnh_distribute_virtual_site_forces (tgnh_virtual_sites.hip has the
 // kernels; include/drude_tgnh.h the contract)
 #include <climits>
 #include <numeric>
@@ -62,8 +62,7 @@ extern "C" tgnh_status tgnh_set_virtual_sites(tgnh_handle h, int n, const int32_
     tgnh_status rc = sites_check(h, n, kind, atoms, params); if (rc) return rc;
     if (h->host_only) { h->vsites.count = n; return TGNH_OK; }
     HIP_OK(hipSetDevice(h->device));
-    h->vsites.drop();
-    if (n == 0) return TGNH_OK;
+    if (n == 0) { h->vsites = tgnh_context::VirtualSites(); return TGNH_OK; }
     // rows by site slot (no slot is a site twice: no ties), so that neighbouring lanes write neighbouring lines
     std::vector<int> order((size_t)n);
     std::iota(order.begin(), order.end(), 0);
@@ -71,8 +70,7 @@ extern "C" tgnh_status tgnh_set_virtual_sites(tgnh_handle h, int n, const int32_
     std::vector<int4> r_atoms((size_t)n);
     std::vector<int> r_kind((size_t)n);
     std::vector<double> r_params(VS_PARAMS * (size_t)n, 0.0);
-    struct Share { int slot, row; unsigned char role; };
-    std::vector<Share> shares;                                   // pushed in row order, sorted below by receiving slot
+    std::vector<Share> shares;                                   // pushed in row order
     for (int row = 0; row < n; row++) {
         const int32_t* at = atoms + 4 * (size_t)order[row];
         const int k = kind[order[row]], np = parents_of(k);
@@ -81,25 +79,13 @@ extern "C" tgnh_status tgnh_set_virtual_sites(tgnh_handle h, int n, const int32_
         for (int j = 0; j < VS_PARAMS_USED[k]; j++) r_params[j * (size_t)n + row] = params[VS_PARAMS * (size_t)order[row] + j];
         for (int m = 0; m < np; m++) shares.push_back({at[1 + m], row, (unsigned char)m});
     }
-    // (stable: a slot's entries keep the ascending row order they were pushed in -- the order the kernel sums them in)
-    std::stable_sort(shares.begin(), shares.end(), [](const Share& x, const Share& y) { return x.slot < y.slot; });
-    std::vector<int> recv_slot, recv_start, recv_row(shares.size());
-    std::vector<unsigned char> recv_role(shares.size());
-    for (size_t e = 0; e < shares.size(); e++) {
-        if (recv_slot.empty() || recv_slot.back() != shares[e].slot) { recv_slot.push_back(shares[e].slot); recv_start.push_back((int)e); }
-        recv_row[e] = shares[e].row;
-        recv_role[e] = shares[e].role;
-    }
-    recv_start.push_back((int)shares.size());
-    HIP_OK(h->vsites.d_atoms.upload(r_atoms));
-    HIP_OK(h->vsites.d_kind.upload(r_kind));
-    HIP_OK(h->vsites.d_params.upload(r_params));
-    HIP_OK(h->vsites.d_recv_slot.upload(recv_slot));
-    HIP_OK(h->vsites.d_recv_start.upload(recv_start));
-    HIP_OK(h->vsites.d_recv_row.upload(recv_row));
-    HIP_OK(h->vsites.d_recv_role.upload(recv_role));
-    h->vsites.receivers = (int)recv_slot.size();
-    h->vsites.count = n;
+    tgnh_context::VirtualSites f;                                // built aside: an upload that fails leaves the table in force as it was
+    HIP_OK(f.d_atoms.upload(r_atoms));
+    HIP_OK(f.d_kind.upload(r_kind));
+    HIP_OK(f.d_params.upload(r_params));
+    HIP_OK(f.recv.upload(invert_shares(std::move(shares))));
+    f.count = n;
+    h->vsites = std::move(f);                                    // (the old table's buffers are released here)
     return TGNH_OK;
 }
 
@@ -110,13 +96,6 @@ extern "C" tgnh_status tgnh_get_num_virtual_sites(tgnh_handle h, int* count) {
     return TGNH_OK;
 }
 
-static tgnh_status sites_ready(tgnh_handle h, const char* what) {
-    CHECK_H(h);
-    if (h->host_only) return fail(TGNH_ERR_STATE, std::string(what) + ": host-only handle (device -1): no GPU work can be launched on it");
-    if (!h->bound.posq) return fail(TGNH_ERR_STATE, std::string(what) + ": tgnh_bind_buffers has not been called");
-    return TGNH_OK;
-}
-
 static SiteTable site_table(tgnh_handle h) {
     SiteTable t{};
     t.atoms = h->vsites.d_atoms; t.kind = h->vsites.d_kind; t.params = h->vsites.d_params; t.n = h->vsites.count;
@@ -124,7 +103,7 @@ static SiteTable site_table(tgnh_handle h) {
 }
 
 extern "C" tgnh_status tgnh_compute_virtual_sites(tgnh_handle h, void* stream) {
-    tgnh_status rc = sites_ready(h, "tgnh_compute_virtual_sites"); if (rc) return rc;
+    tgnh_status rc = feature_ready(h, "tgnh_compute_virtual_sites", &tgnh_context::Bound::posq, false); if (rc) return rc;
     if (h->vsites.count == 0) return TGNH_OK;
     HIP_OK(hipSetDevice(h->device));
     SitePlaceArgs a{};
@@ -134,14 +113,13 @@ extern "C" tgnh_status tgnh_compute_virtual_sites(tgnh_handle h, void* stream) {
 }
 
 extern "C" tgnh_status tgnh_distribute_virtual_site_forces(tgnh_handle h, void* force, void* stream) {
-    tgnh_status rc = sites_ready(h, "tgnh_distribute_virtual_site_forces"); if (rc) return rc;
+    tgnh_status rc = feature_ready(h, "tgnh_distribute_virtual_site_forces", &tgnh_context::Bound::posq, false); if (rc) return rc;
     if (!force) return fail(TGNH_ERR_STATE, "tgnh_distribute_virtual_site_forces: no force buffer");
     if (h->vsites.count == 0) return TGNH_OK;
     HIP_OK(hipSetDevice(h->device));
     SiteSpreadArgs a{};
     a.t = site_table(h);
-    a.recv_slot = h->vsites.d_recv_slot; a.recv_start = h->vsites.d_recv_start; a.recv_row = h->vsites.d_recv_row; a.recv_role = h->vsites.d_recv_role;
-    a.n_recv = h->vsites.receivers;
+    a.recv = h->vsites.recv.view();
     a.posq = h->bound.posq; a.posq_corr = h->bound.posq_corr;
     a.force = static_cast<long long*>(force); a.padded = h->d.padded_num_particles;
     HIP_OK(launch_spread_site_forces(h->d.precision, a, (hipStream_t)stream));

@@ -5,6 +5,7 @@
 #define TGNH_VIRTUAL_SITES_H_
 
 #include "tgnh_internal.h"
+#include "tgnh_receivers.h"
 
 namespace tgnh {
 
@@ -25,15 +26,10 @@ struct SitePlaceArgs {
     void* posq; void* posq_corr;
 };
 
-// The table inverted at set time: the slots that receive a share, ascending, each with its list of (row of the table, which parent
-// of that row it is) in CSR form, in ascending row order.
+// The table and its inverse (tgnh_receivers.h): a term is a row of the table, a role 0, 1, 2 for p1, p2, p3 of that row.
 struct SiteSpreadArgs {
     SiteTable t;
-    const int* recv_slot;           // [n_recv]
-    const int* recv_start;          // [n_recv + 1] into the two arrays below
-    const int* recv_row;            // [entries] row of the table
-    const unsigned char* recv_role; // [entries] 0, 1, 2: p1, p2, p3 of that row
-    int n_recv;
+    ReceiverTable recv;
     const void* posq; const void* posq_corr;
     long long* force;         // [3 * padded] fixed point x 2^32, planes x | y | z
     int padded;

@@ -11,21 +11,19 @@
 //
 // PLACEMENT: one lane per site, rows sorted by site slot; x, y, z of the site's slot are written -- mixed precision: the fp32 value
 // and the residual into posq_correction; single: rounded once -- by stores of those three components alone: the slot is not read.
-// DISTRIBUTION: one lane per RECEIVING slot (the host inverted the table: SiteSpreadArgs), no atomics.  Per entry of the slot's list
-// the lane reads the site's fixed-point force, f = F / 2^32, forms this parent's share -- the transpose of the placement's Jacobian
-// at the current parent positions applied to f --, converts each component on its own with llrint(c * 2^32) and sums the integers in
-// list order; then one plain 64-bit load, add and store on each of the slot's three plane entries.  A parent is never a site (the
-// host checked), so no lane reads an entry another lane writes: the result is a function of the inputs alone.  A site's frame is
-// computed once per receiving parent: arithmetic, not traffic.
+// DISTRIBUTION: tgnh_receiver_device.h's form, one lane per RECEIVING slot, but one lane per row of the inverse with no grid-stride
+// loop (vs_grid).  Per entry of the slot's list the lane reads the site's fixed-point force, f = F / 2^32, and forms this parent's
+// share: the transpose of the placement's Jacobian at the current parent positions applied to f.  A parent is never a site (the
+// host checked), so no lane reads an entry another lane writes.  A site's frame is computed once per receiving parent: arithmetic,
+// not traffic.
 //   averages             w_m f
 //   out of plane         f2 = w12 f + wc (r13 x f), f3 = w13 f - wc (r12 x f), f1 = f - f2 - f3
 //   local coordinates    with u_X = px f + py (f x Z), u_Z = pz f + py (X x f) (the gradients with respect to X and Z),
 //                        t_a = (u_X - (u_X . X) X) / |a|, t_c = (u_Z - (u_Z . Z) Z) / |c| (through the two normalisations),
 //                        g_a = t_a + b x t_c, g_b = t_c x a (through the cross product):  f_m = wo_m f + wx_m g_a + wy_m g_b
-// A degenerate frame (a parallel to b) divides by zero and stores what comes out; llrint of a non-finite share is whatever the
-// conversion instruction gives.  No LDS, no atomic, no inline assembly.
+// A degenerate frame (a parallel to b) divides by zero and stores what comes out.  No LDS, no atomic, no inline assembly.
 #include "tgnh_virtual_sites.h"
-#include "tgnh_position_device.h"      // Vec3, and a parent's position as include/drude_tgnh.h defines it (slot_position)
+#include "tgnh_receiver_device.h"      // Fixed3, add_to_planes; Vec3 and a parent's position as include/drude_tgnh.h defines it (slot_position)
 
 namespace tgnh {
 
@@ -91,12 +89,12 @@ __global__ __launch_bounds__(BLOCK) void place_sites_kernel(const SitePlaceArgs 
 template <int PREC>
 __global__ __launch_bounds__(BLOCK) void spread_site_forces_kernel(const SiteSpreadArgs a) {
     const int r = blockIdx.x * BLOCK + threadIdx.x;
-    if (r >= a.n_recv) return;
-    const int slot = a.recv_slot[r];
-    const int e1 = a.recv_start[r + 1];
-    long long sx = 0, sy = 0, sz = 0;
-    for (int e = a.recv_start[r]; e < e1; e++) {
-        const int row = a.recv_row[e], role = a.recv_role[e];
+    if (r >= a.recv.n) return;
+    const int slot = a.recv.slot[r];
+    const int e1 = a.recv.start[r + 1];
+    Fixed3 sum = {0, 0, 0};                                      // (written out: `Fixed3 sum;` schedules the kernel's instructions in another order)
+    for (int e = a.recv.start[r]; e < e1; e++) {
+        const int row = a.recv.term[e], role = a.recv.role[e];
         const int4 at = a.t.atoms[row];
         const int kind = a.t.kind[row];
         const Vec3 f = {(double)a.force[at.x] * (1.0 / 4294967296.0), (double)a.force[(size_t)a.padded + at.x] * (1.0 / 4294967296.0),
@@ -120,12 +118,9 @@ __global__ __launch_bounds__(BLOCK) void spread_site_forces_kernel(const SiteSpr
                 share = (vs_param(a.t, role, row) * f + vs_param(a.t, 3 + role, row) * ga) + vs_param(a.t, 6 + role, row) * gb;
             }
         }
-        sx += llrint(share.x * 4294967296.0); sy += llrint(share.y * 4294967296.0); sz += llrint(share.z * 4294967296.0);
+        sum.add(share);
     }
-    long long* fx = a.force + slot;
-    long long* fy = a.force + (size_t)a.padded + slot;
-    long long* fz = a.force + 2 * (size_t)a.padded + slot;
-    *fx = *fx + sx; *fy = *fy + sy; *fz = *fz + sz;
+    add_to_planes(a.force, a.padded, slot, sum);
 }
 
 static bool vs_table_ok(const SiteTable& t) { return t.n >= 1 && t.atoms && t.kind && t.params; }
@@ -137,10 +132,10 @@ hipError_t launch_place_sites(int precision, const SitePlaceArgs& a, hipStream_t
 }
 
 hipError_t launch_spread_site_forces(int precision, const SiteSpreadArgs& a, hipStream_t s) {
-    if (!vs_table_ok(a.t) || a.n_recv < 1 || !a.recv_slot || !a.recv_start || !a.recv_row || !a.recv_role || !a.posq || !a.force || a.padded < 1 ||
+    if (!vs_table_ok(a.t) || !receivers_ok(a.recv) || !a.posq || !a.force || a.padded < 1 ||
         (precision == TGNH_PREC_MIXED && !a.posq_corr))
         return hipErrorInvalidValue;
-    TGNH_LAUNCH_PREC(spread_site_forces_kernel, precision, dim3(vs_grid(a.n_recv)), dim3(BLOCK), 0, s, a);
+    TGNH_LAUNCH_PREC(spread_site_forces_kernel, precision, dim3(vs_grid(a.recv.n)), dim3(BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

@@ -163,12 +163,46 @@ class PeriodicTorsionForce(_TermTable):
         self._set(index, particle1, particle2, particle3, particle4, periodicity, phase, k)
 
 
-class BondedForces:
+class _ForceCallOut:
+    """What BondedForces and NonbondedForces share: a force of the library's on `self.owner`'s handle that is computed into the owner's
+    force buffer, gives its energy, and is a force call-out.  A subclass names its two library functions and its energy's width."""
+    _COMPUTE = _ENERGY = None
+    _ENERGY_WIDTH = 0
+
+    def compute(self, energy=False):
+        """tgnh_compute_*_force(s) on the owner's force buffer: the terms are ADDED to what it holds (nothing set: no launch).
+        energy=True: the same launches leave the partial sums energy() adds.  No synchronisation."""
+        o = self.owner
+        force = getattr(o, "force", None)
+        _check(getattr(o.lib, self._COMPUTE)(o.h, None if force is None else force.data_ptr(), 1 if energy else 0, o._stream()))
+
+    def energy(self):
+        """tgnh_get_*_energy: the class's components in kJ/mol, of the positions the last compute(energy=True) read.  Synchronises."""
+        out = (C.c_double * self._ENERGY_WIDTH)()
+        _check(getattr(self.owner.lib, self._ENERGY)(self.owner.h, self.owner._stream(), out))
+        return tuple(float(e) for e in out)
+
+    def __call__(self, ctx):
+        """the form HipContext.force_fn takes"""
+        ctx.force.zero_()
+        self.compute()
+
+    def then(self, fn):
+        """-> a call-out that runs this one and then fn(ctx): for a caller who adds a force of their own behind it"""
+        def both(ctx):
+            self(ctx)
+            fn(ctx)
+        return both
+
+
+class BondedForces(_ForceCallOut):
     """The library's bonded forces on a handle (include/drude_tgnh.h: tgnh_set_bonded_forces, ...).  `owner` is a HipContext or a
     HostTopology; bonds, angles, torsions: a HarmonicBondForce / HarmonicAngleForce / PeriodicTorsionForce, the tuple its tables()
     gives, or None.  Construction hands the tables to the handle (they replace the ones in force); a shape that does not fit is
     refused here, before any library call.  An instance is a force call-out: it zeroes the context's force buffer and adds the
-    bonded forces, so `ctx.force_fn = BondedForces(ctx, ...)` is all a step, the minimiser or the barostat need."""
+    bonded forces, so `ctx.force_fn = BondedForces(ctx, ...)` is all a step, the minimiser or the barostat need.  energy():
+    (bonds, angles, torsions)."""
+    _COMPUTE, _ENERGY, _ENERGY_WIDTH = "tgnh_compute_bonded_forces", "tgnh_get_bonded_energy", 3
 
     def __init__(self, owner, bonds=None, angles=None, torsions=None):
         self.owner = owner
@@ -206,35 +240,9 @@ class BondedForces:
         _check(self.owner.lib.tgnh_get_num_bonded_terms(self.owner.h, out))
         return tuple(out)
 
-    def compute(self, energy=False):
-        """tgnh_compute_bonded_forces on the owner's force buffer: the terms are ADDED to what it holds (empty tables: no launch).
-        energy=True: the same launch leaves the partial sums energy() adds.  No synchronisation."""
-        o = self.owner
-        force = getattr(o, "force", None)
-        _check(o.lib.tgnh_compute_bonded_forces(o.h, None if force is None else force.data_ptr(), 1 if energy else 0, o._stream()))
-
-    def energy(self):
-        """tgnh_get_bonded_energy: (bonds, angles, torsions) in kJ/mol, of the positions the last compute(energy=True) read.
-        Synchronises."""
-        out = (C.c_double * 3)()
-        _check(self.owner.lib.tgnh_get_bonded_energy(self.owner.h, self.owner._stream(), out))
-        return tuple(float(e) for e in out)
-
     def clear(self):
         """all three counts 0: the tables are gone, compute() launches nothing"""
         _check(self.owner.lib.tgnh_set_bonded_forces(self.owner.h, 0, None, None, 0, None, None, 0, None, None, None))
-
-    def __call__(self, ctx):
-        """the form HipContext.force_fn takes"""
-        ctx.force.zero_()
-        self.compute()
-
-    def then(self, fn):
-        """-> a call-out that runs this one and then fn(ctx): for a caller who adds a nonbonded force of their own"""
-        def both(ctx):
-            self(ctx)
-            fn(ctx)
-        return both
 
 
 class _NonbondedDesc(C.Structure):
@@ -359,12 +367,14 @@ class NonbondedForce:
                 np.ascontiguousarray(exc[:, :2], np.int32), np.ascontiguousarray(exc[:, 2:]))
 
 
-class NonbondedForces:
+class NonbondedForces(_ForceCallOut):
     """The library's NonbondedForce on a handle (include/drude_tgnh.h: tgnh_set_nonbonded_force, ...).  `owner` is a HipContext or a
     HostTopology; `force` a NonbondedForce, the tuple its tables() gives, or None (nothing set).  Construction hands the table to
     the handle (it replaces the one in force); a shape that does not fit is refused here, before any library call.  The box is the
     handle's (setPeriodicBoxVectors).  An instance is a force call-out, and `BondedForces(ctx, ...).then(lambda c: nb.compute())`
-    adds it behind the bonded forces."""
+    adds it behind the bonded forces.  energy(): (pair Coulomb with the reaction field, pair Lennard-Jones, exception Coulomb,
+    exception Lennard-Jones)."""
+    _COMPUTE, _ENERGY, _ENERGY_WIDTH = "tgnh_compute_nonbonded_force", "tgnh_get_nonbonded_energy", 4
 
     def __init__(self, owner, force=None):
         self.owner = owner
@@ -394,32 +404,6 @@ class NonbondedForces:
         _check(self.owner.lib.tgnh_get_num_nonbonded_terms(self.owner.h, out))
         return tuple(out)
 
-    def compute(self, energy=False):
-        """tgnh_compute_nonbonded_force on the owner's force buffer: the terms are ADDED to what it holds (no table: no launch).
-        energy=True: the same launches leave the partial sums energy() adds.  No synchronisation."""
-        o = self.owner
-        force = getattr(o, "force", None)
-        _check(o.lib.tgnh_compute_nonbonded_force(o.h, None if force is None else force.data_ptr(), 1 if energy else 0, o._stream()))
-
-    def energy(self):
-        """tgnh_get_nonbonded_energy: (pair Coulomb with the reaction field, pair Lennard-Jones, exception Coulomb, exception
-        Lennard-Jones) in kJ/mol, of the positions the last compute(energy=True) read.  Synchronises."""
-        out = (C.c_double * 4)()
-        _check(self.owner.lib.tgnh_get_nonbonded_energy(self.owner.h, self.owner._stream(), out))
-        return tuple(float(e) for e in out)
-
     def clear(self):
         """the table is gone, compute() launches nothing"""
         _check(self.owner.lib.tgnh_set_nonbonded_force(self.owner.h, None))
-
-    def __call__(self, ctx):
-        """the form HipContext.force_fn takes"""
-        ctx.force.zero_()
-        self.compute()
-
-    def then(self, fn):
-        """-> a call-out that runs this one and then fn(ctx)"""
-        def both(ctx):
-            self(ctx)
-            fn(ctx)
-        return both

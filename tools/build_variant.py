@@ -9,7 +9,7 @@ sys.path.insert(0, root)
 from openmm_drudenose_amd.build import SOURCES
 from concurrent.futures import ThreadPoolExecutor
 base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip"] + defs
-objs = [out + "." + os.path.splitext(s)[0] + ".o" for s in SOURCES]
+objs = [out + "." + s + ".o" for s in SOURCES]      # (by the whole name: tgnh_minimize.cpp and tgnh_minimize.hip are two objects)
 with ThreadPoolExecutor(len(SOURCES)) as pool:      # one hipcc per source file, side by side (as build.py)
     list(pool.map(lambda so: subprocess.run(base + ["-c", os.path.join(csrc, so[0]), "-o", so[1]], check=True, stderr=subprocess.DEVNULL), zip(SOURCES, objs)))
 subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-ldl", "-o", out], check=True)

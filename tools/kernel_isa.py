@@ -6,14 +6,18 @@ device code exactly when `diff` finds their two lists equal -- the check of a re
 What depends on a kernel's position in its unit is normalised away: the `__hip_cuid_` lines, the unit-wide numbering of local labels
 (`.LBB<n>_<m>` -> `.LBB_<m>`, also where a comment names a loop header `BB<n>_<m>`; `.Lfunc_end<n>`, `.LJTI<n>_<m>`, `.Ltmp<n>`), `.file` / `.loc` / `.ident` lines.
 
-    tools/kernel_isa.py [--asm DIR] [extra hipcc flags, e.g. -DTGNH_TRACE]     (--asm keeps the assembly files in DIR)
+    tools/kernel_isa.py [--asm DIR] [--parts] [extra hipcc flags, e.g. -DTGNH_TRACE]     (--asm keeps the assembly files in DIR)
+
+--parts prints two more hashes per kernel, of the descriptor block alone and of the body's sorted opcodes: two kernels that differ
+in the first hash and agree in these two hold the same instructions under the same resources in another order.
 """
 import hashlib, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "openmm_drudenose_amd", "csrc")
 args = sys.argv[1:]
 keep = args.pop(args.index("--asm") + 1) if "--asm" in args else None
-args = [a for a in args if a != "--asm"]
+parts = "--parts" in args
+args = [a for a in args if a not in ("--asm", "--parts")]
 
 
 def normalise(line):
@@ -40,7 +44,12 @@ def kernels(asm):
         if in_desc: desc[in_desc].append(normalise(line))
         if cur and re.match(r"^\.Lfunc_end\d+:", line): cur = None
         if in_desc and ".end_amdhsa_kernel" in line: in_desc = None
-    return {k: hashlib.sha256("".join(body[k] + desc[k]).encode()).hexdigest()[:16] for k in desc}
+    sha = lambda lines: hashlib.sha256("".join(lines).encode()).hexdigest()[:16]
+    if not parts:
+        return {k: sha(body[k] + desc[k]) for k in desc}
+    # an instruction: an indented line that is neither a directive nor a comment; its opcode is the first word
+    opcodes = lambda lines: sorted(l.split()[0] + "\n" for l in lines if l[:1] not in ".;" and not re.match(r"^[\w.$]+:", l) and l.strip())
+    return {k: " ".join([sha(body[k] + desc[k]), sha(desc[k]), sha(opcodes(body[k]))]) for k in desc}
 
 
 def compile_one(name, tmp):

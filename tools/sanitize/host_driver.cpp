@@ -2,12 +2,15 @@
 // tgnh_set_velocities_to_temperature, the argument checks of the centre-of-mass and velocity-rescaling calls, the molecule table of tgnh_scale_positions, and the periodic
 // box, tgnh_get_frame_count and the argument order of tgnh_wrap_molecules / tgnh_write_frame, and the minimiser's argument checks and refusals, through a host-only handle (device -1),
 // no Python in the process.  What needs a device --
-// the upload of the retargeted block, the partner table's first use and the launch -- is not reached here.
+// the upload of the retargeted block, the partner table's first use and the launch -- is not reached here.  And, without a handle, the
+// inversion of a force's shares into receiving slots (tgnh_receivers.h) against a brute-force restatement.
 #include <cmath>
 #include <cstdio>
+#include <utility>
 #include <vector>
 
 #include "../../include/drude_tgnh.h"
+#include "../../openmm_drudenose_amd/csrc/tgnh_receivers.h"
 
 #define EXPECT(cond) do { if (!(cond)) { std::fprintf(stderr, "host_driver: %s failed (line %d): %s\n", #cond, __LINE__, tgnh_last_error()); return 1; } } while (0)
 
@@ -170,7 +173,43 @@ static int run(int mode, int chains, int drude_chains) {
     return 0;
 }
 
+// invert_shares against its definition: for every slot in ascending order, the (term, role) of its shares in push order
+static int inversion_case(const char* name, const std::vector<tgnh::Share>& shares, int slots) {
+    const tgnh::ReceiverLists got = tgnh::invert_shares(shares);
+    std::vector<int> slot, start, term;
+    std::vector<unsigned char> role;
+    for (int s = 0; s < slots; s++) {
+        const size_t first = term.size();
+        for (const tgnh::Share& sh : shares)
+            if (sh.slot == s) { term.push_back(sh.term); role.push_back(sh.role); }
+        if (term.size() > first) { slot.push_back(s); start.push_back((int)first); }
+    }
+    start.push_back((int)term.size());
+    const char* wrong = term.size() != shares.size() ? "a share outside [0, slots)" : got.slot != slot ? "slot" : got.start != start ? "start" :
+                        got.term != term ? "term" : got.role != role ? "role" : nullptr;
+    if (wrong) std::fprintf(stderr, "host_driver: invert_shares, %s: %s differs from the restatement\n", name, wrong);
+    return wrong ? 1 : 0;
+}
+
+static int inversion() {
+    const int top = 184;                                          // the highest slot of run()'s handle
+    int bad = inversion_case("no share", {}, top + 1);
+    bad += inversion_case("one share", {{7, 0, 1}}, top + 1);
+    // slot 5 receives from terms 0, 1 and 2, pushed between shares of higher and lower slots
+    bad += inversion_case("three terms on a slot", {{9, 0, 0}, {5, 0, 1}, {5, 1, 0}, {2, 1, 1}, {11, 2, 0}, {5, 2, 1}, {0, 2, 2}}, top + 1);
+    bad += inversion_case("two shares of a term", {{4, 0, 0}, {3, 0, 1}, {3, 1, 0}, {4, 1, 1}}, top + 1);
+    bad += inversion_case("the highest slot", {{top, 0, 0}, {0, 0, 1}, {top, 1, 2}, {top - 1, 1, 0}}, top + 1);
+    std::vector<tgnh::Share> many;                                // 300 shares over 64 slots: terms ascending, 1 to 4 shares each, from an LCG
+    uint32_t x = 12345;
+    auto next = [&x]() { x = x * 1664525u + 1013904223u; return x >> 8; };
+    for (int t = 0; many.size() < 300; t++)
+        for (int m = 0, k = 1 + (int)(next() % 4); m < k; m++) many.push_back({(int)(next() % 64), t, (unsigned char)m});
+    bad += inversion_case("300 random shares", many, 64);
+    return bad;
+}
+
 int main() {
+    if (inversion()) return 1;
     if (run(TGNH_MODE_TGNH, 3, 1) || run(TGNH_MODE_DUALNH, 3, 1) || run(TGNH_MODE_DUALNH, 2, 0) || run(TGNH_MODE_TGNH, 1, 1)) return 1;
     std::puts("host_driver: ok");
     return 0;
