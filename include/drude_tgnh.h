@@ -1084,8 +1084,9 @@ tgnh_status tgnh_get_bonded_energy(tgnh_handle h, void* stream, double out[3] /*
  * the glue calls none of this): Coulomb with a reaction field and Lennard-Jones between all particles inside a cutoff of a rectangular
  * periodic box, and OpenMM's exceptions -- the intermolecular half of a force field beside the DrudeForce and the bonded forces above.
  * The definitions are OpenMM's NonbondedForce with CutoffPeriodic, recalled from its published documentation, as oracle/water_ff.c
- * restates them; OpenMM was not at hand to check against.  NOT BUILT: Ewald and PME, the switching function, the long-range dispersion
- * correction, triclinic cells, a Verlet list with a skin (the cells are rebuilt by every call, so the call stays stateless).
+ * restates them; OpenMM was not at hand to check against.  Lattice-summed electrostatics: EWALD SUMMATION below, switched on by a call
+ * of its own on top of this table.  NOT BUILT: PME, the switching function, the long-range dispersion correction, triclinic cells,
+ * sharded pairs, a Verlet list with a skin (the cells are rebuilt by every call, so the call stays stateless).
  *
  * tgnh_set_nonbonded_force.  desc->particles [n][3] = (charge e, sigma nm, epsilon kJ/mol), one row per slot of the bound arrays:
  * charges come from this table, posq.w is neither read nor written.  exception_particles [ne][2] = (p1, p2), exception_params [ne][3] =
@@ -1181,6 +1182,84 @@ tgnh_status tgnh_set_nonbonded_force(tgnh_handle h, const tgnh_nonbonded_desc* d
 tgnh_status tgnh_get_num_nonbonded_terms(tgnh_handle h, int out[3]);                    /* particles, exceptions, of which evaluated */
 tgnh_status tgnh_compute_nonbonded_force(tgnh_handle h, void* force, int want_energy, void* stream);   /* ADDS; capturable */
 tgnh_status tgnh_get_nonbonded_energy(tgnh_handle h, void* stream, double out[4]);      /* pair Coulomb (with reaction field), pair LJ, exception Coulomb, exception LJ; synchronises */
+
+/* EWALD SUMMATION on top of the table above: OpenMM's `Ewald` method, an explicit sum over reciprocal vectors with no FFT.  The cost is
+ * O(n M), M the number of reciprocal vectors: it suits boxes of up to a few ten thousand slots, and is what a later PME is checked
+ * against; PME is NOT BUILT.  tgnh_set_nonbonded_force's descriptor, checks and texts are unchanged (methods 3, 4, 5 are refused there
+ * as before): Ewald is switched on by tgnh_set_nonbonded_ewald while a CutoffPeriodic table is in force, and every
+ * tgnh_set_nonbonded_force, a clearing one included, drops the setting again.  With no Ewald setting nothing below is allocated or
+ * launched, and tgnh_compute_nonbonded_force is what it was, launch for launch and bit for bit.
+ *
+ * tgnh_set_nonbonded_ewald(desc).  desc == NULL: back to the reaction field.  Every check runs before any device work, so a host-only
+ * handle gives the same answers.  TGNH_ERR_STATE: no nonbonded table is set.  TGNH_ERR_ARG, with the reason in tgnh_last_error(): a
+ * struct_size that is not sizeof(tgnh_ewald_desc); an alpha that is not finite or <= 0; a kmax component < 0 or > 255.
+ * TGNH_ERR_UNSUPPORTED: M > 2^20.  A refused call leaves whatever was in force untouched.  The reciprocal vectors are the (nx, ny, nz)
+ * != 0 with |n_d| <= kmax_d whose first non-zero component is positive, a half space of
+ *   M = ((2 kmax_x + 1)(2 kmax_y + 1)(2 kmax_z + 1) - 1) / 2
+ * vectors, stored in the order nx, then ny, then nz, ascending; kmax = (0, 0, 0) is legal and means no reciprocal part.  Not inside a
+ * stream capture: the table of vectors, the partial-sum rows (sized from n and M), the receiver table of the exclusion correction and
+ * the set-time constants are allocated and uploaded here, synchronously, so that the compute call never grows anything because of
+ * Ewald.  The call has no stream of its own: it returns TGNH_ERR_STATE when the stream of the handle's last
+ * tgnh_compute_nonbonded_force is capturing; a capture on a stream this handle has not seen is the caller's to avoid.  Formed here,
+ * once, in fp64, each operation rounded on its own (pi = 3.14159265358979323846, sqrt the IEEE one):
+ *   tsp    = (2 alpha) / sqrt(pi)                 a4 = 4 (alpha alpha)
+ *   E_self = -((K (alpha / sqrt(pi))) sum q q)    the sum over the table's charges in slot order
+ *   bgn    = ((pi K) (Q Q)) / (2 (alpha alpha))   Q the table's net charge, summed in slot order
+ * tgnh_get_nonbonded_ewald: the setting in force (out->struct_size 0: off) and M.
+ *
+ * With Ewald on, tgnh_compute_nonbonded_force(force, want_energy) adds the terms below.  Everything in fp64 in every precision, every
+ * operation rounded on its own in the order written; x(i), K, L as above; V = (Lx Ly) Lz; erfc, erf, exp and sincospi are the device
+ * library's (a restatement with another library's cannot give the same bits: tests/test_ewald.py measures how far one is off).
+ * DIRECT SPACE.  The pair launch: the same pairs, minimum image, cutoff and Lennard-Jones lines as PAIRS above; the Coulomb part is
+ *   ar   = alpha r
+ *   ec   = erfc(ar)
+ *   g    = exp(-(ar ar))
+ *   dc   = qq (-((ec inv + tsp g) inv))
+ *   E_C  = qq (ec inv)
+ * Both lanes of a pair hold the same r bits, hence the same ec and g: the pair's two integer shares still cancel exactly.
+ * EXCLUSION CORRECTION.  Every exception row (p1, p2), evaluated or not, whose particles' table charges have a non-zero product; no
+ * cutoff and no periodic image (the bonded rule).  For the share of particle a of the row, b the other one:
+ *   d_k  = x_k(a) - x_k(b);   r2 = (dx dx + dy dy) + dz dz;   qq = K (q_p1 q_p2)
+ *   r2 == 0 (a Drude particle on its parent): no force, E = -(qq tsp)
+ *   otherwise r = sqrt(r2), inv = 1 / r, ar = alpha r
+ *   ef   = erf(ar)
+ *   g    = exp(-(ar ar))
+ *   dc   = qq ((ef inv - tsp g) inv)
+ *   c    = -(dc inv)
+ *   particle a receives llrint((c d_k) 4294967296.0) per component
+ *   E    = -(qq (ef inv))
+ * One lane per receiving slot over the rows inverted at set time, as the evaluated exceptions; those stay as they are.
+ * RECIPROCAL SPACE.  For slot j: s_d = x_d / L_d, then s_d = s_d - floor(s_d) (the cell build's two lines); for vector m = (nx, ny, nz):
+ *   t     = (nx sx + ny sy) + nz sz               the phase in turns
+ *   (sin, cos) = sincospi(2 t)
+ *   C_m   = sum_j q_j cos      S_m = sum_j q_j sin        over parts of 4096 consecutive slots: within a part in slot order from 0,
+ *                                                         then the parts in order from 0
+ *   k_d   = ((2 pi) n_d) / L_d      k2 = (kx kx + ky ky) + kz kz      A_m = exp(-(k2 / a4)) / k2
+ *   w_im  = (A_m C_m) sin_im - (A_m S_m) cos_im           g_d = sum_m k_md w_im    in the table's order, from 0
+ *   slot i receives llrint((((8 (pi K)) / V) q_i) g_d 4294967296.0) once per component; a slot with charge 0 receives nothing
+ *   E_rec = ((4 (pi K)) / V) sum_m A_m (C_m C_m + S_m S_m)      summed as the other energies' rows are
+ * E_bg = -(bgn / V), formed on the device with the box of the call, as A_m and k_m are: a box that changes between calls needs no
+ * reset, and a captured call stays correct for the box it recorded.
+ * ORDER.  No floating-point atomic anywhere, no atomic on the force buffer; every sum's order depends on n, M and the tables alone,
+ * not on the device or the grid: the same positions, box and tables give the same bits from a tiled, a TGNH_FLAG_GATHER and a DUALNH
+ * handle, asked once or twice, run eagerly or replayed from a graph.  The direct and exclusion parts stay a function of positions,
+ * box and tables alone, and a permutation of the slots permutes their bits.  The reciprocal part is NOT permutation-invariant bit for
+ * bit: C_m and S_m are summed in slot order.
+ * LAUNCHES.  The memset and five or six kernels of the call stay; Ewald adds one kernel when some exception row has charged partners
+ * and three when M > 0 (sum, finalise, force): a function of the tables alone, never of n.  The call stays capturable.
+ * ENERGIES.  tgnh_get_nonbonded_energy keeps its four slots; slot 0 is the direct-space sum while Ewald is on.  tgnh_get_ewald_energy
+ * enqueues a one-work-group sum, synchronises `stream` and returns out[0] = E_rec, out[1] = E_self, out[2] = E_bg, out[3] = the
+ * exclusion correction, kJ/mol, of the last want_energy call.  TGNH_ERR_STATE: Ewald is off; no tgnh_compute_nonbonded_force with
+ * want_energy since the setting or the table was made, or since the per-cell buffers last grew; a host-only handle, buffers not
+ * bound.  TGNH_ERR_ARG: out is NULL.  Setting or clearing Ewald closes tgnh_get_nonbonded_energy until the next want_energy call. */
+typedef struct tgnh_ewald_desc {
+    uint32_t struct_size;             /* sizeof(tgnh_ewald_desc); anything else: TGNH_ERR_ARG */
+    int32_t kmax[3];                  /* reciprocal vectors n_d in [-kmax_d, kmax_d]; (0, 0, 0) is legal: no reciprocal part */
+    double alpha;                     /* nm^-1 */
+} tgnh_ewald_desc;
+tgnh_status tgnh_set_nonbonded_ewald(tgnh_handle h, const tgnh_ewald_desc* d);          /* NULL: back to the reaction field */
+tgnh_status tgnh_get_nonbonded_ewald(tgnh_handle h, tgnh_ewald_desc* out, int* num_kvectors);   /* struct_size 0 in *out: off */
+tgnh_status tgnh_get_ewald_energy(tgnh_handle h, void* stream, double out[4]);          /* reciprocal, self, neutralising background, exclusion correction; synchronises */
 
 /* The call-outs of the reference's own testWater (platforms/reference/tests/TestReferenceDrudeTGNHIntegrator.cpp:111-166),
  * harness only: its force field -- NonbondedForce with reaction field, cutoff `cutoff` in a cubic box of edge `box`, +

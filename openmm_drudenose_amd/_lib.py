@@ -92,6 +92,11 @@ class TgnhMinimizeState(C.Structure):
     ]
 
 
+class TgnhEwaldDesc(C.Structure):
+    """tgnh_ewald_desc (tgnh_set_nonbonded_ewald)"""
+    _fields_ = [("struct_size", C.c_uint32), ("kmax", C.c_int32 * 3), ("alpha", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p)
 
 # name -> (restype, argtypes); every symbol include/drude_tgnh.h declares
@@ -210,6 +215,10 @@ SIGNATURES = {
     "tgnh_get_num_nonbonded_terms": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "tgnh_compute_nonbonded_force": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tgnh_get_nonbonded_energy": (C.c_int, [C.c_void_p, C.c_void_p, c_f64p]),
+    # (desc / out: a TgnhEwaldDesc by reference)
+    "tgnh_set_nonbonded_ewald": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tgnh_get_nonbonded_ewald": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "tgnh_get_ewald_energy": (C.c_int, [C.c_void_p, C.c_void_p, c_f64p]),
     "tgnh_harness_water_force": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "tgnh_harness_remove_cm_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tgnh_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),

@@ -241,7 +241,28 @@ struct tgnh_context {
         tgnh::DeviceBuf<int> d_count, d_cell_start;       // [2 cells_allocated], [cells_allocated + 1]
         tgnh::DeviceBuf<int2> d_chunks;           // [cells_allocated + ceil(particles / 64)]
         tgnh::DeviceBuf<double> d_pair_rows;      // [pair grid of cells_allocated][4]
+        std::vector<double> h_charge;             // [particles] the table's charges, and
+        std::vector<int2> h_exc;                  // [exceptions] every row's (p1, p2) in the caller's order: what tgnh_set_nonbonded_ewald builds from (a handle with a device only)
+        hipStream_t last_stream = nullptr;        // of the last tgnh_compute_nonbonded_force: a setter has no stream of its own to ask about a capture
     } nonbonded;
+    struct Ewald {                    // tgnh_set_nonbonded_ewald (tgnh_ewald.cpp), on top of the table above; tgnh_set_nonbonded_force assigns a fresh value
+        bool on = false;
+        int kmax[3] = {0, 0, 0};
+        double alpha = 0, tsp = 0, a4 = 0;        // tsp = 2 alpha / sqrt(pi), a4 = 4 (alpha alpha)
+        double e_self = 0, bg_num = 0;            // -K (alpha / sqrt(pi)) sum q^2 in slot order; ((pi K) (Q Q)) / (2 (alpha alpha))
+        int vectors = 0, parts = 0;               // M; ceil(particles / EW_PART)   (a host-only handle keeps the scalars down to here and nothing else)
+        int corrected = 0;                        // exception rows whose particles' charges have a non-zero product
+        bool energy_launched = false;             // a want_energy call has filled the rows since Ewald was set
+        tgnh::DeviceBuf<int4> d_kvec;             // [vectors] (nx, ny, nz, 0); uploaded at set time, as everything below is allocated there
+        tgnh::DeviceBuf<double2> d_part_rows;     // [parts][vectors]
+        tgnh::DeviceBuf<double> d_coef;           // [vectors][5]
+        tgnh::DeviceBuf<double> d_rec_rows;       // [index_grid(vectors)][4]
+        tgnh::DeviceBuf<int2> d_exc_atoms;        // [corrected] (p1, p2)
+        tgnh::Receivers recv;                     // the slots that receive a share of some corrected row
+        tgnh::DeviceBuf<double> d_exc_rows;       // [index_grid(recv.n)][4]
+        tgnh::DeviceBuf<double> d_misc;           // [2] {E_bg, (4 (pi K)) / V} of the last want_energy call's box
+        tgnh::DeviceBuf<double> d_totals;         // [4] where the energy's sum lands
+    } ewald;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block
         std::vector<double> local_terms, global_terms;   // per thermostat, before CMM correction

@@ -1,7 +1,7 @@
 // tgnh_host.h -- what the host units behind the C ABI (include/drude_tgnh.h) share: tgnh_topology.cpp, tgnh_lifecycle.cpp,
-// tgnh_exchange.cpp, tgnh_step.cpp, tgnh_velocities.cpp, tgnh_queries.cpp, tgnh_positions.cpp, tgnh_frames.cpp, tgnh_minimize.cpp, tgnh_constraints.cpp, tgnh_virtual_sites.cpp, tgnh_drude_force.cpp, tgnh_bonded.cpp, tgnh_nonbonded.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
+// tgnh_exchange.cpp, tgnh_step.cpp, tgnh_velocities.cpp, tgnh_queries.cpp, tgnh_positions.cpp, tgnh_frames.cpp, tgnh_minimize.cpp, tgnh_constraints.cpp, tgnh_virtual_sites.cpp, tgnh_drude_force.cpp, tgnh_bonded.cpp, tgnh_nonbonded.cpp, tgnh_ewald.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
 // live in tgnh_kernels.hip (tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h), tgnh_gather.hip, tgnh_velinit.hip,
-// tgnh_drude_stats.hip, tgnh_cm_motion.hip, tgnh_rescale.hip, tgnh_scale_positions.hip, tgnh_wrap.hip, tgnh_minimize.hip, tgnh_constraints.hip, tgnh_virtual_sites.hip, tgnh_drude_force.hip, tgnh_bonded.hip, tgnh_nonbonded.hip, tgnh_vplanes.hip and tgnh_harness.hip.
+// tgnh_drude_stats.hip, tgnh_cm_motion.hip, tgnh_rescale.hip, tgnh_scale_positions.hip, tgnh_wrap.hip, tgnh_minimize.hip, tgnh_constraints.hip, tgnh_virtual_sites.hip, tgnh_drude_force.hip, tgnh_bonded.hip, tgnh_nonbonded.hip, tgnh_ewald.hip, tgnh_vplanes.hip and tgnh_harness.hip.
 // The library's forces (virtual sites, DrudeForce, bonded, the nonbonded exceptions) share one form, said once: the table of receiving
 // slots and its inversion in tgnh_receivers.h, its owner in tgnh_context.h (Receivers), the lane's loop in tgnh_receiver_device.h.
 //

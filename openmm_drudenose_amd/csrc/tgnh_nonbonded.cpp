@@ -1,11 +1,12 @@
 // tgnh_nonbonded.cpp -- the library's NonbondedForce: the particle table and the exceptions (checks, krf and crf formed in fp64, the
 // exclusion lists per slot, the evaluated exceptions' shares by receiving slot), tgnh_compute_nonbonded_force (the box's checks,
 // the cell grid, the per-cell buffers, the launches) and tgnh_get_nonbonded_energy (tgnh_nonbonded.hip has the kernels;
-// include/drude_tgnh.h the contract)
+// include/drude_tgnh.h the contract).  With Ewald summation on (tgnh_set_nonbonded_ewald, tgnh_ewald.cpp) the compute call hands the pair
+// launch alpha and adds tgnh_ewald.hip's launches behind the exceptions.
 #include <climits>
 
 #include "tgnh_host.h"
-#include "tgnh_nonbonded.h"
+#include "tgnh_ewald.h"
 
 #pragma clang fp contract(off)      // krf and crf are part of the contract: every operation rounded on its own
 
@@ -19,6 +20,7 @@ extern "C" tgnh_status tgnh_set_nonbonded_force(tgnh_handle h, const tgnh_nonbon
     if (!d || d->num_particles == 0) {
         if (!h->host_only) HIP_OK(hipSetDevice(h->device));
         h->nonbonded = tgnh_context::Nonbonded();
+        h->ewald = tgnh_context::Ewald();                        // (Ewald summation rests on the table: it goes with it)
         return TGNH_OK;
     }
     if (d->method != TGNH_NB_CUTOFF_PERIODIC)
@@ -72,7 +74,7 @@ extern "C" tgnh_status tgnh_set_nonbonded_force(tgnh_handle h, const tgnh_nonbon
     const double rc = d->cutoff, eps = d->reaction_field_dielectric;
     f.krf = ((1.0 / ((rc * rc) * rc)) * (eps - 1.0)) / (2.0 * eps + 1.0);
     f.crf = ((1.0 / rc) * (3.0 * eps)) / (2.0 * eps + 1.0);
-    if (h->host_only) { h->nonbonded = std::move(f); return TGNH_OK; }
+    if (h->host_only) { h->nonbonded = std::move(f); h->ewald = tgnh_context::Ewald(); return TGNH_OK; }
     HIP_OK(hipSetDevice(h->device));
     // the exclusion lists: every exception row, evaluated or not, under both of its slots, ascending
     std::vector<int> excl_start((size_t)N + 1, 0), excl(2 * (size_t)ne);
@@ -117,7 +119,11 @@ extern "C" tgnh_status tgnh_set_nonbonded_force(tgnh_handle h, const tgnh_nonbon
     HIP_OK(f.d_sorted_range.alloc((size_t)N));
     HIP_OK(f.d_n_chunks.alloc(1, true));
     HIP_OK(f.d_totals.alloc(4, true));
+    f.h_charge.resize((size_t)N); f.h_exc.resize((size_t)ne);
+    for (int i = 0; i < N; i++) f.h_charge[i] = d->particles[3 * (size_t)i];
+    for (int r = 0; r < ne; r++) f.h_exc[r] = make_int2(d->exception_particles[2 * (size_t)r], d->exception_particles[2 * (size_t)r + 1]);
     h->nonbonded = std::move(f);                                 // (the old tables' buffers are released here)
+    h->ewald = tgnh_context::Ewald();
     return TGNH_OK;
 }
 
@@ -176,6 +182,9 @@ extern "C" tgnh_status tgnh_compute_nonbonded_force(tgnh_handle h, void* force, 
     a.placed = f.d_placed; a.sorted = f.d_sorted; a.sorted_slot = f.d_sorted_slot; a.sorted_range = f.d_sorted_range;
     a.force = static_cast<long long*>(force); a.padded = h->d.padded_num_particles;
     a.rows = want_energy ? f.d_pair_rows.get() : nullptr;
+    tgnh_context::Ewald& ew = h->ewald;
+    if (ew.on) { a.alpha = ew.alpha; a.tsp = ew.tsp; a.bg_num = ew.bg_num; a.ew_misc = ew.d_misc; }
+    f.last_stream = s;
     HIP_OK(hipMemsetAsync(f.d_count, 0, 2 * (size_t)ncells * sizeof(int), s));
     for (int stage = 0; stage < 4; stage++) {
         Timed t(h, s, KID_OTHER);
@@ -195,8 +204,34 @@ extern "C" tgnh_status tgnh_compute_nonbonded_force(tgnh_handle h, void* force, 
         Timed t(h, s, KID_OTHER);
         HIP_OK(launch_nonbonded_exceptions(h->d.precision, x, s));
     }
+    if (ew.on && ew.corrected) {
+        EwaldExclusionArgs x{};
+        x.atoms = ew.d_exc_atoms; x.par = f.d_par;
+        x.recv = ew.recv.view();
+        x.posq = h->bound.posq; x.posq_corr = h->bound.posq_corr;
+        x.alpha = ew.alpha; x.tsp = ew.tsp;
+        x.force = a.force; x.padded = a.padded;
+        x.rows = want_energy ? ew.d_exc_rows.get() : nullptr;
+        Timed t(h, s, KID_OTHER);
+        HIP_OK(launch_ewald_exclusions(h->d.precision, x, s));
+    }
+    if (ew.on && ew.vectors > 0) {
+        EwaldArgs r{};
+        r.n = n; r.m = ew.vectors; r.parts = ew.parts;
+        r.kvec = ew.d_kvec; r.par = f.d_par;
+        r.posq = h->bound.posq; r.posq_corr = h->bound.posq_corr;
+        for (int k = 0; k < 3; k++) r.box[k] = L[k];
+        r.a4 = ew.a4;
+        r.part_rows = ew.d_part_rows; r.coef = ew.d_coef;
+        r.rows = want_energy ? ew.d_rec_rows.get() : nullptr;
+        r.force = a.force; r.padded = a.padded;
+        for (int stage = 0; stage < 3; stage++) {
+            Timed t(h, s, KID_OTHER);
+            HIP_OK(launch_ewald_reciprocal(h->d.precision, r, s, stage));
+        }
+    }
     // (a launch recorded into a stream capture has not run: it fills the rows when the graph is replayed, and does not count here)
-    if (want_energy && !stream_capturing(s)) { f.energy_launched = true; f.energy_rows = nb_pair_grid(n, a.ncells); }
+    if (want_energy && !stream_capturing(s)) { f.energy_launched = true; f.energy_rows = nb_pair_grid(n, a.ncells); ew.energy_launched = ew.on; }
     return TGNH_OK;
 }
 

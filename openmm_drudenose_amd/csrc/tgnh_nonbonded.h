@@ -10,6 +10,7 @@
 namespace tgnh {
 
 constexpr double NB_COULOMB = 138.935456;         // K, kJ nm / (mol e^2): the project's constant (oracle/water_ff.c, tgnh_drude_force.hip)
+constexpr double NB_PI = 3.14159265358979323846;
 constexpr double NB_CELL_MARGIN = 1.001;          // a cell is at least this many cutoffs wide
 constexpr int NB_WAVES = BLOCK / 64;              // wavefronts, and chunks, per work-group of the pair launch
 constexpr long long NB_MAX_CELLS = 1LL << 24;     // more cells than this: TGNH_ERR_UNSUPPORTED (the scan is one work-group)
@@ -39,6 +40,10 @@ struct NonbondedArgs {
     long long* force;               // [3 * padded] fixed point x 2^32, planes x | y | z
     int padded;
     double* rows;                   // want_energy: [pair_grid][4] a work-group's {E_C, E_LJ, 0, 0}; nullptr: forces only
+    // tgnh_set_nonbonded_ewald (alpha > 0; 0: the reaction field).  The pair launch takes its Ewald instantiation: erfc pairs
+    double alpha, tsp;              // tsp = 2 alpha / sqrt(pi), formed on the host
+    double bg_num;                  // ((pi K) (Q Q)) / (2 (alpha alpha)), Q the net charge: E_bg = -(bg_num / V)
+    double* ew_misc;                // want_energy: [2] {E_bg, (4 (pi K)) / V} of the call's box, written by the pair launch
 };
 
 // The evaluated exceptions and their inverse (tgnh_receivers.h): a term is a row, a role 0 for the row's p1, 1 for its p2

@@ -64,7 +64,7 @@ __device__ __forceinline__ double min_image(const double d, const double L) {
     return d - L * rint(d / L);
 }
 
-template <bool ENERGY>
+template <bool ENERGY, bool EWALD = false>
 __device__ __forceinline__ void pair_wave(const NonbondedArgs& a, NbImage& img, const int w, const int wave, double& e_c, double& e_lj) {
     const int lane = threadIdx.x & 63;
     const size_t n = (size_t)a.n;
@@ -116,12 +116,20 @@ __device__ __forceinline__ void pair_wave(const NonbondedArgs& a, NbImage& img, 
                         const double e4 = 4.0 * sqrt(ei * img.v[w][5][k]);
                         const double s2 = (sig * sig) / r2;
                         const double s6 = (s2 * s2) * s2, s12 = s6 * s6;
-                        const double dc = qq * ((2.0 * a.krf) * r - inv * inv);
+                        double dc, ec = 0.0;
+                        if (EWALD) {
+                            const double ar = a.alpha * r;
+                            ec = erfc(ar);
+                            const double g = exp(-(ar * ar));
+                            dc = qq * (-((ec * inv + a.tsp * g) * inv));
+                        } else {
+                            dc = qq * ((2.0 * a.krf) * r - inv * inv);
+                        }
                         const double dl = (e4 * (6.0 * s6 - 12.0 * s12)) * inv;
                         const double c = -((dc + dl) * inv);
                         fx += llrint((c * dx) * NB_FIXED); fy += llrint((c * dy) * NB_FIXED); fz += llrint((c * dz) * NB_FIXED);
                         if (ENERGY && js > slot) {
-                            e_c = e_c + qq * ((inv + a.krf * r2) - a.crf);
+                            e_c = e_c + (EWALD ? qq * (ec * inv) : qq * ((inv + a.krf * r2) - a.crf));
                             e_lj = e_lj + e4 * (s12 - s6);
                         }
                     }
@@ -216,6 +224,29 @@ __global__ __launch_bounds__(BLOCK) void nb_pair_energy_kernel(const NonbondedAr
     sum4_store(l, a.rows, e_c, e_lj, 0.0, 0.0);
 }
 
+// the same two launches with Ewald summation on (tgnh_set_nonbonded_ewald): the Coulomb part of a pair is the erfc term.  The energy
+// launch also leaves the two numbers of the call's box that tgnh_get_ewald_energy needs: it is the one launch every call makes
+__global__ __launch_bounds__(BLOCK) void nb_pair_ewald_kernel(const NonbondedArgs a) {
+    __shared__ NbImage img;
+    const int w = threadIdx.x >> 6, wave = blockIdx.x * NB_WAVES + w;
+    double e_c = 0.0, e_lj = 0.0;
+    if (wave < *a.n_chunks) pair_wave<false, true>(a, img, w, wave, e_c, e_lj);
+}
+
+__global__ __launch_bounds__(BLOCK) void nb_pair_ewald_energy_kernel(const NonbondedArgs a) {
+    __shared__ Sum4Lds l;
+    __shared__ NbImage img;
+    const int w = threadIdx.x >> 6, wave = blockIdx.x * NB_WAVES + w;
+    double e_c = 0.0, e_lj = 0.0;
+    if (wave < *a.n_chunks) pair_wave<true, true>(a, img, w, wave, e_c, e_lj);
+    sum4_store(l, a.rows, e_c, e_lj, 0.0, 0.0);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const double V = (a.box[0] * a.box[1]) * a.box[2];
+        a.ew_misc[0] = -(a.bg_num / V);
+        a.ew_misc[1] = (4.0 * (NB_PI * NB_COULOMB)) / V;
+    }
+}
+
 // An evaluated exception (p1, p2; chargeProd, sigma, epsilon), for the receiving slot at `role`:
 //   d = x(receiver) - x(other), r2 = (dx^2 + dy^2) + dz^2, r = sqrt(r2), inv = 1 / r, qq = K chargeProd, e4 = 4 epsilon,
 //   s2 = (sigma sigma) / r2, s6 = (s2 s2) s2, s12 = s6 s6, dc = qq (-(inv inv)), dl = (e4 (6 s6 - 12 s12)) inv, c = -((dc + dl) inv)
@@ -291,7 +322,11 @@ hipError_t launch_nonbonded_cells(int precision, const NonbondedArgs& a, hipStre
 hipError_t launch_nonbonded_pairs(int precision, const NonbondedArgs& a, hipStream_t s) {
     if (!nb_args_ok(precision, a)) return hipErrorInvalidValue;
     const int grid = nb_pair_grid(a.n, a.ncells);
-    if (a.rows) TGNH_LAUNCH(nb_pair_energy_kernel, grid, BLOCK, 0, s, a);
+    if (a.alpha > 0.0) {
+        if (a.rows && !a.ew_misc) return hipErrorInvalidValue;
+        if (a.rows) TGNH_LAUNCH(nb_pair_ewald_energy_kernel, grid, BLOCK, 0, s, a);
+        else TGNH_LAUNCH(nb_pair_ewald_kernel, grid, BLOCK, 0, s, a);
+    } else if (a.rows) TGNH_LAUNCH(nb_pair_energy_kernel, grid, BLOCK, 0, s, a);
     else TGNH_LAUNCH(nb_pair_kernel, grid, BLOCK, 0, s, a);
     return hipGetLastError();
 }

@@ -10,7 +10,7 @@
 //
 // The rule these helpers live by is tgnh_slot_device.h's: a kernel that existed before them compiles to what it compiled to before
 // (tools/kernel_isa.py), or does not take the helper.  A new force has no such past and takes all of it.  Who takes what:
-//   exception_body (tgnh_nonbonded.hip) all of it
+//   exception_body (tgnh_nonbonded.hip), exclusion_body (tgnh_ewald.hip) all of it
 //   bonded_body, drude_force_body       Fixed3, neg, add_to_planes; the loop is written out there.  for_each_receiver gives
 //                                       bonded_forces_kernel, drude_force_kernel and drude_force_energy_kernel the same instructions
 //                                       under the same descriptor in another order (lambda or functor; table, sum and entry by value or

@@ -12,9 +12,11 @@ library's forces alone.
 
 `NonbondedForce` is OpenMM's table of charges, Lennard-Jones parameters and exceptions with its method names; `NonbondedForces` hands
 it to a handle (tgnh_set_nonbonded_force: CutoffPeriodic with a reaction field, over cell lists) and is a force call-out too:
-`BondedForces(ctx, ...).then(lambda c: nb.compute())`.
+`BondedForces(ctx, ...).then(lambda c: nb.compute())`.  A table whose method is `Ewald` is handed over as CutoffPeriodic followed by
+tgnh_set_nonbonded_ewald: an explicit reciprocal sum, O(n M), for boxes of up to a few ten thousand slots (PME is not built).
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -256,9 +258,9 @@ class _NonbondedDesc(C.Structure):
 
 class NonbondedForce:
     """OpenMM's NonbondedForce as a table: per particle (charge e, sigma nm, epsilon kJ/mol), exceptions (p1, p2, chargeProd, sigma,
-    epsilon), the method, the cutoff and the reaction field's dielectric.  The library takes CutoffPeriodic only (the other
-    methods are refused by tgnh_set_nonbonded_force, not here)."""
-    NoCutoff, CutoffNonPeriodic, CutoffPeriodic = 0, 1, 2        # OpenMM's numbering
+    epsilon), the method, the cutoff and the reaction field's dielectric.  The library takes CutoffPeriodic, and Ewald through
+    NonbondedForces (the other methods are refused by tgnh_set_nonbonded_force, not here)."""
+    NoCutoff, CutoffNonPeriodic, CutoffPeriodic, Ewald = 0, 1, 2, 3      # OpenMM's numbering
 
     def __init__(self):
         self._particles = []         # [charge, sigma, epsilon]
@@ -267,6 +269,8 @@ class NonbondedForce:
         self._method = self.NoCutoff                             # OpenMM's defaults
         self._cutoff = 1.0
         self._dielectric = 78.3
+        self._ewald_tolerance = 5e-4
+        self._ewald = (0.0, 0, 0, 0)                             # alpha, kmaxx, kmaxy, kmaxz; all zero: derived from the tolerance
 
     # --- particles ---
     def getNumParticles(self):
@@ -343,7 +347,7 @@ class NonbondedForce:
         return self._method
 
     def setNonbondedMethod(self, method):
-        if method not in (self.NoCutoff, self.CutoffNonPeriodic, self.CutoffPeriodic):
+        if method not in (self.NoCutoff, self.CutoffNonPeriodic, self.CutoffPeriodic, self.Ewald):
             raise ValueError("NonbondedForce: Illegal value for nonbonded method")
         self._method = int(method)
 
@@ -359,6 +363,39 @@ class NonbondedForce:
     def setReactionFieldDielectric(self, dielectric):
         self._dielectric = float(dielectric)
 
+    # --- Ewald summation ---
+    def getEwaldErrorTolerance(self):
+        return self._ewald_tolerance
+
+    def setEwaldErrorTolerance(self, tol):
+        self._ewald_tolerance = float(tol)
+
+    def getEwaldParameters(self):
+        return self._ewald
+
+    def setEwaldParameters(self, alpha, kmaxx, kmaxy, kmaxz):
+        """alpha (nm^-1) and the largest reciprocal index per axis; all zero: ewald_parameters derives them from the tolerance"""
+        self._ewald = (float(alpha), int(kmaxx), int(kmaxy), int(kmaxz))
+
+    def ewald_parameters(self, box):
+        """-> (alpha, kmaxx, kmaxy, kmaxz) for a box given as three edges or three vectors (nm): what setEwaldParameters holds, or,
+        where that is all zero, OpenMM's rule from the error tolerance and the cutoff as recalled (OpenMM was not at hand to check
+        against): alpha = sqrt(-ln(2 tol)) / rc, and kmax_d the smallest k >= 1 with
+        k sqrt(L_d alpha) / 20 exp(-(pi k / (L_d alpha))^2) <= tol.  The rule is a heuristic, not a bound."""
+        if self._ewald != (0.0, 0, 0, 0):
+            return self._ewald
+        box = np.asarray(box, np.float64)
+        edges = np.diag(box) if box.ndim == 2 else box
+        tol = self._ewald_tolerance
+        alpha = math.sqrt(-math.log(2.0 * tol)) / self._cutoff
+        kmax = []
+        for edge in edges:
+            k = 1
+            while k * math.sqrt(edge * alpha) / 20.0 * math.exp(-(math.pi * k / (edge * alpha)) ** 2) > tol:
+                k += 1
+            kmax.append(k)
+        return (alpha, kmax[0], kmax[1], kmax[2])
+
     # --- the table as tgnh_set_nonbonded_force takes it ---
     def tables(self):
         """-> (method, cutoff, dielectric, particles [n, 3] float64, exception_particles [ne, 2] int32, exception_params [ne, 3] float64)"""
@@ -373,15 +410,33 @@ class NonbondedForces(_ForceCallOut):
     the handle (it replaces the one in force); a shape that does not fit is refused here, before any library call.  The box is the
     handle's (setPeriodicBoxVectors).  An instance is a force call-out, and `BondedForces(ctx, ...).then(lambda c: nb.compute())`
     adds it behind the bonded forces.  energy(): (pair Coulomb with the reaction field, pair Lennard-Jones, exception Coulomb,
-    exception Lennard-Jones)."""
+    exception Lennard-Jones).
+
+    Ewald summation (tgnh_set_nonbonded_ewald): a NonbondedForce whose method is Ewald is handed over as CutoffPeriodic and Ewald is
+    switched on behind it, with `ewald` = (alpha, kmaxx, kmaxy, kmaxz) if given, otherwise force.ewald_parameters(the owner's box) --
+    an owner without a box is refused with ERR_STATE before any library call.  `ewald` beside a CutoffPeriodic table switches it on
+    as well; a raw tuple whose method is 3 is refused by the library as before.  `ewald`: (alpha, (kx, ky, kz), M) or None;
+    ewald_energy(): (reciprocal, self, neutralising background, exclusion correction); energy()[0] is then the direct-space sum."""
     _COMPUTE, _ENERGY, _ENERGY_WIDTH = "tgnh_compute_nonbonded_force", "tgnh_get_nonbonded_energy", 4
 
-    def __init__(self, owner, force=None):
+    def __init__(self, owner, force=None, ewald=None):
         self.owner = owner
         if force is None:
             self.clear()
             return
         table = force.tables() if hasattr(force, "tables") else force
+        if hasattr(force, "tables") and len(table) == 6 and int(table[0]) == NonbondedForce.Ewald:
+            if ewald is None:
+                box = owner.getPeriodicBoxVectors()
+                if box is None:
+                    raise TgnhError(_lib.ERR_STATE, "set_nonbonded_force: the Ewald parameters come from the box, and the owner has none: "
+                                                    "call setPeriodicBoxVectors first, or pass ewald=(alpha, kmaxx, kmaxy, kmaxz)")
+                ewald = force.ewald_parameters(box)
+            table = (NonbondedForce.CutoffPeriodic,) + tuple(table[1:])
+        if ewald is not None:
+            ewald = tuple(ewald)
+            if len(ewald) != 4:
+                raise TgnhError(_lib.ERR_ARG, f"set_nonbonded_force: ewald: (alpha, kmaxx, kmaxy, kmaxz), got {len(ewald)} values")
         if len(table) != 6:
             raise TgnhError(_lib.ERR_ARG, f"set_nonbonded_force: a method, a cutoff, a dielectric and three arrays, got {len(table)} values")
         method, cutoff, dielectric = int(table[0]), float(table[1]), float(table[2])
@@ -396,6 +451,31 @@ class NonbondedForces(_ForceCallOut):
         d = _NonbondedDesc(C.sizeof(_NonbondedDesc), method, cutoff, dielectric, len(par), par.ctypes.data if len(par) else None,
                            ne, ep.ctypes.data if ne else None, ex.ctypes.data if ne else None)
         _check(owner.lib.tgnh_set_nonbonded_force(owner.h, C.byref(d)))
+        if ewald is not None:
+            self.set_ewald(*ewald)
+
+    def set_ewald(self, alpha, kmaxx, kmaxy, kmaxz):
+        """tgnh_set_nonbonded_ewald on the table in force"""
+        e = _lib.TgnhEwaldDesc(C.sizeof(_lib.TgnhEwaldDesc), (C.c_int32 * 3)(int(kmaxx), int(kmaxy), int(kmaxz)), float(alpha))
+        _check(self.owner.lib.tgnh_set_nonbonded_ewald(self.owner.h, C.byref(e)))
+
+    def clear_ewald(self):
+        """back to the reaction field"""
+        _check(self.owner.lib.tgnh_set_nonbonded_ewald(self.owner.h, None))
+
+    @property
+    def ewald(self):
+        """tgnh_get_nonbonded_ewald: (alpha, (kmaxx, kmaxy, kmaxz), M reciprocal vectors) of the setting in force, None: off"""
+        e, m = _lib.TgnhEwaldDesc(), C.c_int(0)
+        _check(self.owner.lib.tgnh_get_nonbonded_ewald(self.owner.h, C.byref(e), C.byref(m)))
+        return (float(e.alpha), tuple(e.kmax), int(m.value)) if e.struct_size else None
+
+    def ewald_energy(self):
+        """tgnh_get_ewald_energy: (reciprocal, self, neutralising background, exclusion correction) in kJ/mol, of the positions the
+        last compute(energy=True) read.  Synchronises."""
+        out = (C.c_double * 4)()
+        _check(self.owner.lib.tgnh_get_ewald_energy(self.owner.h, self.owner._stream(), out))
+        return tuple(float(v) for v in out)
 
     @property
     def num_terms(self):
