@@ -1184,8 +1184,8 @@ tgnh_status tgnh_compute_nonbonded_force(tgnh_handle h, void* force, int want_en
 tgnh_status tgnh_get_nonbonded_energy(tgnh_handle h, void* stream, double out[4]);      /* pair Coulomb (with reaction field), pair LJ, exception Coulomb, exception LJ; synchronises */
 
 /* EWALD SUMMATION on top of the table above: OpenMM's `Ewald` method, an explicit sum over reciprocal vectors with no FFT.  The cost is
- * O(n M), M the number of reciprocal vectors: it suits boxes of up to a few ten thousand slots, and is what a later PME is checked
- * against; PME is NOT BUILT.  tgnh_set_nonbonded_force's descriptor, checks and texts are unchanged (methods 3, 4, 5 are refused there
+ * O(n M), M the number of reciprocal vectors: it suits boxes of up to a few ten thousand slots, and is what PME (PARTICLE-MESH EWALD
+ * below) is checked against.  tgnh_set_nonbonded_force's descriptor, checks and texts are unchanged (methods 3, 4, 5 are refused there
  * as before): Ewald is switched on by tgnh_set_nonbonded_ewald while a CutoffPeriodic table is in force, and every
  * tgnh_set_nonbonded_force, a clearing one included, drops the setting again.  With no Ewald setting nothing below is allocated or
  * launched, and tgnh_compute_nonbonded_force is what it was, launch for launch and bit for bit.
@@ -1193,7 +1193,7 @@ tgnh_status tgnh_get_nonbonded_energy(tgnh_handle h, void* stream, double out[4]
  * tgnh_set_nonbonded_ewald(desc).  desc == NULL: back to the reaction field.  Every check runs before any device work, so a host-only
  * handle gives the same answers.  TGNH_ERR_STATE: no nonbonded table is set.  TGNH_ERR_ARG, with the reason in tgnh_last_error(): a
  * struct_size that is not sizeof(tgnh_ewald_desc); an alpha that is not finite or <= 0; a kmax component < 0 or > 255.
- * TGNH_ERR_UNSUPPORTED: M > 2^20.  A refused call leaves whatever was in force untouched.  The reciprocal vectors are the (nx, ny, nz)
+ * TGNH_ERR_UNSUPPORTED: M > 2^20 (tgnh_set_nonbonded_pme is for that).  A refused call leaves whatever was in force untouched.  The reciprocal vectors are the (nx, ny, nz)
  * != 0 with |n_d| <= kmax_d whose first non-zero component is positive, a half space of
  *   M = ((2 kmax_x + 1)(2 kmax_y + 1)(2 kmax_z + 1) - 1) / 2
  * vectors, stored in the order nx, then ny, then nz, ascending; kmax = (0, 0, 0) is legal and means no reciprocal part.  Not inside a
@@ -1260,6 +1260,72 @@ typedef struct tgnh_ewald_desc {
 tgnh_status tgnh_set_nonbonded_ewald(tgnh_handle h, const tgnh_ewald_desc* d);          /* NULL: back to the reaction field */
 tgnh_status tgnh_get_nonbonded_ewald(tgnh_handle h, tgnh_ewald_desc* out, int* num_kvectors);   /* struct_size 0 in *out: off */
 tgnh_status tgnh_get_ewald_energy(tgnh_handle h, void* stream, double out[4]);          /* reciprocal, self, neutralising background, exclusion correction; synchronises */
+
+/* PARTICLE-MESH EWALD: the same sum with the reciprocal part formed on a mesh (Essmann et al. 1995, OpenMM's `PME`), O(n + N log N)
+ * in the slots n and the grid points N, for boxes the explicit sum cannot reach.  PME and the explicit sum are two forms of ONE
+ * setting: each setter replaces whatever is in force, NULL to either goes back to the reaction field, and tgnh_set_nonbonded_force
+ * drops either.  Everything under DIRECT SPACE, EXCLUSION CORRECTION, E_self and E_bg above holds unchanged with PME in force; only
+ * RECIPROCAL SPACE is replaced by what follows.  With PME in force tgnh_get_nonbonded_ewald answers "off" (struct_size 0, M = 0),
+ * tgnh_get_nonbonded_pme answers alpha and the grid, and tgnh_get_ewald_energy keeps its four slots, slot 0 being the mesh sum.  With
+ * no PME setting nothing below is allocated or launched.  Nothing new is linked: the transform is the library's own.
+ *
+ * tgnh_set_nonbonded_pme(desc) follows tgnh_set_nonbonded_ewald point for point: it needs a CutoffPeriodic table in force
+ * (TGNH_ERR_STATE), runs every check before any device work (a host-only handle answers alike), builds the setting aside and moves
+ * it in whole, allocates and uploads everything the compute call will need (three grids of nx ny nz points: int64, complex fp64,
+ * fp64; per axis a table of twiddle factors and one of moduli), and refuses with TGNH_ERR_STATE when the stream of the handle's last
+ * tgnh_compute_nonbonded_force is capturing.  TGNH_ERR_ARG, with the reason in tgnh_last_error(): a struct_size that is not
+ * sizeof(tgnh_pme_desc); an alpha that is not finite or <= 0; a grid component below 6, above 256, or with a prime factor other than
+ * 2, 3, 5 (the text names the component).  TGNH_ERR_UNSUPPORTED: nx ny nz > 2^24.  The B-spline order is 5, a constant.  Formed at set
+ * time on the host, per axis with N points:
+ *   w^k      = (cos(2 pi k / N), -sin(2 pi k / N)), k < N, exact at the quarter turns: every twiddle factor of the transform is an
+ *              entry of this table, so the transform kernels make no transcendental call
+ *   |b(m)|^2 = (sum_j M(j) cos(2 pi m j / N))^2 + (sum_j M(j) sin(2 pi m j / N))^2, j = 0..3 in order, M = 1/24, 11/24, 11/24, 1/24,
+ *              the cosines and sines being the table's entries at (m j) mod N; then, for m ascending, a modulus below 1e-7 is replaced
+ *              by (|b(m - 1)|^2 + |b(m + 1)|^2) 0.5, indices mod N (OpenMM's rule: with order 5 the modulus vanishes at m = N / 2 for
+ *              every even N)
+ *   pi2 = pi pi     alpha2 = alpha alpha
+ *
+ * With PME on, tgnh_compute_nonbonded_force adds, behind the exclusion correction (fp64 in every precision, every operation rounded
+ * on its own in the order written; the only library call is the exp of G):
+ * WEIGHTS.  For slot i and an axis with N points and edge L:
+ *   s = x / L;  s = s - floor(s);  t = s N;  i0 = (int)floor(t);  u = t - floor(t)
+ *   th_0 = 1 - u, th_1 = u, th_2 = th_3 = th_4 = 0; then raise to order k for k = 3, 4:
+ *     th_(k-1) = (u th_(k-2)) / (k - 1)
+ *     th_(k-1-j) = ((u + j) th_(k-2-j) + ((k - j) - u) th_(k-1-j)) / (k - 1)      j = 1 .. k - 2
+ *     th_0 = ((1 - u) th_0) / (k - 1)
+ *   dth_0 = -th_0, dth_j = th_(j-1) - th_j (j = 1..4); then raise th to order 5 by the same three lines.
+ *   Point j of the axis is (i0 + j) mod N (t can round up to N: the mod covers it).
+ * SPREADING.  w = (thx_a thy_b) thz_c; grid point (a, b, c) of the slot receives llrint((q w) 281474976710656.0) (2^48) in an int64
+ * grid Q[z][y][x] that the call clears first.  Integer adds commute: Q's bits depend on neither the order of arrival nor the order
+ * of the slots.  A slot with q == 0 contributes nothing.  RANGE: a grid point holds up to 2^15 e of |q w|.
+ * INFLUENCE FUNCTION.  For grid index m_d in [0, N_d): n_d = m_d if m_d <= N_d / 2 (integer division), else m_d - N_d;
+ *   h_d = n_d / L_d;  m2 = (hx hx + hy hy) + hz hz;  V = (Lx Ly) Lz
+ *   G = exp(-((pi2 m2) / alpha2)) / (((pi V) m2) ((|bx|^2 |by|^2) |bz|^2));  G(0, 0, 0) = 0
+ * formed on the device from the box of the call: a box that changes between calls needs no reset.
+ * TRANSFORMS.  F = DFT((double)Q 2^-48); phi = the real part of the unnormalised inverse DFT of G F.  A mixed-radix (4, 2, 3, 5)
+ * Stockham transform of whole lines in LDS, five launches: x forward, y forward, z forward x G z inverse, y inverse, x inverse.  The
+ * order of its sums depends on the grid alone; its rounding is not restated here (tests/test_pme.py measures how far an fp64 twin
+ * built on another FFT is off an fp80 reference, and gates the device with that).
+ * ENERGY.  E_rec = K sum over the z launch's work-groups of (1/2 sum_m G |F|^2), summed as the other energies' rows are.
+ * FORCE.  g_d = sum over c (outermost), b, a (innermost) of (dth (in d) th th) phi, the product grouped as w is; slot i receives
+ *   llrint((-(((K q_i) (N_d / L_d)) g_d)) 4294967296.0) once per component; a slot with charge 0 receives nothing.
+ * PME does not conserve momentum exactly: the sum of the reciprocal forces falls with the grid spacing, it is not zero.
+ * ORDER.  No floating-point atomic anywhere; the only atomics are the integer adds of the spreading.  The same positions, box and
+ * tables give the same bits from a tiled, a TGNH_FLAG_GATHER and a DUALNH handle, asked once or twice, run eagerly or replayed from
+ * a graph, and -- Q being a sum of integers and everything behind it a function of Q -- a permutation of the slots permutes the
+ * force bits and leaves Q and phi alone.
+ * LAUNCHES.  Behind the exclusion kernel: a memset of Q and seven kernels (spread, five transform launches, gather).  Capturable.
+ * tgnh_get_pme_grids: host copies of the last call's Q and phi, [nz][ny][nx], either pointer may be NULL; synchronises `stream`.
+ * TGNH_ERR_STATE: PME is off; no tgnh_compute_nonbonded_force has run since it was set (a call recorded into a capture has not run);
+ * a host-only handle, buffers not bound. */
+typedef struct tgnh_pme_desc {
+    uint32_t struct_size;             /* sizeof(tgnh_pme_desc); anything else: TGNH_ERR_ARG */
+    int32_t grid[3];                  /* nx, ny, nz: each in [6, 256] with prime factors 2, 3, 5 only; nx ny nz <= 2^24 */
+    double alpha;                     /* nm^-1 */
+} tgnh_pme_desc;
+tgnh_status tgnh_set_nonbonded_pme(tgnh_handle h, const tgnh_pme_desc* d);              /* NULL: back to the reaction field */
+tgnh_status tgnh_get_nonbonded_pme(tgnh_handle h, tgnh_pme_desc* out);                  /* struct_size 0 in *out: off */
+tgnh_status tgnh_get_pme_grids(tgnh_handle h, void* stream, long long* charge, double* potential);   /* either may be NULL; [nz][ny][nx]; synchronises */
 
 /* The call-outs of the reference's own testWater (platforms/reference/tests/TestReferenceDrudeTGNHIntegrator.cpp:111-166),
  * harness only: its force field -- NonbondedForce with reaction field, cutoff `cutoff` in a cubic box of edge `box`, +

@@ -97,6 +97,11 @@ class TgnhEwaldDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kmax", C.c_int32 * 3), ("alpha", C.c_double)]
 
 
+class TgnhPmeDesc(C.Structure):
+    """tgnh_pme_desc (tgnh_set_nonbonded_pme)"""
+    _fields_ = [("struct_size", C.c_uint32), ("grid", C.c_int32 * 3), ("alpha", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p)
 
 # name -> (restype, argtypes); every symbol include/drude_tgnh.h declares
@@ -219,6 +224,10 @@ SIGNATURES = {
     "tgnh_set_nonbonded_ewald": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tgnh_get_nonbonded_ewald": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "tgnh_get_ewald_energy": (C.c_int, [C.c_void_p, C.c_void_p, c_f64p]),
+    # (desc / out: a TgnhPmeDesc by reference; charge / potential: host arrays of nx ny nz int64 / float64, or None)
+    "tgnh_set_nonbonded_pme": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tgnh_get_nonbonded_pme": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tgnh_get_pme_grids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tgnh_harness_water_force": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "tgnh_harness_remove_cm_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tgnh_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),

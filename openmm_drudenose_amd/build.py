@@ -13,10 +13,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdrudetgnh_hip.so")
 SOURCES = ["tgnh_topology.cpp", "tgnh_lifecycle.cpp", "tgnh_exchange.cpp", "tgnh_step.cpp", "tgnh_velocities.cpp", "tgnh_queries.cpp", "tgnh_harness_host.cpp", "tgnh_positions.cpp",
-           "tgnh_frames.cpp", "tgnh_minimize.cpp", "tgnh_constraints.cpp", "tgnh_virtual_sites.cpp", "tgnh_drude_force.cpp", "tgnh_bonded.cpp", "tgnh_nonbonded.cpp", "tgnh_ewald.cpp",
+           "tgnh_frames.cpp", "tgnh_minimize.cpp", "tgnh_constraints.cpp", "tgnh_virtual_sites.cpp", "tgnh_drude_force.cpp", "tgnh_bonded.cpp", "tgnh_nonbonded.cpp", "tgnh_ewald.cpp", "tgnh_pme.cpp",
            "tgnh_kernels.hip", "tgnh_gather.hip", "tgnh_harness.hip", "tgnh_velinit.hip", "tgnh_drude_stats.hip", "tgnh_cm_motion.hip",
            "tgnh_rescale.hip", "tgnh_scale_positions.hip", "tgnh_wrap.hip", "tgnh_minimize.hip", "tgnh_constraints.hip",
-           "tgnh_virtual_sites.hip", "tgnh_drude_force.hip", "tgnh_bonded.hip", "tgnh_nonbonded.hip", "tgnh_ewald.hip", "tgnh_vplanes.hip"]
+           "tgnh_virtual_sites.hip", "tgnh_drude_force.hip", "tgnh_bonded.hip", "tgnh_nonbonded.hip", "tgnh_ewald.hip", "tgnh_pme.hip", "tgnh_vplanes.hip"]
 # every header of csrc/ (read off the directory, as source_sha does: a new header cannot leave a stale object behind) and the ABI header
 HEADERS = sorted(n for n in os.listdir(CSRC) if n.endswith(".h")) + [os.path.join("..", "..", "include", "drude_tgnh.h")]
 ARCH = "gfx950"

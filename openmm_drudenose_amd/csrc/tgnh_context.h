@@ -262,6 +262,16 @@ struct tgnh_context {
         tgnh::DeviceBuf<double> d_exc_rows;       // [index_grid(recv.n)][4]
         tgnh::DeviceBuf<double> d_misc;           // [2] {E_bg, (4 (pi K)) / V} of the last want_energy call's box
         tgnh::DeviceBuf<double> d_totals;         // [4] where the energy's sum lands
+        // the other form of the setting: tgnh_set_nonbonded_pme (tgnh_pme.cpp).  `on` with pme: the mesh forms the reciprocal part, vectors == 0
+        bool pme = false;
+        int grid[3] = {0, 0, 0};                  // nx, ny, nz   (a host-only handle keeps these two lines and nothing below)
+        double pi2 = 0, alpha2 = 0;               // pi pi, alpha alpha
+        bool grids_filled = false;                // an eager tgnh_compute_nonbonded_force has run since PME was set
+        tgnh::DeviceBuf<long long> d_charge;      // [nz][ny][nx] the spread charges x 2^48
+        tgnh::DeviceBuf<double2> d_work;          // [nz][ny][nx] the transforms' complex grid
+        tgnh::DeviceBuf<double> d_potential;      // [nz][ny][nx] phi
+        tgnh::DeviceBuf<double2> d_twiddle[3];    // [N_d] w^k
+        tgnh::DeviceBuf<double> d_modulus[3];     // [N_d] |b_d(m)|^2      (d_rec_rows: [pme_fft_grid(grid, 2)][4])
     } ewald;
     struct Thermostat {               // dof bookkeeping (A2) and the thermostat block
         std::vector<double> h_state;      // host copy of the initial thermostat block

@@ -48,8 +48,10 @@ struct EwaldExclusionArgs {
 hipError_t launch_ewald_exclusions(int precision, const EwaldExclusionArgs& a, hipStream_t s);
 hipError_t launch_ewald_reciprocal(int precision, const EwaldArgs& a, hipStream_t s, int stage /* 0 sum, 1 finalise, 2 force */);
 // rec rows [0, n_rec) (may be 0) and exclusion rows [0, n_exc) (may be 0) -> out[4] = misc[1] x the rec rows' sum, e_self, misc[0],
-// the exclusion rows' sum; misc = {E_bg, 4 pi K / V} as the pair launch of the call left them
-hipError_t launch_ewald_energy_sum(const double* rec_rows, int n_rec, const double* exc_rows, int n_exc, const double* misc, double e_self,
+// the exclusion rows' sum; misc = {E_bg, 4 pi K / V} as the pair launch of the call left them.  rec_scale != 0 (the mesh sum's rows,
+// tgnh_pme.h: one per work-group of its z launch, up to 2^16 / 8 of them): that factor in the place of misc[1]
+constexpr int EW_MAX_REC_ROWS = 8192;
+hipError_t launch_ewald_energy_sum(const double* rec_rows, int n_rec, double rec_scale, const double* exc_rows, int n_exc, const double* misc, double e_self,
                                    double* out, hipStream_t s);
 
 }  // namespace tgnh

@@ -36,13 +36,6 @@ __device__ __forceinline__ void ew_wave_sync() {
 }
 
 struct EwImage { double v[NB_WAVES][4][64]; };                 // 8 KiB a work-group; each wavefront its own
-
-// cell_coord's two lines: the fractional coordinate in [0, 1)
-__device__ __forceinline__ double frac_coord(const double x, const double L) {
-    double s = x / L;
-    s = s - floor(s);
-    return s;
-}
 }  // namespace
 
 template <int PREC>
@@ -186,7 +179,7 @@ __global__ __launch_bounds__(BLOCK) void ew_exclusion_energy_kernel(const EwaldE
 }
 
 // One work-group, a thread its chunk of each kind of row (row_chunk)
-__global__ __launch_bounds__(BLOCK) void ew_energy_sum_kernel(const double* __restrict__ rec_rows, const int n_rec, const double* __restrict__ exc_rows,
+__global__ __launch_bounds__(BLOCK) void ew_energy_sum_kernel(const double* __restrict__ rec_rows, const int n_rec, const double rec_scale, const double* __restrict__ exc_rows,
                                                               const int n_exc, const double* __restrict__ misc, const double e_self,
                                                               double* __restrict__ out) {
     __shared__ Sum4Lds l;
@@ -200,7 +193,7 @@ __global__ __launch_bounds__(BLOCK) void ew_energy_sum_kernel(const double* __re
     __syncthreads();
     if (threadIdx.x < 4) {
         const double total = sum4_total(l);
-        out[threadIdx.x] = threadIdx.x == 0 ? misc[1] * total : (threadIdx.x == 1 ? e_self : (threadIdx.x == 2 ? misc[0] : total));
+        out[threadIdx.x] = threadIdx.x == 0 ? (rec_scale != 0.0 ? rec_scale : misc[1]) * total : (threadIdx.x == 1 ? e_self : (threadIdx.x == 2 ? misc[0] : total));
     }
 }
 
@@ -229,11 +222,11 @@ hipError_t launch_ewald_reciprocal(int precision, const EwaldArgs& a, hipStream_
     return hipGetLastError();
 }
 
-hipError_t launch_ewald_energy_sum(const double* rec_rows, int n_rec, const double* exc_rows, int n_exc, const double* misc, double e_self,
+hipError_t launch_ewald_energy_sum(const double* rec_rows, int n_rec, double rec_scale, const double* exc_rows, int n_exc, const double* misc, double e_self,
                                    double* out, hipStream_t s) {
-    if (!misc || !out || n_rec < 0 || n_exc < 0 || (n_rec > 0 && !rec_rows) || (n_exc > 0 && !exc_rows) || n_rec > INDEX_GRID_CAP || n_exc > INDEX_GRID_CAP)
+    if (!misc || !out || n_rec < 0 || n_exc < 0 || (n_rec > 0 && !rec_rows) || (n_exc > 0 && !exc_rows) || n_rec > EW_MAX_REC_ROWS || n_exc > INDEX_GRID_CAP)
         return hipErrorInvalidValue;
-    TGNH_LAUNCH(ew_energy_sum_kernel, 1, BLOCK, 0, s, rec_rows, n_rec, exc_rows, n_exc, misc, e_self, out);
+    TGNH_LAUNCH(ew_energy_sum_kernel, 1, BLOCK, 0, s, rec_rows, n_rec, rec_scale, exc_rows, n_exc, misc, e_self, out);
     return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // tgnh_host.h -- what the host units behind the C ABI (include/drude_tgnh.h) share: tgnh_topology.cpp, tgnh_lifecycle.cpp,
-// tgnh_exchange.cpp, tgnh_step.cpp, tgnh_velocities.cpp, tgnh_queries.cpp, tgnh_positions.cpp, tgnh_frames.cpp, tgnh_minimize.cpp, tgnh_constraints.cpp, tgnh_virtual_sites.cpp, tgnh_drude_force.cpp, tgnh_bonded.cpp, tgnh_nonbonded.cpp, tgnh_ewald.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
+// tgnh_exchange.cpp, tgnh_step.cpp, tgnh_velocities.cpp, tgnh_queries.cpp, tgnh_positions.cpp, tgnh_frames.cpp, tgnh_minimize.cpp, tgnh_constraints.cpp, tgnh_virtual_sites.cpp, tgnh_drude_force.cpp, tgnh_bonded.cpp, tgnh_nonbonded.cpp, tgnh_ewald.cpp, tgnh_pme.cpp, tgnh_harness_host.cpp (each says at its top what it holds).  Kernels
 // live in tgnh_kernels.hip (tgnh_tile_kernels.h, tgnh_wave_kernels.h, tgnh_chain_kernels.h), tgnh_gather.hip, tgnh_velinit.hip,
-// tgnh_drude_stats.hip, tgnh_cm_motion.hip, tgnh_rescale.hip, tgnh_scale_positions.hip, tgnh_wrap.hip, tgnh_minimize.hip, tgnh_constraints.hip, tgnh_virtual_sites.hip, tgnh_drude_force.hip, tgnh_bonded.hip, tgnh_nonbonded.hip, tgnh_ewald.hip, tgnh_vplanes.hip and tgnh_harness.hip.
+// tgnh_drude_stats.hip, tgnh_cm_motion.hip, tgnh_rescale.hip, tgnh_scale_positions.hip, tgnh_wrap.hip, tgnh_minimize.hip, tgnh_constraints.hip, tgnh_virtual_sites.hip, tgnh_drude_force.hip, tgnh_bonded.hip, tgnh_nonbonded.hip, tgnh_ewald.hip, tgnh_pme.hip, tgnh_vplanes.hip and tgnh_harness.hip.
 // The library's forces (virtual sites, DrudeForce, bonded, the nonbonded exceptions) share one form, said once: the table of receiving
 // slots and its inversion in tgnh_receivers.h, its owner in tgnh_context.h (Receivers), the lane's loop in tgnh_receiver_device.h.
 //
@@ -72,6 +72,12 @@ tgnh_status flush_impl(tgnh_handle h, hipStream_t s);
 tgnh_status ke_query_launches(tgnh_handle h, hipStream_t s);    // tgnh_queries.cpp: what tgnh_compute_kinetic_energies enqueues behind its entry checks
 tgnh_status cm_removal_due(tgnh_handle h, hipStream_t s);      // tgnh_velocities.cpp: tgnh_set_cm_motion_removal's launches where this step is due; a step begins with this
 tgnh_status rescale_due(tgnh_handle h, hipStream_t s);         // ... and then with tgnh_set_velocity_rescaling's
+// tgnh_ewald.cpp: what tgnh_set_nonbonded_ewald and tgnh_set_nonbonded_pme share
+tgnh_status ewald_set_begin(tgnh_handle h, const char* me, bool clear, bool* done);       // the capture refusal, the clearing call, the table that must be in force
+void ewald_set_constants(tgnh_context::Ewald& e, double alpha);                           // on, alpha, tsp, a4
+tgnh_status ewald_set_shared(tgnh_handle h, tgnh_context::Ewald& e);                      // E_self, bgn, the exclusion rows and their receiver table, misc, totals
+// tgnh_pme.cpp: tgnh_compute_nonbonded_force's launches with particle-mesh Ewald on; L the edges of the call's box
+tgnh_status pme_launches(tgnh_handle h, const double L[3], void* force, int want_energy, hipStream_t s);
 // tgnh_positions.cpp
 tgnh_status molecules_ensure(tgnh_context* c, const char* what);              // the table in force: the caller's, or the default resolved now (TGNH_ERR_STATE: no resid)
 tgnh_status molecules_launch_bounds(const tgnh_context* c);                   // what the launches over the table are bound by, against what the tables hold

@@ -2,7 +2,8 @@
 // exclusion lists per slot, the evaluated exceptions' shares by receiving slot), tgnh_compute_nonbonded_force (the box's checks,
 // the cell grid, the per-cell buffers, the launches) and tgnh_get_nonbonded_energy (tgnh_nonbonded.hip has the kernels;
 // include/drude_tgnh.h the contract).  With Ewald summation on (tgnh_set_nonbonded_ewald, tgnh_ewald.cpp) the compute call hands the pair
-// launch alpha and adds tgnh_ewald.hip's launches behind the exceptions.
+// launch alpha and adds tgnh_ewald.hip's launches behind the exceptions, and with PME on (tgnh_set_nonbonded_pme, tgnh_pme.cpp) that
+// unit's behind those.
 #include <climits>
 
 #include "tgnh_host.h"
@@ -230,6 +231,7 @@ extern "C" tgnh_status tgnh_compute_nonbonded_force(tgnh_handle h, void* force, 
             HIP_OK(launch_ewald_reciprocal(h->d.precision, r, s, stage));
         }
     }
+    if (ew.on && ew.pme) { rc = pme_launches(h, L, force, want_energy, s); if (rc) return rc; }
     // (a launch recorded into a stream capture has not run: it fills the rows when the graph is replayed, and does not count here)
     if (want_energy && !stream_capturing(s)) { f.energy_launched = true; f.energy_rows = nb_pair_grid(n, a.ncells); ew.energy_launched = ew.on; }
     return TGNH_OK;

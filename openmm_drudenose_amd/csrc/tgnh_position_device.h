@@ -29,5 +29,12 @@ __device__ __forceinline__ Vec3 slot_position(const void* posq, const void* corr
     return x;
 }
 
+// cell_coord's two lines: the fractional coordinate in [0, 1) (the reciprocal sums of tgnh_ewald.hip and tgnh_pme.hip)
+__device__ __forceinline__ double frac_coord(const double x, const double L) {
+    double s = x / L;
+    s = s - floor(s);
+    return s;
+}
+
 }  // namespace tgnh
 #endif

@@ -271,6 +271,7 @@ class NonbondedForce:
         self._dielectric = 78.3
         self._ewald_tolerance = 5e-4
         self._ewald = (0.0, 0, 0, 0)                             # alpha, kmaxx, kmaxy, kmaxz; all zero: derived from the tolerance
+        self._pme = (0.0, 0, 0, 0)                               # alpha, nx, ny, nz; all zero: derived from the tolerance
 
     # --- particles ---
     def getNumParticles(self):
@@ -396,6 +397,40 @@ class NonbondedForce:
             kmax.append(k)
         return (alpha, kmax[0], kmax[1], kmax[2])
 
+    # --- particle-mesh Ewald ---
+    def getPMEParameters(self):
+        return self._pme
+
+    def setPMEParameters(self, alpha, nx, ny, nz):
+        """alpha (nm^-1) and the grid; all zero: pme_parameters derives them from the tolerance"""
+        self._pme = (float(alpha), int(nx), int(ny), int(nz))
+
+    def pme_parameters(self, box):
+        """-> (alpha, nx, ny, nz) for a box given as three edges or three vectors (nm): what setPMEParameters holds, or, where that
+        is all zero, OpenMM's rule from the error tolerance and the cutoff as recalled (OpenMM was not at hand to check against):
+        alpha = sqrt(-ln(2 tol)) / rc, and N_d = ceil(2 alpha L_d / (3 tol^(1/5))), at least 6, raised to the next size whose prime
+        factors are 2, 3 and 5 only.  The rule is a heuristic, not a bound."""
+        if self._pme != (0.0, 0, 0, 0):
+            return self._pme
+        box = np.asarray(box, np.float64)
+        edges = np.diag(box) if box.ndim == 2 else box
+        tol = self._ewald_tolerance
+        alpha = math.sqrt(-math.log(2.0 * tol)) / self._cutoff
+        grid = []
+        for edge in edges:
+            n = max(6, int(math.ceil(2.0 * alpha * edge / (3.0 * tol ** 0.2))))
+            while not self._smooth(n):
+                n += 1
+            grid.append(n)
+        return (alpha, grid[0], grid[1], grid[2])
+
+    @staticmethod
+    def _smooth(n):
+        for r in (2, 3, 5):
+            while n % r == 0:
+                n //= r
+        return n == 1
+
     # --- the table as tgnh_set_nonbonded_force takes it ---
     def tables(self):
         """-> (method, cutoff, dielectric, particles [n, 3] float64, exception_particles [ne, 2] int32, exception_params [ne, 3] float64)"""
@@ -416,17 +451,37 @@ class NonbondedForces(_ForceCallOut):
     switched on behind it, with `ewald` = (alpha, kmaxx, kmaxy, kmaxz) if given, otherwise force.ewald_parameters(the owner's box) --
     an owner without a box is refused with ERR_STATE before any library call.  `ewald` beside a CutoffPeriodic table switches it on
     as well; a raw tuple whose method is 3 is refused by the library as before.  `ewald`: (alpha, (kx, ky, kz), M) or None;
-    ewald_energy(): (reciprocal, self, neutralising background, exclusion correction); energy()[0] is then the direct-space sum."""
+    ewald_energy(): (reciprocal, self, neutralising background, exclusion correction); energy()[0] is then the direct-space sum.
+
+    Particle-mesh Ewald (tgnh_set_nonbonded_pme), the other form of the same setting: `pme` = (alpha, nx, ny, nz) switches it on
+    behind the table, whether the table's method is CutoffPeriodic or Ewald; `pme=True` takes force.pme_parameters(the owner's box)
+    -- an owner without a box is refused with ERR_STATE before any library call.  `ewald` and `pme` together: ERR_ARG.  `pme`:
+    (alpha, (nx, ny, nz)) or None; with it in force `ewald` is None and ewald_energy()[0] is the mesh sum; pme_grids(): the last
+    call's charge grid (int64, x 2^48) and potential, [nz, ny, nx]."""
     _COMPUTE, _ENERGY, _ENERGY_WIDTH = "tgnh_compute_nonbonded_force", "tgnh_get_nonbonded_energy", 4
 
-    def __init__(self, owner, force=None, ewald=None):
+    def __init__(self, owner, force=None, ewald=None, pme=None):
         self.owner = owner
         if force is None:
             self.clear()
             return
+        if ewald is not None and pme is not None:
+            raise TgnhError(_lib.ERR_ARG, "set_nonbonded_force: ewald= and pme= are two forms of one setting: pass one of them")
         table = force.tables() if hasattr(force, "tables") else force
+        if pme is True:
+            if not hasattr(force, "pme_parameters"):
+                raise TgnhError(_lib.ERR_ARG, "set_nonbonded_force: pme=True takes the parameters from a NonbondedForce; beside a tuple pass pme=(alpha, nx, ny, nz)")
+            box = owner.getPeriodicBoxVectors()
+            if box is None:
+                raise TgnhError(_lib.ERR_STATE, "set_nonbonded_force: the PME parameters come from the box, and the owner has none: "
+                                                "call setPeriodicBoxVectors first, or pass pme=(alpha, nx, ny, nz)")
+            pme = force.pme_parameters(box)
+        if pme is not None:
+            pme = tuple(pme)
+            if len(pme) != 4:
+                raise TgnhError(_lib.ERR_ARG, f"set_nonbonded_force: pme: (alpha, nx, ny, nz), got {len(pme)} values")
         if hasattr(force, "tables") and len(table) == 6 and int(table[0]) == NonbondedForce.Ewald:
-            if ewald is None:
+            if ewald is None and pme is None:
                 box = owner.getPeriodicBoxVectors()
                 if box is None:
                     raise TgnhError(_lib.ERR_STATE, "set_nonbonded_force: the Ewald parameters come from the box, and the owner has none: "
@@ -453,6 +508,35 @@ class NonbondedForces(_ForceCallOut):
         _check(owner.lib.tgnh_set_nonbonded_force(owner.h, C.byref(d)))
         if ewald is not None:
             self.set_ewald(*ewald)
+        if pme is not None:
+            self.set_pme(*pme)
+
+    def set_pme(self, alpha, nx, ny, nz):
+        """tgnh_set_nonbonded_pme on the table in force"""
+        e = _lib.TgnhPmeDesc(C.sizeof(_lib.TgnhPmeDesc), (C.c_int32 * 3)(int(nx), int(ny), int(nz)), float(alpha))
+        _check(self.owner.lib.tgnh_set_nonbonded_pme(self.owner.h, C.byref(e)))
+
+    def clear_pme(self):
+        """back to the reaction field"""
+        _check(self.owner.lib.tgnh_set_nonbonded_pme(self.owner.h, None))
+
+    @property
+    def pme(self):
+        """tgnh_get_nonbonded_pme: (alpha, (nx, ny, nz)) of the setting in force, None: off"""
+        e = _lib.TgnhPmeDesc()
+        _check(self.owner.lib.tgnh_get_nonbonded_pme(self.owner.h, C.byref(e)))
+        return (float(e.alpha), tuple(e.grid)) if e.struct_size else None
+
+    def pme_grids(self):
+        """tgnh_get_pme_grids: (charge int64 [nz, ny, nx], the spread charges x 2^48; potential float64 [nz, ny, nx]) of the last
+        compute().  Synchronises."""
+        setting = self.pme
+        if setting is None:
+            _check(self.owner.lib.tgnh_get_pme_grids(self.owner.h, self.owner._stream(), None, None))
+        nx, ny, nz = setting[1]
+        charge, potential = np.empty((nz, ny, nx), np.int64), np.empty((nz, ny, nx), np.float64)
+        _check(self.owner.lib.tgnh_get_pme_grids(self.owner.h, self.owner._stream(), charge.ctypes.data, potential.ctypes.data))
+        return charge, potential
 
     def set_ewald(self, alpha, kmaxx, kmaxy, kmaxz):
         """tgnh_set_nonbonded_ewald on the table in force"""

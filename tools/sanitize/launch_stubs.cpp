@@ -12,6 +12,7 @@
 #include "../../openmm_drudenose_amd/csrc/tgnh_bonded.h"
 #include "../../openmm_drudenose_amd/csrc/tgnh_nonbonded.h"
 #include "../../openmm_drudenose_amd/csrc/tgnh_ewald.h"
+#include "../../openmm_drudenose_amd/csrc/tgnh_pme.h"
 
 namespace tgnh {
 hipError_t launch_tile(int, int, int, const TileArgs&, int, size_t, hipStream_t) { return hipErrorNoDevice; }
@@ -50,7 +51,8 @@ hipError_t launch_nonbonded_exceptions(int, const NbExceptionArgs&, hipStream_t)
 hipError_t launch_nonbonded_energy_sum(const double*, int, const double*, int, double*, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_ewald_exclusions(int, const EwaldExclusionArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_ewald_reciprocal(int, const EwaldArgs&, hipStream_t, int) { return hipErrorNoDevice; }
-hipError_t launch_ewald_energy_sum(const double*, int, const double*, int, const double*, double, double*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_ewald_energy_sum(const double*, int, double, const double*, int, const double*, double, double*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_pme(int, const PmeArgs&, hipStream_t, int) { return hipErrorNoDevice; }
 hipError_t launch_scale_positions_spans(int, const ScalePosArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_scale_positions_table(int, const ScalePosArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_wrap_spans(int, const WrapArgs&, hipStream_t) { return hipErrorNoDevice; }
